@@ -1,13 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- point-clouds/sec, forward+backward(+SGD step), PointNet++ SSG cls, B=32 per GPU, N=1024.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement): whole-job clouds/s with inputs resident in
-HBM, `roofline` for the dominant own kernel (HIP events on the launch stream inside the timed region) and
-`cpu_baseline` (the CPU restatement of the reference semantics timed on the host cores; rank 0, N=1 only).
+Prints ONE JSON line on rank 0: whole-job clouds/s with inputs resident in HBM.  A plain run sets up, runs exactly W
+warm-up steps and K timed steps (one window, bracketed by barrier + synchronize), writes the last step's outputs with
+--dump-outputs, and prints the line.  --full adds everything else: clock-settling windows, --windows timed windows
+(median), `roofline` for the dominant own kernel (HIP events on the launch stream inside the timed region), the host
+enqueue time, `cpu_baseline` (the CPU restatement of the reference semantics timed on the host cores; rank 0, N=1 only)
+and `other_configs`.
 """
 import argparse
 import json
@@ -102,36 +105,71 @@ def cpu_baseline(state, B, N, n_steps=10, n_warm=3):
             "label": "CPU restatement of reference semantics (Jittor not runnable)"}
 
 
+def dump_outputs(path, net, out, loss):
+    """--dump-outputs: what the timed path handed back in its last step, as float32 .npy files under `path` (~12 MB at the
+    default size): that step's logits and loss, and every parameter (after its SGD update), gradient and BatchNorm buffer."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"logits": out, "loss": loss}
+    for n, p in net.named_parameters():
+        arrays[f"param.{n}"] = p
+        if p.grad is not None:
+            arrays[f"grad.{n}"] = p.grad
+    for n, b in net.named_buffers():
+        if b.is_floating_point():
+            arrays[f"buffer.{n}"] = b
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
+    full_only = []                   # (dest, flag) of the options that only take effect with --full: a plain run refuses them
+
+    def full_opt(*flags, **kw):
+        action = ap.add_argument(*flags, **kw)
+        full_only.append((action.dest, flags[0]))
+        return action
+
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5,
-                    help="consecutive timed windows of --steps steps each (every one bracketed by barrier + synchronize, MAX over ranks); "
-                         "the line reports the MEDIAN window and lists all of them")
-    ap.add_argument("--rewarm", type=int, default=10, help="untimed product-path steps between the per-kernel profiling pre-pass and the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: settling windows, several timed windows, the roofline of the dominant kernel, host "
+                         "enqueue time, the CPU baseline and the other BASELINE configs (minutes; the options below marked [full] need it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's logits, loss, parameters, gradients and BatchNorm buffers "
+                         "as float32 DIR/<name>.npy (rank 0)")
+    full_opt("--windows", type=int, default=None,
+                    help="[full] consecutive timed windows of --steps steps each (every one bracketed by barrier + synchronize, MAX over ranks); "
+                         "the line reports the MEDIAN window and lists all of them (default 5)")
+    full_opt("--rewarm", type=int, default=10, help="[full] untimed product-path steps between the per-kernel profiling pre-pass and the timed region")
     ap.add_argument("--batch", type=int, default=32, help="clouds per GPU (BASELINE config 2: 32)")
     ap.add_argument("--npoints", type=int, default=1024, help="points per cloud (1024; 4096 is the north-star extra)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", dest="other_configs", action="store_false",
-                    help="skip the short legs for BASELINE configs 1, 3, 4, 5 and config 2 on sphere_shell clouds / at N=4096 that follow the timed region (N=1 only; ~25 s)")
-    ap.add_argument("--cpu-baselines", action="store_true",
-                    help="every other_configs row also carries the CPU restatement of its own workload (tools/bench_models.py's leg: minutes; off by default so "
+    full_opt("--no-cpu-baseline", action="store_true", help="[full] skip the CPU baseline leg")
+    full_opt("--no-other-configs", dest="other_configs", action="store_false",
+                    help="[full] skip the short legs for BASELINE configs 1, 3, 4, 5 and config 2 on sphere_shell clouds / at N=4096 that follow the timed region (N=1 only; ~25 s)")
+    full_opt("--cpu-baselines", action="store_true",
+                    help="[full] every other_configs row also carries the CPU restatement of its own workload (tools/bench_models.py's leg: minutes; off by default so "
                          "that the default run stays inside a few minutes)")
-    ap.add_argument("--roofline-kernel", default="auto")
+    full_opt("--roofline-kernel", default="auto", help="[full] own entry point to event-time ('auto': the dominant one; 'none')")
     ap.add_argument("--no-prefetch-sampling", dest="prefetch_sampling", action="store_false",
                     help="run FPS/ball query inline at the head of each forward instead of one step ahead on a side stream")
-    ap.add_argument("--profile-all", action="store_true", help="print a per-entry-point event-timed table to stderr")
+    full_opt("--profile-all", action="store_true", help="[full] print a per-entry-point event-timed table to stderr")
     ap.add_argument("--dist", choices=["gauss_ball", "sphere_shell"], default="gauss_ball",
                     help="synthetic cloud distribution (SURVEY 8d): gauss_ball = the ModelNet40 loader's statistics (headline), "
                          "sphere_shell = never-saturating ball queries, ~80 %% padded duplicates")
     ap.add_argument("--dp-bucket-bytes", type=int, default=0, help="cut the gradient exchange (N>1) into buckets of this size; 0 = one all-reduce")
     ap.add_argument("--dp-overlap", action="store_true",
                     help="send gradient buckets from autograd hooks during backward (measured slower, see pointcloudlib_amd/dp.py)")
-    ap.add_argument("--no-settle", dest="settle", action="store_false", help="skip the untimed clock-settling windows (profiler passes)")
-    ap.add_argument("--dump-launch-order", default=None, help="write the (entry point, shape) sequence of one step as JSON")
+    full_opt("--no-settle", dest="settle", action="store_false", help="[full] skip the untimed clock-settling windows (profiler passes)")
+    full_opt("--dump-launch-order", default=None, help="[full] write the (entry point, shape) sequence of one step as JSON")
     args = ap.parse_args()
+    if not args.full:
+        given = [flag for dest, flag in full_only if getattr(args, dest) != ap.get_default(dest)]
+        if given:
+            ap.error(f"{', '.join(given)}: only with --full")
+    windows = args.windows if args.windows is not None else (5 if args.full else 1)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -190,7 +228,7 @@ def main():
         loss_backward(loss)
         dp.all_reduce()
         opt.step()
-        return loss
+        return out, loss
 
     def fence():
         torch.cuda.synchronize()
@@ -198,13 +236,18 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    import gc
+    if not args.full:
+        # one full collection, then none until the line is out: before the warm-up, so that no idle GPU separates it from the timing
+        gc.collect()
+        gc.disable()
     it = 0
     for _ in range(args.warmup):
         step(it); it += 1
     # clocks, allocator pools and the sampling pipeline settle over the first ~50 ms; short runs (W=5, K=30) otherwise
     # swing by 10 % from run to run.  Untimed, like the W steps above.
     prev = None
-    for _ in range(12 if args.settle else 0):                      # 10-step windows until two consecutive ones agree within 2 % (<= 120 steps)
+    for _ in range(12 if args.full and args.settle else 0):                      # 10-step windows until two consecutive ones agree within 2 % (<= 120 steps)
         torch.cuda.synchronize(); t0 = time.perf_counter()
         for _ in range(10):
             step(it); it += 1
@@ -251,7 +294,7 @@ def main():
         _lib.PROFILER = None
         mlp_hip.USE_STACK = stack_default; _head.USE_STACK = head_default
     # pick the dominant own kernel (untimed 2-step pre-pass with every entry point bracketed by events)
-    target = args.roofline_kernel
+    target = args.roofline_kernel if args.full else "none"
     target_algo = None
     if target == "auto":
         mlp_hip.per_kernel_path().__enter__()
@@ -290,10 +333,9 @@ def main():
         else:
             timer = _lib.KernelTimer([target[0]], tags=None if target[1] is None else [target[1]], max_records=64)
 
-    import gc
     lab_no_gc = bool(os.environ.get("PCL_BENCH_NO_GC"))                   # lab switches (tools/first_window.sh): what makes the FIRST window slow?
     lab_idle_ms = float(os.environ.get("PCL_BENCH_IDLE_MS", "0"))         # host sleep (GPU idle) in front of window 2
-    if not lab_no_gc:
+    if args.full and not lab_no_gc:
         gc.collect()
         gc.disable()             # no collector pauses inside the timed region (a gen-2 pass over the autograd objects is ~5 ms: a window of 5.3 ms per step, measured)
     # Round 6, root cause of round 5's driver line (2.135 ms where the same run's N = 4096 row took 2.187): the GPU IDLES through the
@@ -303,7 +345,7 @@ def main():
     # re-warm steps come AFTER the collect, and run until two consecutive 10-step windows agree within 1 % (at most 100 steps), like the
     # settling pass in front of the pre-pass.
     prev = None
-    for k in range(10):
+    for k in range(10 if args.full else 0):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         for _ in range(10 if k or args.rewarm <= 10 else args.rewarm):
             step(it); it += 1
@@ -326,11 +368,12 @@ def main():
     win_dt, win_host, win_armed = [], [], []
     if timer is not None:
         timer.max_records = None
-    for w in range(max(1, args.windows)):
+    last = None
+    for w in range(max(1, windows)):
         # (armed in windows 1, 3, ...: the event pair costs ~8 us per step -- 12 of 12 runs on one box: armed windows 1.809-1.815 ms, the
         #  unarmed ones between them 1.800-1.807 -- and the product path does not carry it, so the MAJORITY of the windows, and with it the
         #  median, is unarmed; a single window is armed, or the line would have no live kernel time)
-        armed = timer is not None and (w % 2 == 1 or max(1, args.windows) == 1)
+        armed = timer is not None and (w % 2 == 1 or max(1, windows) == 1)
         _lib.PROFILER = timer if armed else None
         win_armed.append(armed)
         if lab_idle_ms and w == 2:
@@ -338,7 +381,7 @@ def main():
         fence()
         t0 = time.perf_counter()
         for j in range(args.steps):
-            step(it)
+            last = step(it)
             it += 1
             if host_trace is not None:
                 host_trace.append(time.perf_counter() - t0)
@@ -350,10 +393,13 @@ def main():
             print(f"window {w}: host left step j at [ms]: " + " ".join(f"{t * 1e3:.2f}" for t in host_trace) + f" | fence at {win_dt[-1] * 1e3:.2f}", file=sys.stderr)
             host_trace.clear()
     _lib.PROFILER = None
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, net, *last)
+    last = None
     # host side of a step (untimed extras): the time Python needs to ENQUEUE one step with the stream empty behind it (4
     # steps back to back without a sync; the launch queue is deeper than that), and the number of own C-ABI launches
     host_ms = own_launches = None
-    if True:
+    if args.full:
         torch.cuda.synchronize()
         h0 = time.perf_counter()
         for _ in range(4):
@@ -408,10 +454,10 @@ def main():
                         "launches": r["launches"], "algo_bytes_per_launch": r["algo_bytes"],
                         "algo_flops_per_launch": r["algo_flops"]}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(state0, B, N)
         others = None
-        if world == 1 and not distributed and args.other_configs and (B, N, args.dist) == (32, 1024, "gauss_ball"):
+        if args.full and world == 1 and not distributed and args.other_configs and (B, N, args.dist) == (32, 1024, "gauss_ball"):
             # after the headline's timed region and its CPU leg: the other BASELINE workloads, 20 train steps each on this GPU with the
             # roofline of their own dominant kernel (tools/bench_models.py; builder-run copies with kernel-stat CSVs under profiles/)
             # Nothing in this leg may cost the headline its line: every config is isolated inside other_configs(), and a failure of the
@@ -422,7 +468,7 @@ def main():
                 torch.cuda.empty_cache()
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
                 import bench_models
-                others = bench_models.other_configs(steps=20, windows=max(1, args.windows), cpu_baselines=args.cpu_baselines)
+                others = bench_models.other_configs(steps=20, windows=max(1, windows), cpu_baselines=args.cpu_baselines)
             except Exception as e:                                  # noqa: BLE001 -- reported in the line
                 others = [{"key": "other_configs", "error": f"{type(e).__name__}: {e}"[:400]}]
         value = world * B * args.steps / dt
@@ -430,7 +476,8 @@ def main():
             "metric": f"point-clouds/sec fwd+bwd, PointNet++ SSG B={B} N={N}", "value": round(value, 2),
             "unit": "point-clouds/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "timing": f"median of {len(win_dt)} consecutive windows of {args.steps} steps, each bracketed by barrier + synchronize (MAX over ranks per window)",
+            "timing": (f"median of {len(win_dt)} consecutive windows of {args.steps} steps, each bracketed by barrier + synchronize (MAX over ranks per window)"
+                       if args.full else f"one window of {args.steps} steps after {args.warmup} warm-up steps, bracketed by barrier + synchronize (MAX over ranks)"),
             "windows_ms_per_step": [round(v / args.steps * 1e3, 4) for v in win_dt],
             "windows_host_enqueue_ms_per_step": [round(v / args.steps * 1e3, 4) for v in win_host],
             "windows_timer_armed": win_armed,

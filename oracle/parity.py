@@ -80,6 +80,11 @@ FEATURE_WAIVERS = [
       "PointNet's two T-Nets (misc/layers.py:11-87) end in Linear + BatchNorm1d layers whose batch is the B = 16 pooled rows: dividing by "
       "the std of 16 numbers amplifies the rounding of the 1024-wide pooled vector, and the 3x3 / 128x128 transforms they emit multiply "
       "EVERY point, so the error reaches all 4944 channels of the segmentation head")),
+    ("DGCNN part-seg*", "logits*",
+     ("W-F5 DGCNN part-seg logits", 1.3,      # measured 1.05 (fp32 restatement 1.44) on the fp64 evaluation's k-NN graph
+      "three EdgeConv stages (k = 40 over 2048 points) and four BatchNorm'd 1x1 convolutions over B*N = 32 768 rows into 50 classes: "
+      "the HIP logits sit at the edge of the bound whatever the graph (1.05 x on the fp64 evaluation's lists, which the test now "
+      "uses; 0.96 - 1.17 x on fp32 restatements' lists from different PyTorch-CPU thread counts), the fp32 restatement at 1.44 x")),
     ("PointCNN part-seg*", "logits*",
      ("W-F4 X-conv depth", 16.3,              # measured 13.0; PyTorch-CPU fp32 (NCHW restatement) 32.4
       "eight X-conv stages (four encoders, four decoders), each a learned K x K transform applied to BatchNorm'd features followed by "
@@ -119,6 +124,12 @@ GRAD_WAIVERS = [
       "weights.2).  Not the density input (same figures with the oracle's densities fed in, tools/dbg/pc_density_src.py), not "
       "the DensityNet kernels (against fp64 on equal inputs they are closer than PyTorch fp32, tools/dbg/narrow_err.py).  Absolute "
       "error 2.8e-4 = 2.3e-4 of the model's largest gradient entry; capped at 3e-4.  Round 4: summing the contraction's channel chunks in fp64 (t = sum_c feat dout, d_dens = sum_m w t) left this row unchanged to three digits -- the noise is not that sum's.")),
+    ("PointNet part-seg*", "conv5.weights.0",
+     ("W-G2 global max-pool winner", 6.8e-4,      # measured 5.4e-4 (max|err| 9.2e-5 against the model's largest entry 0.171)
+      "the mechanism of GRAD_CAP_MAX: the 1024-wide global max over the 2048 points picks, for one channel, a different point than "
+      "fp64 (two pre-BatchNorm values within an ulp), which moves that channel's weight-gradient row (max-norm 2.3e-2, relL2 3.0e-3).  "
+      "The fp32 restatement makes the same flip on 8 and 4 PyTorch-CPU threads and not on 16, so the 10 x rule passes or fails with "
+      "the host's thread count")),
     # (r2's 800 %-relative-error row, PointConv's sa?.densitynet.mlp.gammas.2, is analytically ZERO -- the last
     # DensityNet layer is BatchNorm(1 channel) + ReLU with beta = 0, so gamma scales every input of the Linear + BatchNorm that
     # follows, which removes it again -- and its absolute error, 1.6e-7 against a model-wide largest gradient entry of O(1), is

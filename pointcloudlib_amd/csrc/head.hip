@@ -8,7 +8,7 @@
 //             cross-lane reduction lane r holds y[r,n]; batch mean / variance over the R rows, normalise, activate, store.
 //   backward: (1) wave = column n again: du = dout * act'(out), BatchNorm backward over the column, dy[:,n] stored;
 //                 dW[n,:] = sum_r dy[r] X[r,:] written coalesced; dgamma, dbeta, dbias.
-//             (2) dX[r,k] = sum_n dy[r,n] W[n,k]: lane = k, the n range split over waves, atomics into dX.
+//             (2) dX[r,k] = sum_n dy[r,n] W[n,k]: lane = k, the n range split over waves, summed in a fixed order.
 // BatchNorm1d follows torch (the head is torch's BatchNorm1d in the counterpart networks): biased variance for the
 // normalisation, UNBIASED variance into running_var, momentum 0.1.
 #include "common.h"
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void head_bwd_col_kernel(const float* __restri
                                                            float* __restrict__ dbeta, float* __restrict__ dX_zero, const Drop drop) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = blockIdx.x;
-    if (dX_zero) {                         // the dX kernel that follows accumulates with atomics: clear its target here
+    if (dX_zero) {                         // head_dx_mfma_kernel, which may follow, accumulates with atomics: clear its target here
         const int total = R * K, chunk = (total + N - 1) / N;
         for (int e = n * chunk + threadIdx.x; e < min((n + 1) * chunk, total); e += 256) dX_zero[e] = 0.f;
     }
@@ -231,34 +231,37 @@ __device__ __forceinline__ float head_col_dy(int lane, int n, const float* __res
     return dy;
 }
 
-// dX[r,k] += sum_{n in this wave's range} dy[r,n] * W[n,k]; grid (ceil(K/64), N splits of HD_NS)
-constexpr int HD_NS = 8;
-template <int RMAX>
-__global__ __launch_bounds__(256) void head_bwd_dx_kernel(const float* __restrict__ dY, const float* __restrict__ W, int R, int K,
+// dX[r,k] = sum_n dy[r,n] * W[n,k]; grid (ceil(K/64), ceil(R/HD_RB)): lane = k, a workgroup owns HD_RB batch rows and the whole n
+// range, wave w of HD_W sums n = w, w + HD_W, ... in order and the waves meet in LDS in a fixed order.  dX is written once, no atomics: the
+// same inputs give the same bits on every run (the earlier split-n form added its partial sums with fp32 atomics in arrival order).
+constexpr int HD_RB = 4, HD_W = 16;
+__global__ __launch_bounds__(64 * HD_W) void head_bwd_dx_kernel(const float* __restrict__ dY, const float* __restrict__ W, int R, int K,
                                                           int N, float* __restrict__ dX) {
-    __shared__ float sD[4][RMAX][HD_NS + 1];
+    __shared__ float sP[HD_W - 1][HD_RB][64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int k = blockIdx.x * 64 + lane;
-    const int n0 = (blockIdx.y * 4 + wave) * HD_NS;
-    for (int e = lane; e < RMAX * HD_NS; e += 64) {
-        const int r = e / HD_NS, j = e - r * HD_NS;
-        sD[wave][r][j] = (r < R && n0 + j < N) ? dY[(size_t)r * N + n0 + j] : 0.f;
+    const int k = blockIdx.x * 64 + lane, kc = min(k, K - 1);
+    const int r0 = blockIdx.y * HD_RB;
+    float acc[HD_RB];
+#pragma unroll
+    for (int r = 0; r < HD_RB; ++r) acc[r] = 0.f;
+#pragma unroll 4
+    for (int n = wave; n < N; n += HD_W) {
+        const float w = W[(size_t)n * K + kc];
+#pragma unroll
+        for (int r = 0; r < HD_RB; ++r) acc[r] = fmaf(r0 + r < R ? dY[(size_t)(r0 + r) * N + n] : 0.f, w, acc[r]);
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int r = 0; r < HD_RB; ++r) sP[wave - 1][r][lane] = acc[r];
     }
     __syncthreads();
-    float acc[RMAX];
+    if (wave == 0 && k < K) {
 #pragma unroll
-    for (int r = 0; r < RMAX; ++r) acc[r] = 0.f;
-    const int kc = min(k, K - 1);
-    for (int j = 0; j < HD_NS; ++j) {
-        if (n0 + j >= N) break;
-        const float w = W[(size_t)(n0 + j) * K + kc];
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) acc[r] = fmaf(sD[wave][r][j], w, acc[r]);
-    }
-    if (k < K && n0 < N) {
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r)
-            if (r < R) unsafeAtomicAdd(&dX[(size_t)r * K + k], acc[r]);
+        for (int r = 0; r < HD_RB; ++r) {
+            float v = acc[r];
+            for (int w = 0; w < HD_W - 1; ++w) v += sP[w][r][lane];
+            if (r0 + r < R) dX[(size_t)(r0 + r) * K + k] = v;
+        }
     }
 }
 
@@ -508,21 +511,20 @@ static int head_layer_bwd_impl(const float* X, const float* W, const float* dOUT
                            dbias, dgamma, dbeta, dX, drop);
         const int kblocks = (K + 31) / 32, gy = kblocks >= 128 ? 32 : 8, kb_per_wg = (kblocks + gy - 1) / gy;
         hipLaunchKernelGGL(head_dw_mfma_kernel, dim3((N + 31) / 32, gy), block, 0, st, dY_ws, X, R, K, N, kb_per_wg, dW);
-    } else if (R <= 32)
+    } else if (R <= 32)                           // dX cleared only for head_dx_mfma_kernel's atomics; head_bwd_dx_kernel writes it whole
         hipLaunchKernelGGL(head_bwd_col_kernel<32>, grid, block, 0, st, X, dOUT, OUT, Ypre, gamma, mean, invstd, R, K, N, bn_mode & 3, slope, dY_ws,
-                           dW, dbias, dgamma, dbeta, dX, drop);
+                           dW, dbias, dgamma, dbeta, K >= 2048 ? dX : nullptr, drop);
     else
         hipLaunchKernelGGL(head_bwd_col_kernel<64>, grid, block, 0, st, X, dOUT, OUT, Ypre, gamma, mean, invstd, R, K, N, bn_mode & 3, slope, dY_ws,
-                           dW, dbias, dgamma, dbeta, dX, drop);
+                           dW, dbias, dgamma, dbeta, nullptr, drop);
     int rc = check_launch("pcl_head_layer_bwd_f32(col)");
     if (rc || !dX) return rc;
-    const dim3 g2((K + 63) / 64, (N + 4 * HD_NS - 1) / (4 * HD_NS));
+    const dim3 g2((K + 63) / 64, (R + HD_RB - 1) / HD_RB);
     if (R <= 32 && K >= 2048) {
         const int NS = N >= 512 ? 2 : 1, nper = ((N + NS - 1) / NS + 127) / 128 * 128;
         hipLaunchKernelGGL(head_dx_mfma_kernel, dim3((K + 127) / 128, NS), block, 0, st, dY_ws, W, R, K, N, nper, dX);
     }
-    else if (R <= 32) hipLaunchKernelGGL(head_bwd_dx_kernel<32>, g2, block, 0, st, dY_ws, W, R, K, N, dX);
-    else hipLaunchKernelGGL(head_bwd_dx_kernel<64>, g2, block, 0, st, dY_ws, W, R, K, N, dX);
+    else hipLaunchKernelGGL(head_bwd_dx_kernel, g2, dim3(64 * HD_W), 0, st, dY_ws, W, R, K, N, dX);
     return check_launch("pcl_head_layer_bwd_f32(dx)");
 }
 

@@ -4,6 +4,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CPU_THREADS = 16          # PyTorch-CPU intra-op threads of the GPU test session (see `dev`)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
@@ -24,6 +25,11 @@ def dev():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
+    # The fp32 CPU restatements the GPU parity tests measure against split their reductions over PyTorch's intra-op threads,
+    # so their rounding -- and with it the yardstick -- moves with the host's thread count (PointNet++ SSG cls B=8, SA3
+    # output vs fp64, relative to its largest entry: 1.1e-5 on 16 threads, 2.1e-5 on 8, 4.6e-5 on 4).  One fixed count makes
+    # them the same on every host with the same CPU; the waivers' measured values in oracle/parity.py are on 16.
+    torch.set_num_threads(CPU_THREADS)
     from pointcloudlib_amd import _lib
     _lib.lib()          # fail loudly if the HIP library is missing
     return torch.device("cuda:0")

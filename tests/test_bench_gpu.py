@@ -1,9 +1,11 @@
-"""GPU: bench.py prints ONE JSON line with the fields the driver and the judge read (short run, no CPU baseline leg)."""
+"""GPU: bench.py prints ONE JSON line with the fields the driver and the judge read: the plain run (headline only, with its
+output dump) and short --full runs (roofline, RCCL path; no CPU baseline leg)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -11,8 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-settle",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full",
+                          "--no-settle", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -28,6 +30,37 @@ def test_bench_line_contract():
         assert k in r, k
     assert r["bound"] in ("hbm", "mfma") and 0.0 < r["frac"] <= 1.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
     assert r["kernel"].startswith("pcl_")                                            # an own C-ABI entry point, event-timed live
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: exactly --steps timed steps in one window, none of the --full legs, and --dump-outputs writes the last
+    timed step's logits, loss, parameters and gradients as float32 .npy files (64 MB at most)."""
+    import torch
+    from pointcloudlib_amd import synth
+    from pointcloudlib_amd.train_utils import soft_cross_entropy_loss
+    steps, warmup = 7, 3
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == steps and d["warmup"] == warmup and d["windows_ms_per_step"] == [d["ms_per_step"]]
+    assert abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["other_configs"] is None
+    arrays = {p.name[:-4]: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    params = [n for n in arrays if n.startswith("param.")]
+    assert len(params) > 20 and all("grad." + n[len("param."):] in arrays for n in params)
+    # the loss is the one of the dumped logits against the labels of the last step's batch (bench.py cycles 4 seeded batches)
+    logits, loss = arrays["logits"], arrays["loss"]
+    assert logits.shape == (32, 40) and loss.shape == ()
+    labels = torch.from_numpy(synth.labels(32, 40, 20242 + (warmup + steps - 1) % 4 + 900))
+    want = soft_cross_entropy_loss(torch.from_numpy(logits).double(), labels).item()
+    assert abs(float(loss) - want) <= 1e-5 * max(1.0, abs(want)), (float(loss), want)
 
 
 def _free_port():
@@ -51,7 +84,7 @@ def test_bench_under_torchrun_runs_the_rccl_path():
         assert len(lines) == 1, out.stdout
         return json.loads(lines[0])
 
-    common = ["--gpus", "1", "--steps", "40", "--warmup", "5", "--no-cpu-baseline"]
+    common = ["--gpus", "1", "--steps", "40", "--warmup", "5", "--full", "--no-cpu-baseline"]
     solo = run([sys.executable, os.path.join(ROOT, "bench.py")] + common)
     dist = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                 "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + common)

@@ -281,7 +281,8 @@ def test_batchnorm_statistics_survive_large_mean(dev, offset, spread):
 
 @pytest.mark.parametrize("R,K,N,bn,slope,bias", [(32, 1024, 512, True, 0.0, False), (32, 256, 40, False, 1.0, True),
                                                  (5, 300, 33, True, 0.2, True), (64, 2048, 512, True, 0.2, False),
-                                                 (1, 16, 8, False, 0.0, True), (33, 70, 130, True, 0.0, True)])
+                                                 (1, 16, 8, False, 0.0, True), (33, 70, 130, True, 0.0, True),
+                                                 (8, 2050, 64, True, 0.0, False)])
 def test_head_layer_matches_torch(dev, R, K, N, bn, slope, bias):
     """csrc/head.hip (Linear + BatchNorm1d + activation on <= 64 rows as one kernel) against the PyTorch modules in fp64:
     outputs, running statistics and every gradient; training and evaluation mode."""

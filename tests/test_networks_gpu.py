@@ -1,5 +1,5 @@
 """GPU: whole networks built from the HIP ops -- shapes, backend agreement (fused HIP MLP vs plain-PyTorch MLP on
-the same HIP indices) and, for PointNet++ SSG, feature parity with the CPU restatement level by level."""
+the same HIP indices) and, for PointNet++ SSG, feature parity with the fp64 evaluation of the CPU restatement level by level."""
 import copy
 
 import numpy as np
@@ -35,6 +35,8 @@ def fwd_bwd(model, args, backend):
 
 
 def test_pointnet2_cls_matches_cpu_restatement(oracle, dev):
+    """PointNet++ SSG cls level by level against the fp64 evaluation of the CPU restatement: sampled xyz bit-exact, pooled
+    features within 1e-5 of the level's largest entry, logits within 1e-4."""
     from oracle.cpu_model import PointNet2ClsCPU
     from pointcloudlib_amd.misc import ops
     from pointcloudlib_amd.networks.cls.pointnet2 import PointNet2_cls
@@ -42,7 +44,9 @@ def test_pointnet2_cls_matches_cpu_restatement(oracle, dev):
     B, N = 8, 1024
     pts, nrm = synth.gauss_ball(B, N, 11), synth.unit_normals(B, N, 12)
     net = no_dropout(PointNet2_cls().to(dev)).train()
-    ref = PointNet2ClsCPU(net.state_dict(), tie_stride=ops.optimal_block(B)).train()
+    # against the fp64 evaluation of the restatement (index ops stay fp32): the fp32 one is itself 0.5-1.1 x 1e-5 from fp64
+    # at these levels on 16 PyTorch-CPU threads (more on fewer), while the HIP path is within 0.07-0.18 x 1e-5 of it
+    ref = PointNet2ClsCPU(net.state_dict(), tie_stride=ops.optimal_block(B), dtype=torch.float64).train()
     x, f = torch.from_numpy(pts).to(dev), torch.from_numpy(nrm).to(dev)
     # level by level: sampled xyz bit-exact, pooled features within 1e-5 (relative to the level's max)
     with torch.no_grad():
@@ -52,14 +56,14 @@ def test_pointnet2_cls_matches_cpu_restatement(oracle, dev):
             new_xyz, cur_f = mod(cur_xyz, cur_f)
             want = aux[lvl]["feat"]
             scale = max(1.0, want.abs().max().item())
-            err = (cur_f.cpu() - want).abs().max().item()
+            err = (cur_f.cpu().double() - want).abs().max().item()
             assert err <= 1e-5 * scale, f"SA{lvl + 1}: {err:.3e} vs scale {scale:.3f}"
             if new_xyz is not None:
                 assert np.array_equal(new_xyz.cpu().numpy()[:, :, 0], pts[np.arange(B)[:, None], aux[lvl]["fps_idx"]][:, :, 0]) \
                     if lvl == 0 else True
                 cur_xyz = new_xyz
         logits = net.fc_layer(cur_f.squeeze(1))
-        assert (logits.cpu() - logits_ref).abs().max().item() <= 1e-4 * max(1.0, logits_ref.abs().max().item())
+        assert (logits.cpu().double() - logits_ref).abs().max().item() <= 1e-4 * max(1.0, logits_ref.abs().max().item())
 
 
 def test_pointnet2_cls_backends_agree_with_grads(dev):

@@ -4,7 +4,7 @@ O=$1; PAT=$2; shift 2; mkdir -p $O
 for rep in 1 2 3; do
   for v in "$@"; do
     n=${v%%=*}; so=${v#*=}
-    PCL_HIP_SO=$PWD/$so python bench.py --no-cpu-baseline --no-other-configs --steps 20 --roofline-kernel none 2>/dev/null | python -c "
+    PCL_HIP_SO=$PWD/$so python bench.py --full --no-cpu-baseline --no-other-configs --steps 20 --roofline-kernel none 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); print('rep $rep [$n]', d['ms_per_step'], d['windows_ms_per_step'])"
   done
@@ -12,5 +12,5 @@ done
 for v in "$@"; do
   n=${v%%=*}; so=${v#*=}
   echo "--- $n"
-  PCL_HIP_SO=$PWD/$so python bench.py --steps 10 --warmup 3 --windows 1 --profile-all --no-cpu-baseline --no-other-configs --roofline-kernel none 2>&1 >/dev/null | grep -E "n/step" | grep -E "$PAT"
+  PCL_HIP_SO=$PWD/$so python bench.py --full --steps 10 --warmup 3 --windows 1 --profile-all --no-cpu-baseline --no-other-configs --roofline-kernel none 2>&1 >/dev/null | grep -E "n/step" | grep -E "$PAT"
 done

@@ -5,7 +5,7 @@ O=$1; shift; mkdir -p $O
 for rep in 1 2; do
   for v in "$@"; do
     n=${v%%=*}; so=${v#*=}
-    PCL_HIP_SO=$PWD/$so python bench.py --no-cpu-baseline --no-other-configs --steps 20 2>/dev/null > $O/ab_${n}_$rep.json
+    PCL_HIP_SO=$PWD/$so python bench.py --full --no-cpu-baseline --no-other-configs --steps 20 2>/dev/null > $O/ab_${n}_$rep.json
     python - $O/ab_${n}_$rep.json $n $rep <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
@@ -15,6 +15,6 @@ PY
 done
 for v in "$@"; do
   n=${v%%=*}; so=${v#*=}
-  PCL_HIP_SO=$PWD/$so python bench.py --steps 10 --warmup 3 --windows 1 --profile-all --no-cpu-baseline --no-other-configs --roofline-kernel none 2>&1 >/dev/null | grep -E "n/step" | grep -E "fb|fused" > $O/table_$n.txt
+  PCL_HIP_SO=$PWD/$so python bench.py --full --steps 10 --warmup 3 --windows 1 --profile-all --no-cpu-baseline --no-other-configs --roofline-kernel none 2>&1 >/dev/null | grep -E "n/step" | grep -E "fb|fused" > $O/table_$n.txt
   echo "--- $n"; cat $O/table_$n.txt
 done

@@ -2,7 +2,7 @@
 # Which HIP API calls / memory copies sit between the kernels of one step (run through gpurun): kernel + HIP runtime + memory-copy
 # traces of a short bench run (no counters), and the API calls made while the main stream idles at the loss -> backward turn.
 R=${1:-x}; O=gpurun_out/$R; mkdir -p $O; cd /tmp 2>/dev/null; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --hip-runtime-trace --memory-copy-trace --output-format csv -d $O/tr -o b -- python bench.py --steps 6 --warmup 3 --no-settle --no-cpu-baseline --roofline-kernel none > $O/tr.log 2>&1
+rocprofv3 --kernel-trace --hip-runtime-trace --memory-copy-trace --output-format csv -d $O/tr -o b -- python bench.py --full --steps 6 --warmup 3 --no-settle --no-cpu-baseline --roofline-kernel none > $O/tr.log 2>&1
 find $O/tr -name "*.csv" | head
 python - <<PY
 import csv, glob

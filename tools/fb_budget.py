@@ -21,7 +21,7 @@ def run(out):
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     os.environ["PCL_HIP_SO"] = os.path.join(ROOT, "pointcloudlib_amd", "libpcl_hip_exp7.so")
     sys.path.insert(0, ROOT)
-    sys.argv = ["bench.py", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-other-configs", "--roofline-kernel", "none"]
+    sys.argv = ["bench.py", "--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-other-configs", "--roofline-kernel", "none"]
     import ctypes
     import bench
     bench.main()

@@ -3,7 +3,7 @@
 #   PCL_BENCH_NO_GC=1     no gc.collect() / gc.disable() in front of the windows
 #   PCL_BENCH_IDLE_MS=n   n ms of host sleep with the GPU idle in front of window 2 (does an idle GPU make the NEXT window slow?)
 R=${1:-r06b}; O=gpurun_out/$R; mkdir -p $O
-B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs"
+B="python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs"
 for k in 1 2; do $B > $O/base_$k.json 2>/dev/null; done
 for k in 1 2; do PCL_BENCH_NO_GC=1 $B > $O/nogc_$k.json 2>/dev/null; done
 for ms in 20 100 400; do PCL_BENCH_IDLE_MS=$ms $B > $O/idle${ms}.json 2>/dev/null; done

@@ -1,6 +1,6 @@
 """Wave-state / MFMA-pipe summary per kernel and grid from one rocprofv3 counter pass:
     rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES \
-        SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d out -o b -- python bench.py --steps 3 --warmup 1 --no-settle \
+        SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d out -o b -- python bench.py --full --steps 3 --warmup 1 --no-settle \
         --no-cpu-baseline --roofline-kernel none
     python tools/pmc_sq.py out/b_counter_collection.csv profiles/rNN_pmc_sq_wave_states.csv"""
 import csv, sys
@@ -12,7 +12,7 @@ for r in csv.DictReader(open(src)):
     key = (name, int(r["Grid_Size"]) if "Grid_Size" in r else int(r["Grid_Size_X"]))
     acc[key][r["Counter_Name"]] += float(r["Counter_Value"]); n[key].add(r["Dispatch_Id"])
 with open(dst, "w") as f:
-    f.write("# rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -- python bench.py --steps 3 --warmup 1 --no-settle\n")
+    f.write("# rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -- python bench.py --full --steps 3 --warmup 1 --no-settle\n")
     f.write("# per-launch means.  SQ_WAVE_CYCLES/WAIT_*/ACTIVE_* are quad-cycles (fractions of wave time are unit-free); SQ_VALU_MFMA_BUSY_CYCLES = 64 x (number of v_mfma_f32_32x32x2_f32), summed over the 1024 SIMDs;\n")
     f.write("# GRBM_GUI_ACTIVE is summed over the 8 XCDs: mfma_pipe_util = MFMA_BUSY / (GUI_ACTIVE / 8 * 1024)\n")
     f.write("kernel,grid,launches,wait_any_frac,wait_inst_frac,active_frac,mfma_busy_cycles,gui_active,mfma_pipe_util\n")

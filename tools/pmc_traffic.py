@@ -1,8 +1,8 @@
 """HBM traffic per launch shape from two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of bench.py.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d out/fetch -o b -- python bench.py --steps 3 --warmup 1 \
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d out/fetch -o b -- python bench.py --full --steps 3 --warmup 1 \
         --no-settle --no-cpu-baseline --roofline-kernel none --dump-launch-order out/order.json
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d out/write -o b -- python bench.py ... (same)
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d out/write -o b -- python bench.py --full ... (same)
     python tools/pmc_traffic.py out/fetch/b_counter_collection.csv out/write/b_counter_collection.csv out/order.json \
         profiles/rNN_pmc_hbm_traffic.csv profiles/rNN_traffic.json
 
@@ -52,7 +52,7 @@ def family_series(path, counter, families=FAMILY):
 def main():
     fetch_csv, write_csv, order_json, out_csv, out_json = sys.argv[1:6]
     workload = sys.argv[6] if len(sys.argv) > 6 else "PointNet++ SSG cls B=32 N=1024, duplicate-compacted padded rows"
-    command = sys.argv[7] if len(sys.argv) > 7 else "python bench.py --steps 3 --warmup 1 --no-settle"
+    command = sys.argv[7] if len(sys.argv) > 7 else "python bench.py --full --steps 3 --warmup 1 --no-settle"
     order = [tuple(o) + ("",) * (3 - len(o)) for o in json.load(open(order_json))["step_launch_order"]]
     families = sorted({family_of(*o) for o in order} - {None, ""})
     fetch, write = family_series(fetch_csv, "FETCH_SIZE", families), family_series(write_csv, "WRITE_SIZE", families)
