@@ -695,7 +695,8 @@ int pcl_group_compact_f32(const float* xyz, const float* new_xyz, const float* f
                           const int32_t* cnt, const int32_t* group_off, int B, int N, int m, int ns, int C, int use_xyz,
                           int row_stride /* >= 3*use_xyz + C; extra columns are written as zeros */, float* rows,
                           int32_t* row_meta, int32_t* row_src, void* stream);
-/* reference: as pcl_linear_fwd_f32 (networks/cls/pointnet2.py:25-29) on duplicate-compacted rows */
+/* reference: as pcl_linear_fwd_f32 (networks/cls/pointnet2.py:25-29) on duplicate-compacted rows.  stats_ws NULL (plain rows only,
+ * row_meta NULL): the stats-free form for inference -- the same products and stores without the BatchNorm partial sums. */
 int pcl_linear_fwd_rows_f32(const float* X, const float* W, const float* bias, const float* in_scale,
                             const float* in_shift, float in_slope, int P, int Cin, int Cout, float* Y,
                             double* stats_ws, const int32_t* row_meta, const int32_t* n_rows_dev, void* stream);
@@ -737,6 +738,27 @@ int pcl_xconv_core_fwd_f32(const float* X, const float* F1, int C1, const float*
 int pcl_xconv_core_bwd_f32(const float* X, const float* F1, int C1, const float* F2, int C2, const float* wd, const float* dD,
                            int R, int K, int dm, float* dX, float* dF1, float* dF2, float* dwd_part, float* dbias_part,
                            void* stream);
+
+/* ---- Frozen inference: one ball-query set-abstraction level in evaluation mode as ONE launch ---------------------------
+ * networks/cls/pointnet2.py:33-62 (PointNetModuleBase.execute: grouping, conv/bn/relu x L, max over the group) as evaluated by
+ * train_cls.py:92-124 (net.eval(): running statistics), with the grouping of misc/ops.py:383-407 folded into the first layer as in
+ * pcl_group_linear_f32:
+ *     y1 = Wx (xyz[nbr] - centre) + Uf[nbr] (+ Wf_small feat_small[nbr]),  z_l = act(scale_l * y_l + shift_l),
+ *     y_l = W_l z_{l-1} (l >= 2),  out[g * ldo + col0 + c] = max over the group's DISTINCT rows of z_L[c]
+ * The rows are the max(cnt, 1) distinct ones pcl_group_linear_f32 emits (ball-query padding repeats the first hit).  Eval
+ * BatchNorm: scale = gamma / sqrt(running_var + eps), shift = beta - scale * running_mean; without BatchNorm scale = 1, shift =
+ * bias.  act = leaky ReLU with `slope` (0: ReLU).  Inputs as pcl_group_linear_f32: xyz [B*N,3], new_xyz [B*m,3], idx [B,m,ns],
+ * cnt [B,m]; Wx [C1,3] (row stride ldw) or NULL; Uf [B*N, C1] or NULL; feat_small [B*N, CF] with Wf_small [C1, CF] (stride ldw),
+ * CF <= 4.  Host arrays of L entries: widths C_l, W (device pointers, W[l] [C_l, C_{l-1}] dense; W[0] ignored), scale, shift.
+ * Uf and the W_l 16-byte aligned.  Activations stay in LDS / registers; fp32 MFMA; no atomics (run-to-run identical).
+ * Kernels exist for the SA levels of the classification networks (L = 3; widths 32/32/64, 64/64/128, 64/96/128, 128/128/256;
+ * ns <= 1024): pcl_sa_level_infer_supported (unused widths 0); any other shape returns PCL_EINVAL. */
+int pcl_sa_level_infer_supported(int ns, int L, int C1, int C2, int C3, int C4);
+/* reference: networks/cls/pointnet2.py:33-62 + misc/ops.py:383-407 in eval mode (train_cls.py:92-124) */
+int pcl_sa_level_infer_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, const float* feat_small,
+                           const float* Wf_small, int CF, int ldw, const int32_t* idx, const int32_t* cnt, int B, int N, int m, int ns,
+                           int L, const int32_t* widths, const float* const* W, const float* const* scale, const float* const* shift,
+                           float slope, float* out, int ldo, int col0, void* stream);
 
 #ifdef __cplusplus
 }

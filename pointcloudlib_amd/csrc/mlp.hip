@@ -3129,6 +3129,8 @@ static int launch_linear(const LinArgs& a, hipStream_t st) {
     }
     if (a.a_mode == A_PLAIN && a.e_mode == E_STORE_STATS) return launch_linear_t<A_PLAIN, E_STORE_STATS>(a, st);
     if (a.a_mode == A_BNACT && a.e_mode == E_STORE_STATS) return launch_linear_t<A_BNACT, E_STORE_STATS>(a, st);
+    if (a.a_mode == A_PLAIN && a.e_mode == E_STORE) return launch_linear_t<A_PLAIN, E_STORE>(a, st);      // stats-free forward (inference)
+    if (a.a_mode == A_BNACT && a.e_mode == E_STORE) return launch_linear_t<A_BNACT, E_STORE>(a, st);
     if (a.a_mode == A_DY && a.e_mode == E_MASK_STORE_STATS) return launch_linear_t<A_DY, E_MASK_STORE_STATS>(a, st);
     if (a.a_mode == A_DY && a.e_mode == E_STORE) return launch_linear_t<A_DY, E_STORE>(a, st);
     if (a.a_mode == A_DY_SPARSE && a.e_mode == E_MASK_STORE_STATS) return launch_linear_t<A_DY_SPARSE, E_MASK_STORE_STATS>(a, st);
@@ -3147,7 +3149,8 @@ extern "C" int pcl_mlp_stat_rows(int P, int C, int flags) {
 extern "C" int pcl_linear_fwd_rows_f32(const float* X, const float* W, const float* bias, const float* in_scale,
                                        const float* in_shift, float in_slope, int P, int Cin, int Cout, float* Y,
                                        double* stats_ws, const int32_t* row_meta, const int32_t* n_rows_dev, void* stream) {
-    PCL_REQUIRE(X && W && Y && stats_ws, "pcl_linear_fwd_f32: null pointer");
+    PCL_REQUIRE(X && W && Y, "pcl_linear_fwd_f32: null pointer");
+    PCL_REQUIRE(stats_ws || !row_meta, "pcl_linear_fwd_rows_f32: the stats-free form (stats_ws NULL) takes plain rows only");
     PCL_REQUIRE(P >= 1 && Cin >= 1 && Cout >= 1, "pcl_linear_fwd_f32: bad sizes P=%d Cin=%d Cout=%d", P, Cin, Cout);
     PCL_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "pcl_linear_fwd_f32: in_scale/in_shift must come together");
     PCL_REQUIRE((row_meta == nullptr) == (n_rows_dev == nullptr), "pcl_linear_fwd_rows_f32: row_meta and n_rows_dev come together");
@@ -3155,7 +3158,7 @@ extern "C" int pcl_linear_fwd_rows_f32(const float* X, const float* W, const flo
     a.A = X; a.B = W; a.bias = bias; a.sc = in_scale; a.sh = in_shift; a.slope = in_slope;
     a.C = Y; a.stats = stats_ws; a.M = P; a.N = Cout; a.K = Cin; a.ldc = Cout;
     a.rmeta = reinterpret_cast<const int2*>(row_meta); a.m_dev = n_rows_dev;
-    a.a_mode = in_scale ? A_BNACT : A_PLAIN; a.e_mode = E_STORE_STATS;
+    a.a_mode = in_scale ? A_BNACT : A_PLAIN; a.e_mode = stats_ws ? E_STORE_STATS : E_STORE;
     return launch_linear(a, as_stream(stream));
 }
 

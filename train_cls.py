@@ -61,8 +61,10 @@ def lookahead(loader, dev):
         cur = nxt
 
 
-def run_epoch(net, name, loader, dev, optimizer=None, side=None):
+def run_epoch(net, name, loader, dev, optimizer=None, side=None, fnet=None):
+    """One pass over ``loader``; ``fnet``: a frozen evaluator of ``net`` (pointcloudlib_amd.inference) that runs the validation forwards."""
     train = optimizer is not None
+    model = net if train or fnet is None else fnet
     net.train(train)
     seen = correct = 0
     loss_sum = 0.0
@@ -76,9 +78,9 @@ def run_epoch(net, name, loader, dev, optimizer=None, side=None):
                 # FPS / ball query of the NEXT batch on the library's side stream, beside this step (enqueued ahead of the forward:
                 # bench.py measured 1.900 vs 1.914 ms for enqueueing it behind the forward)
                 pending = net.precompute_sampling(nxt[0], stream=side) if nxt is not None else None
-                out = net(pts, normals, sampling=cur_samp)
+                out = model(pts, normals, sampling=cur_samp)
             else:
-                out = forward(net, name, pts, normals)
+                out = forward(model, name, pts, normals)
             if train:
                 loss = soft_cross_entropy_loss(out, labels)
                 optimizer.zero_grad(set_to_none=True)
@@ -103,7 +105,10 @@ def main():
     ap.add_argument("--lr_decay", action="store_true")
     ap.add_argument("--synthetic_items", type=int, default=512)
     ap.add_argument("--seed", type=int, default=0, help="numpy (shuffles, augmentation: freeze_random_seed, train_cls.py:27-28) and torch (init)")
+    ap.add_argument("--fast_eval", action="store_true", help="--model pointnet2: validation through pointcloudlib_amd.inference.frozen(net)")
     a = ap.parse_args()
+    if a.fast_eval and a.model != "pointnet2":
+        raise SystemExit("--fast_eval: --model pointnet2 only")
     if not torch.cuda.is_available():
         raise SystemExit("train_cls.py needs a GPU (the HIP path has no CPU fallback)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -123,13 +128,17 @@ def main():
     net = build_model(a.model).to(dev)
     opt = make_sgd(net.parameters(), lr=a.lr, momentum=a.momentum)
     side = "own" if a.model == "pointnet2" else None     # sampling of batch t+1 beside batch t, on the network's private stream
+    fnet = None
+    if a.fast_eval:
+        from pointcloudlib_amd.inference import frozen
+        fnet = frozen(net)
     best = 0.0
     for epoch in range(a.epochs):
         if a.lr_decay and epoch and epoch % 20 == 0:
             for g in opt.param_groups:
                 g["lr"] *= 0.7
         acc, loss, rate = run_epoch(net, a.model, train_set, dev, opt, side)
-        vacc, _, vrate = run_epoch(net, a.model, val_set, dev, None, side)
+        vacc, _, vrate = run_epoch(net, a.model, val_set, dev, None, side, None if fnet is None else fnet.refresh())
         best = max(best, vacc)
         print(f"epoch {epoch}: train loss {loss:.3f} acc {100 * acc:.2f} ({rate:.0f} clouds/s)   val acc {100 * vacc:.2f} "
               f"(best {100 * best:.2f}, {vrate:.0f} clouds/s)", flush=True)
