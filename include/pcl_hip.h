@@ -760,6 +760,28 @@ int pcl_sa_level_infer_f32(const float* xyz, const float* new_xyz, const float* 
                            int L, const int32_t* widths, const float* const* W, const float* const* scale, const float* const* shift,
                            float slope, float* out, int ldo, int col0, void* stream);
 
+/* ---- Frozen inference: one PointNet++ feature-propagation level in evaluation mode as ONE launch ------------------------
+ * misc/ops.py:54-107 (PointNetFeaturePropagation.execute: 3-NN inverse-distance interpolation, concat with the skip features,
+ * conv/bn/relu x L) as evaluated by net.eval(), optionally followed by the part-seg head of networks/seg/pointnet2_partseg.py:151-176
+ * (Conv1d + BN without activation, Dropout = identity, Conv1d with bias).  The first layer is linear and folded:
+ *     y1[r] = Us[r] + Ws_small skip_small[r] + cloud_bias[b] + sum_k w3[r,k] Uc[b*S + idx3[r,k]],   r = b*N + n,
+ *     z_l = act_l(scale_l * y_l + shift_l),  y_l = W_l z_{l-1} (l >= 2),  out[r * ldo + c] = z_L[c] (c < widths[L-1])
+ * Us [B*N, C1] = skip W0s^T (or NULL); skip_small [B*N, CS] with Ws_small [C1, CS] (row stride ldw), CS <= 8 (or CS = 0);
+ * Uc [B*S, C1] = coarse W0c^T with idx3 / w3 [B*N, 3] from pcl_three_nn_f32 (or NULL); cloud_bias [B, C1] (or NULL: e.g. a
+ * one-row coarse level, or the one-hot class label times its weight columns).  act_l = leaky ReLU with `slope` where bit l of
+ * act_mask is set, else the identity.  Host arrays of L entries: widths C_l, W (device pointers, W[l] [C_l', C_{l-1}] dense with
+ * C_l' = C_l rounded up to 32 -- padding rows zero; W[0] ignored), scale, shift (C_l' entries).  tap (or NULL): layer tap_layer
+ * (1 .. L-2) is also stored, tap[r * ldt + c].  Us, Uc, cloud_bias and the W_l 16-byte aligned.  Activations stay in LDS /
+ * registers; fp32 MFMA; no atomics (run-to-run identical).  Kernels exist for the FP levels of the part-seg networks (widths
+ * 256/256, 256/128, 128/128/128) and the last one with the head fused (128/128/128/128/part_num, part_num <= 64):
+ * pcl_fp_level_infer_supported (unused widths 0); any other shape returns PCL_EINVAL. */
+int pcl_fp_level_infer_supported(int L, int C1, int C2, int C3, int C4, int C5);
+/* reference: misc/ops.py:54-107 + networks/seg/pointnet2_partseg.py:151-176 in eval mode */
+int pcl_fp_level_infer_f32(const float* Us, const float* skip_small, const float* Ws_small, int CS, int ldw, const float* Uc,
+                           const int32_t* idx3, const float* w3, int S, const float* cloud_bias, int B, int N, int L,
+                           const int32_t* widths, const float* const* W, const float* const* scale, const float* const* shift,
+                           int act_mask, float slope, float* out, int ldo, float* tap, int tap_layer, int ldt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,9 @@ _SIGS = {
     "pcl_sa_level_infer_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "pcl_sa_level_infer_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P,
                                        c_float, _P, c_int, c_int, _P]),
+    "pcl_fp_level_infer_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "pcl_fp_level_infer_f32": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P,
+                                       c_int, c_float, _P, c_int, _P, c_int, c_int, _P]),
     "pcl_group_linear_stat_rows": (c_int, [c_int, c_int]),
     "pcl_group_linear_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "pcl_group_linear_bwd_f32": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int, _P]),

@@ -16,16 +16,20 @@
 // The k order inside a block of 8 is permuted (lane half h holds k = 8q + 4h + i at k-step 4q + i) identically for A and
 // B, so each lane moves 16-byte pieces; the sum is the same set of products in a different order.
 #include "common.h"
+#include "infer_mfma.h"
 
 namespace pcl {
 namespace {
+
+using infer::act;
+using infer::f32x16;
+using infer::imax;
+using infer::mfma_layer;
 
 constexpr int IF_T = 256;        // threads per workgroup (4 waves)
 constexpr int IF_RT = 64;        // rows per tile (two 32-row MFMA blocks)
 constexpr int IF_MAXGT = 16;     // groups per workgroup at most
 constexpr size_t IF_LDS_CAP = 80 * 1024;     // two workgroups per CU
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct InferArgs {
     const float* xyz; const float* new_xyz; const float* Uf; const float* Wx; const float* fs; const float* Wfs;
@@ -38,8 +42,6 @@ struct InferArgs {
     float* out; int ldo, col0;
 };
 
-__host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
-
 template <int C1, int C2, int C3>
 struct InferShape {
     static constexpr int LD1 = C1 + 4, LD2 = C2 + 4;                       // +4 floats: ds_read_b128 rows on distinct banks
@@ -47,57 +49,6 @@ struct InferShape {
         return 4 * ((size_t)IF_RT * LD1 + IF_RT * LD2 + (size_t)GT * C3) + 32 * IF_RT + 8 * IF_RT + 4 * (IF_MAXGT + 4);
     }
 };
-
-__device__ __forceinline__ float act(float u, float slope) { return u > 0.f ? u : u * slope; }
-
-// acc[rb][j] += X[rb*32 + row][k] * W[(w + 4j)*32 + col][k] over k < K (X in LDS with row stride LDX, W [*, K] in global memory)
-template <int K, int LDX, int NJ, int NCB>
-__device__ __forceinline__ void mfma_layer(const float* __restrict__ X, const float* __restrict__ W, int wave, int lane,
-                                           f32x16 (&acc)[2][NJ]) {
-    const int lr = lane & 31, lh = lane >> 5;
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rb][j][r] = 0.f;
-    const float* xa0 = X + (size_t)lr * LDX + 4 * lh;
-    const float* xa1 = X + (size_t)(32 + lr) * LDX + 4 * lh;
-    const float* wb[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int cb = imax(0, wave + 4 * j < NCB ? wave + 4 * j : 0);
-        wb[j] = W + (size_t)(cb * 32 + lr) * K + 4 * lh;
-    }
-    float4 bn[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) bn[j] = *reinterpret_cast<const float4*>(wb[j]);
-#pragma unroll 2
-    for (int q = 0; q < K / 8; ++q) {
-        float4 b[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) b[j] = bn[j];
-        if (q + 1 < K / 8) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) bn[j] = *reinterpret_cast<const float4*>(wb[j] + 8 * (q + 1));
-        }
-        const float4 a0 = *reinterpret_cast<const float4*>(xa0 + 8 * q);
-        const float4 a1 = *reinterpret_cast<const float4*>(xa1 + 8 * q);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            if (wave + 4 * j < NCB) {
-                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b[j].x, acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b[j].x, acc[1][j], 0, 0, 0);
-                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b[j].y, acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b[j].y, acc[1][j], 0, 0, 0);
-                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b[j].z, acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b[j].z, acc[1][j], 0, 0, 0);
-                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b[j].w, acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b[j].w, acc[1][j], 0, 0, 0);
-            }
-        }
-    }
-}
 
 template <int C1, int C2, int C3>
 __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs a) {

@@ -8,7 +8,13 @@ layer (stats-free library GEMM; narrow features such as SA1's normals fold inlin
 launch that runs the whole MLP + max of every group with its activations in LDS and writes its column slice of the level's output.
 The GroupAll level runs the library's forward GEMMs stats-free with the snapshot constants, then its max; the head runs the
 eval-mode head kernels on at most 64 rows per call.  A level whose shape has no fused kernel runs an eval-mode copy of its own
-module.  ``net`` itself is never modified (parameters, running statistics, ``training`` flags)."""
+module.  ``net`` itself is never modified (parameters, running statistics, ``training`` flags).
+
+The part-seg networks (``PointNet2_partseg`` / its ``PointNetMSG``) share that encoder plan; each feature-propagation level runs
+the stats-free GEMMs of its folded first layer (``Uc = coarse W0c^T`` at the coarse resolution, ``Us = skip W0s^T`` per point, or
+the skip inline when it is narrow; the one-hot class label as a per-cloud bias) and then ONE ``pcl_fp_level_infer_f32`` launch.
+The last level carries the head (Conv1d + BN, Dropout = identity, Conv1d) in the same launch, which also stores the level's own
+output (the tap).  FP levels and heads of other widths run eval-mode copies of their own modules."""
 import copy
 import ctypes
 
@@ -16,17 +22,23 @@ import torch
 
 from . import _lib
 from .misc.head import MAX_ROWS, fc_head
-from .misc.ops import _p, _stream, group_all, group_points
+from .misc.ops import _p, _stream, group_all, group_points, three_nn
 from .networks.cls.pointnet2 import PointNet2_cls
+from .networks.seg.pointnet2_partseg import PointNet2_partseg
 
-__all__ = ["frozen", "FrozenPointNet2"]
+__all__ = ["frozen", "FrozenPointNet2", "FrozenPointNet2Partseg"]
 
 
 def frozen(net):
-    """A frozen evaluator of ``net`` (``PointNet2_cls`` or ``PointNetMSG``): ``fnet(xyz, feature, sampling=None) -> [B, n_classes]``."""
-    if not isinstance(net, PointNet2_cls):
-        raise TypeError(f"frozen() takes PointNet2_cls or PointNetMSG (PointNet++ classification), got {type(net).__name__}")
-    return FrozenPointNet2(net)
+    """A frozen evaluator of ``net``: ``PointNet2_cls`` or ``PointNetMSG`` (classification) -> ``fnet(xyz, feature, sampling=None)
+    -> [B, n_classes]``; ``PointNet2_partseg`` or its ``PointNetMSG`` (part segmentation) -> ``fnet(xyz, feature, cls_label,
+    sampling=None) -> [B, part_num, N]``."""
+    if isinstance(net, PointNet2_cls):
+        return FrozenPointNet2(net)
+    if isinstance(net, PointNet2_partseg):
+        return FrozenPointNet2Partseg(net)
+    raise TypeError(f"frozen() takes PointNet2_cls or PointNetMSG (PointNet++ classification) or PointNet2_partseg / its PointNetMSG "
+                    f"(PointNet++ part segmentation), got {type(net).__name__}")
 
 
 def _eval_consts(mlp, l):
@@ -118,12 +130,13 @@ def _fusable(mlp, use_xyz, C, ns):
     return mlp.n_layers <= 4 and bool(_lib.size_query("pcl_sa_level_infer_supported", int(ns), mlp.n_layers, *widths[:4]))
 
 
-class FrozenPointNet2:
-    """See the module docstring.  ``refresh()`` re-reads weights and running statistics from the network."""
+class _FrozenEncoder:
+    """The set-abstraction levels of a PointNet++ network (``net.pointnet_modules``, input feature 3 wide): a plan per level and
+    scale, and the eval-mode copies of modules without a fused kernel.  Shared by the classification and part-seg evaluators."""
 
     def __init__(self, net):
         self.net = net
-        self._copies = {}          # eval-mode copies of the head and of levels without a fused kernel, kept across refresh()
+        self._copies = {}          # eval-mode copies of the heads and of levels without a fused kernel, kept across refresh()
         self.refresh()
 
     def _copy(self, key, module):
@@ -134,10 +147,9 @@ class FrozenPointNet2:
             c.load_state_dict(module.state_dict())        # same objects: the head kernels' plan cache keys on them
         return c
 
-    @torch.no_grad()
-    def refresh(self):
+    def _refresh_encoder(self):
         net = self.net
-        C = 3                      # the classifiers' input feature: the normals (PointNet2_cls.forward(xyz, feature))
+        C = 3                      # the input feature: the normals (forward(xyz, feature, ...))
         self.levels = []
         for i, module in enumerate(net.pointnet_modules):
             plans = []
@@ -151,25 +163,17 @@ class FrozenPointNet2:
                     plans.append(("module", self._copy((i, j), mlp)))
             self.levels.append(plans)
             C = sum(mlp.spec[-1] for mlp in module.mlps)
-        self.head = self._copy("head", net.fc_layer)
-        return self
 
-    def __call__(self, xyz, feature, sampling=None):
-        return self.run(xyz, feature, sampling)[1]
-
-    @torch.no_grad()
-    def run(self, xyz, feature, sampling=None):
-        """-> ([feature of every set-abstraction level], logits [B, n_classes])."""
+    def _encode(self, xyz, feature, sampling):
+        """-> [(xyz, feature) after every set-abstraction level] (xyz None after the GroupAll level)."""
         net = self.net
         net.adopt_sampling(sampling)
-        feats = []
+        out = []
         for i, (module, plans) in enumerate(zip(net.pointnet_modules, self.levels)):
             s = sampling["levels"][i] if sampling is not None else module.sample(xyz)
             xyz, feature = self._level(module, plans, xyz, feature, s)
-            feats.append(feature)
-        feature = feature.squeeze(dim=1)
-        logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, feature.shape[0], MAX_ROWS)]
-        return feats, logits[0] if len(logits) == 1 else torch.cat(logits)
+            out.append((xyz, feature))
+        return out
 
     def _level(self, module, plans, xyz, feature, s):
         new_xyz, idxs = s
@@ -197,3 +201,182 @@ class FrozenPointNet2:
                 out[:, :, col:col + cl] = y
             col += cl
         return new_xyz, out
+
+
+class FrozenPointNet2(_FrozenEncoder):
+    """See the module docstring.  ``refresh()`` re-reads weights and running statistics from the network."""
+
+    @torch.no_grad()
+    def refresh(self):
+        self._refresh_encoder()
+        self.head = self._copy("head", self.net.fc_layer)
+        return self
+
+    def __call__(self, xyz, feature, sampling=None):
+        return self.run(xyz, feature, sampling)[1]
+
+    @torch.no_grad()
+    def run(self, xyz, feature, sampling=None):
+        """-> ([feature of every set-abstraction level], logits [B, n_classes])."""
+        feats = [f for _, f in self._encode(xyz, feature, sampling)]
+        feature = feats[-1].squeeze(dim=1)
+        logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, feature.shape[0], MAX_ROWS)]
+        return feats, logits[0] if len(logits) == 1 else torch.cat(logits)
+
+
+def _pad32(t, fill):
+    """``t`` ([C, ...] or [C]) with its first dimension padded to a multiple of 32 with ``fill``."""
+    c = t.shape[0]
+    cp = -(-c // 32) * 32
+    if cp == c:
+        return t.contiguous()
+    out = torch.full((cp,) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)
+    out[:c] = t
+    return out
+
+
+class _FusedFP:
+    """Snapshot of one feature-propagation level for pcl_fp_level_infer_f32, optionally with the head layers behind it.
+
+    ``D1`` skip channels (the first ``n_onehot`` of them the one-hot class label, a per-cloud bias), then the coarse
+    channels; skips of at most 8 (other) channels fold inline, wider ones through the per-point table ``Us``."""
+
+    def __init__(self, mlp, D1, n_onehot=0, head=()):
+        W0 = mlp.weights[0].detach().float().contiguous().clone()
+        self.D1, self.n_onehot, self.slope = D1, n_onehot, float(mlp.slope)
+        self.CS = D1 - n_onehot
+        self.inline = self.CS <= 8
+        self.W0 = W0
+        self.Woh = W0[:, :n_onehot].contiguous() if n_onehot else None
+        self.Wsk = None if self.CS == 0 else (W0[:, n_onehot:D1] if self.inline else W0[:, n_onehot:D1].contiguous())
+        self.Wc = W0[:, D1:].contiguous()
+        layers = [(mlp, l, l < mlp.n_layers - 1 or mlp.last_act) for l in range(mlp.n_layers)]
+        for h in head:
+            layers += [(h, l, l < h.n_layers - 1 or h.last_act) for l in range(h.n_layers)]
+        self.widths = [m.weights[l].shape[0] for m, l, _ in layers]
+        self.act_mask = sum(1 << i for i, (_, _, a) in enumerate(layers) if a)
+        self.tap_layer = mlp.n_layers - 1 if head else None          # the level's own output, stored beside the head's
+        L = len(layers)
+        self.Ws, self.scales, self.shifts = [None], [], []
+        for i, (m, l, _) in enumerate(layers):
+            sc, sh = _eval_consts(m, l)
+            W = m.weights[l].detach().float()
+            if i == L - 1:                                           # the last layer: padded to 32 columns with zero weights
+                W, sc, sh = _pad32(W, 0.0), _pad32(sc, 1.0), _pad32(sh, 0.0)
+            if i:
+                self.Ws.append(W.contiguous().clone())
+            self.scales.append(sc)
+            self.shifts.append(sh)
+        self.c_widths = (ctypes.c_int32 * L)(*self.widths)
+        self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in self.Ws])
+        self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
+        self.c_shift = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.shifts])
+
+    @staticmethod
+    def _rows(X, W, P):
+        """X [P, Cin] W^T -> [P, Cout] (stats-free library GEMM)."""
+        Cout, Cin = W.shape
+        Y = torch.empty((P, Cout), dtype=torch.float32, device=X.device)
+        _lib.call("pcl_linear_fwd_rows_f32", _p(X), _p(W), None, None, None, 0.0, P, Cin, Cout, _p(Y), None, None, None, _stream(),
+                  tag=f"pt{Cin}x{Cout}")
+        return Y
+
+    def run(self, xyz1, xyz2, skip, coarse, onehot=None):
+        """xyz1 [B,N,3], xyz2 [B,S,3], skip [B,N,D1 - n_onehot] (or None), coarse [B,S,D2], onehot [B, n_onehot]
+        -> (out [B, N, widths[-1]], tap [B, N, widths[tap_layer]] or None)."""
+        B, N, _ = xyz1.shape
+        S = coarse.shape[1]
+        dev = xyz1.device
+        Uc = self._rows(coarse.reshape(B * S, -1).contiguous(), self.Wc, B * S)
+        idx3 = w3 = None
+        if S == 1:                                                   # a one-row coarse level: a per-cloud bias
+            cb, Uc = Uc, None
+        else:
+            idx3, w3 = three_nn(xyz1, xyz2)
+            cb = None
+        if self.Woh is not None:
+            c = self._rows(onehot.reshape(B, self.n_onehot).float().contiguous(), self.Woh, B)
+            cb = c if cb is None else cb + c
+        Us = fs = None
+        if self.CS:
+            fs = skip.reshape(B * N, self.CS).contiguous()
+            if not self.inline:
+                Us, fs = self._rows(fs, self.Wsk, B * N), None
+        out = torch.empty((B, N, self.widths[-1]), dtype=torch.float32, device=dev)
+        tap = None if self.tap_layer is None else torch.empty((B, N, self.widths[self.tap_layer]), dtype=torch.float32, device=dev)
+        _lib.call("pcl_fp_level_infer_f32", _p(Us), _p(fs), _p(self.Wsk) if fs is not None else None, self.CS if fs is not None else 0,
+                  self.W0.shape[1], _p(Uc), _p(idx3), _p(w3), S, _p(cb), B, N, len(self.widths), self.c_widths, self.c_W, self.c_scale,
+                  self.c_shift, self.act_mask, self.slope, _p(out), out.shape[-1], _p(tap), -1 if tap is None else self.tap_layer,
+                  0 if tap is None else tap.shape[-1], _stream())
+        return out, tap
+
+
+def _fp_supported(widths):
+    return len(widths) <= 5 and bool(_lib.size_query("pcl_fp_level_infer_supported", len(widths), *(list(widths) + [0] * (5 - len(widths)))))
+
+
+def _head_fusable(fp_mlp, head1, head2):
+    """FP1 + Conv1d/BN (no activation) + Conv1d/bias (no BN, no activation) in one launch."""
+    return (head1.n_layers == 1 and head2.n_layers == 1 and head1.bn and not head2.bn and not head1.last_act and not head2.last_act
+            and head1.spec[0] == fp_mlp.spec[-1] and head2.spec[0] == head1.spec[-1]
+            and _fp_supported([w.shape[0] for w in fp_mlp.weights] + [head1.spec[-1], head2.spec[-1]]))
+
+
+class FrozenPointNet2Partseg(_FrozenEncoder):
+    """Frozen evaluator of ``PointNet2_partseg`` / its ``PointNetMSG`` (see the module docstring): the encoder plan of the
+    classifiers, one launch per feature-propagation level, the head fused into the last one.  ``refresh()`` re-reads weights
+    and running statistics from the network."""
+
+    N_ONEHOT = 16                  # FP1's skip: cat(one-hot class label [16], xyz [3], feature [3])  (pointnet2_partseg.py:170-173)
+
+    @torch.no_grad()
+    def refresh(self):
+        net = self.net
+        self._refresh_encoder()
+        enc = [sum(mlp.spec[-1] for mlp in module.mlps) for module in net.pointnet_modules]
+        skips = {"fp3": enc[1], "fp2": enc[0], "fp1": self.N_ONEHOT + 6}
+        self.fp = {}
+        for name in ("fp3", "fp2", "fp1"):
+            mlp = getattr(net, name).mlp
+            head = ()
+            if name == "fp1" and _head_fusable(mlp, net.head1, net.head2):
+                head = (net.head1, net.head2)
+            widths = [w.shape[0] for w in mlp.weights] + [h.spec[-1] for h in head]
+            if 2 <= mlp.n_layers and _fp_supported(widths):
+                self.fp[name] = ("fused", _FusedFP(mlp, skips[name], self.N_ONEHOT if name == "fp1" else 0, head))
+            else:
+                self.fp[name] = ("module", self._copy(name, getattr(net, name)))
+        self.head_fused = self.fp["fp1"][0] == "fused" and self.fp["fp1"][1].tap_layer is not None
+        self.head = None if self.head_fused else (self._copy("head1", net.head1), self._copy("head2", net.head2))
+        return self
+
+    def __call__(self, xyz, feature, cls_label, sampling=None):
+        return self.run(xyz, feature, cls_label, sampling)[1]
+
+    def _fp(self, name, xyz1, xyz2, skip, coarse, onehot=None):
+        kind, plan = self.fp[name]
+        if kind == "fused":
+            return plan.run(xyz1, xyz2, skip, coarse, onehot)
+        if onehot is not None:
+            B, N, _ = xyz1.shape
+            skip = torch.cat([onehot.view(B, 1, -1).expand(B, N, onehot.shape[-1]), skip], 2)
+        return plan(xyz1, xyz2, skip, coarse), None
+
+    @torch.no_grad()
+    def run(self, xyz, feature, cls_label, sampling=None):
+        """-> ([sa1, sa2, sa3, fp3, fp2, fp1] level features, logits [B, part_num, N] (the network's layout and view))."""
+        B, N, _ = xyz.shape
+        xyz = xyz.contiguous()
+        (l1_xyz, l1), (l2_xyz, l2), (_, l3) = self._encode(xyz, feature, sampling)
+        l3_xyz = torch.zeros((B, 1, 3), device=xyz.device, dtype=xyz.dtype)
+        f3, _ = self._fp("fp3", l2_xyz, l3_xyz, l2, l3)
+        f2, _ = self._fp("fp2", l1_xyz, l2_xyz, l1, f3)
+        onehot = cls_label.reshape(B, self.N_ONEHOT).float()
+        out, tap = self._fp("fp1", xyz, l1_xyz, torch.cat([xyz, feature.float()], 2), f2, onehot)
+        if self.head_fused:
+            f1, logits = tap, out
+        else:
+            f1 = out
+            h1, h2 = self.head
+            logits = h2(h1(f1))
+        return [l1, l2, l3, f3, f2, f1], logits.permute(0, 2, 1)

@@ -3,9 +3,14 @@
 alternate window by window in one process, device events around each window, median over the windows; peak
 ``torch.cuda.max_memory_allocated`` above the resident set of one forward of each form.  Prints one JSON line.
 
-    python tools/bench_infer.py [--windows 7] [--iters 5] [--warmup 3] [--batch 32 256] [--nets ssg msg]
+The part-seg PointNet++ nets (``--nets partseg_ssg partseg_msg``; B in {16, 64}, N = 2048 unless --batch / --points say otherwise)
+compare three forms: ``eval`` (the network's default accumulation, fp64 flush every 32 terms), ``eval_acc0`` (a copy with
+``set_accumulation(copy, 0)``: plain fp32 chains) and ``frozen``.
+
+    python tools/bench_infer.py [--windows 7] [--iters 5] [--warmup 3] [--batch 32 256] [--nets ssg msg] [--points 1024]
 """
 import argparse
+import copy
 import json
 import os
 import statistics
@@ -42,8 +47,9 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--batch", type=int, nargs="+", default=[32, 256])
-    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"])
+    ap.add_argument("--batch", type=int, nargs="+", default=None, help="default: 32 256 (cls), 16 64 (part-seg)")
+    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg"])
+    ap.add_argument("--points", type=int, default=None, help="default: 1024 (cls), 2048 (part-seg)")
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -52,23 +58,42 @@ def main():
     from pointcloudlib_amd.inference import frozen
     from pointcloudlib_amd.networks.cls.pointnet2 import PointNet2_cls, PointNetMSG
     dev = torch.device("cuda")
-    res = {"N": 1024, "windows": a.windows, "iters": a.iters, "cases": []}
+    cls_only = all(k in ("ssg", "msg") for k in a.nets)
+    res = {"N": (a.points or 1024) if cls_only else (a.points or 2048), "windows": a.windows, "iters": a.iters, "cases": []}
     for kind in a.nets:
+        seg = kind.startswith("partseg")
+        N = a.points or (2048 if seg else 1024)
         torch.manual_seed(0)
-        net = (PointNet2_cls if kind == "ssg" else PointNetMSG)().to(dev).eval()
+        if seg:
+            from pointcloudlib_amd.misc.layers import set_accumulation
+            from pointcloudlib_amd.networks.seg.pointnet2_partseg import PointNet2_partseg, PointNetMSG as PartsegMSG
+            net = (PointNet2_partseg if kind == "partseg_ssg" else PartsegMSG)().to(dev).eval()
+            net0 = set_accumulation(copy.deepcopy(net), 0)
+        else:
+            net = (PointNet2_cls if kind == "ssg" else PointNetMSG)().to(dev).eval()
         fnet = frozen(net)
-        for B in a.batch:
-            xyz = torch.from_numpy(synth.gauss_ball(B, 1024, 1)).to(dev)
-            nrm = torch.from_numpy(synth.unit_normals(B, 1024, 2)).to(dev)
+        for B in a.batch or ([16, 64] if seg else [32, 256]):
+            xyz = torch.from_numpy(synth.gauss_ball(B, N, 1)).to(dev)
+            nrm = torch.from_numpy(synth.unit_normals(B, N, 2)).to(dev)
+            extra = ()
+            if seg:
+                onehot = torch.zeros(B, 16, device=dev)
+                onehot[torch.arange(B), torch.arange(B) % 16] = 1.0
+                extra = (onehot,)
 
-            def eval_fwd():
+            def eval_fwd(net=net):
                 with torch.no_grad():
-                    return net(xyz, nrm)
+                    return net(xyz, nrm, *extra)
 
             def frozen_fwd():
-                return fnet(xyz, nrm)
+                return fnet(xyz, nrm, *extra)
 
-            forms = [("frozen", frozen_fwd)] if a.frozen_only else [("eval", eval_fwd), ("frozen", frozen_fwd)]
+            if a.frozen_only:
+                forms = [("frozen", frozen_fwd)]
+            elif seg:
+                forms = [("eval", eval_fwd), ("eval_acc0", lambda: eval_fwd(net0)), ("frozen", frozen_fwd)]
+            else:
+                forms = [("eval", eval_fwd), ("frozen", frozen_fwd)]
             for _ in range(a.warmup):
                 for _, fn in forms:
                     fn()
@@ -76,13 +101,16 @@ def main():
             for w in range(a.windows):
                 for name, fn in (forms if w % 2 == 0 else forms[::-1]):
                     times[name].append(_window(fn, a.iters))
-            case = {"net": kind, "B": B}
+            case = {"net": kind, "B": B, "N": N} if seg else {"net": kind, "B": B}
             for name, fn in forms:
                 case[f"{name}_ms"] = round(statistics.median(times[name]), 4)
                 case[f"{name}_ms_min"] = round(min(times[name]), 4)
                 case[f"{name}_peak_mib"] = round(_peak(fn) / 2**20, 1)
             if not a.frozen_only:
                 case["speedup"] = round(case["eval_ms"] / case["frozen_ms"], 3)
+                if seg:
+                    case["speedup_vs_acc0"] = round(case["eval_acc0_ms"] / case["frozen_ms"], 3)
+                    case["mem_ratio"] = round(case["eval_peak_mib"] / max(case["frozen_peak_mib"], 0.1), 1)
                 with torch.no_grad():
                     case["max_abs_logit_diff"] = float((eval_fwd() - frozen_fwd()).abs().max())
             res["cases"].append(case)

@@ -71,7 +71,8 @@ def lookahead(loader):
         cur = nxt
 
 
-def run_epoch(net, name, loader, dev, seg_num_all, optimizer=None, side=None):
+def run_epoch(net, name, loader, dev, seg_num_all, optimizer=None, side=None, fnet=None):
+    """One pass over ``loader``; ``fnet``: a frozen evaluator of ``net`` (pointcloudlib_amd.inference) that runs the test forwards."""
     train = optimizer is not None
     net.train(train)
     loss_sum, count = 0.0, 0
@@ -85,7 +86,9 @@ def run_epoch(net, name, loader, dev, seg_num_all, optimizer=None, side=None):
         one_hot = torch.zeros(label.shape[0], 16, device=dev)
         one_hot[torch.arange(label.shape[0], device=dev), label[:, 0].to(dev)] = 1                  # :103-107
         with torch.set_grad_enabled(train):
-            if prefetch:
+            if fnet is not None and not train:
+                scores = fnet(data, data, one_hot).permute(0, 2, 1)                  # the network's own inputs (:111-112)
+            elif prefetch:
                 scores = net(data, data, one_hot, sampling=pending).permute(0, 2, 1)
                 # the encoder's FPS / ball query of the NEXT batch on the side stream, beside this batch's backward
                 nxt_dev = nxt[0].to(dev) if nxt is not None else None
@@ -125,7 +128,11 @@ def main():
     ap.add_argument("--prefetch_sampling", action="store_true",
                     help="pointnet2: issue the next batch's FPS / ball query on a side stream (off by default: this step is host-bound,\n"
                          "measured 3.31 ms with vs 3.15 ms without at B=16, N=2048)")
+    ap.add_argument("--fast_eval", action="store_true",
+                    help="--model pointnet2 | pointnet2_msg: the test pass through pointcloudlib_amd.inference.frozen(net)")
     a = ap.parse_args()
+    if a.fast_eval and a.model not in ("pointnet2", "pointnet2_msg"):
+        raise SystemExit("--fast_eval: --model pointnet2 or pointnet2_msg only")
     if not torch.cuda.is_available():
         raise SystemExit("train_partseg.py needs a GPU (the HIP path has no CPU fallback)")
     dev = torch.device("cuda")
@@ -141,10 +148,15 @@ def main():
     net = build_model(a.model).to(dev)
     opt = make_sgd(net.parameters(), lr=a.lr, momentum=a.momentum, weight_decay=1e-4)
     side = "own" if (a.prefetch_sampling and a.model.startswith("pointnet2")) else None
+    fnet = None
+    if a.fast_eval:
+        from pointcloudlib_amd.inference import frozen
+        fnet = frozen(net)
     for epoch in range(a.epochs):
         loss, acc, bacc, iou, rate = run_epoch(net, a.model, train_set, dev, train_set.seg_num_all, opt, side)
         print(f"Train {epoch}, loss: {loss:.6f}, train acc: {acc:.6f}, train avg acc: {bacc:.6f}, train iou: {iou:.6f} ({rate:.0f} shapes/s)", flush=True)
-        loss, acc, bacc, iou, rate = run_epoch(net, a.model, test_set, dev, test_set.seg_num_all, None, side)
+        loss, acc, bacc, iou, rate = run_epoch(net, a.model, test_set, dev, test_set.seg_num_all, None, side,
+                                               None if fnet is None else fnet.refresh())
         print(f"Test {epoch}, loss: {loss:.6f}, test acc: {acc:.6f}, test avg acc: {bacc:.6f}, test iou: {iou:.6f} ({rate:.0f} shapes/s)", flush=True)
 
 
