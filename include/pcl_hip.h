@@ -75,6 +75,22 @@ void pcl_set_fps_tuning(int threads_per_cloud, int issue_priority);
 int pcl_fps_f32(const float* xyz, int B, int N, int m, int tie_stride, double skip_sqnorm_le,
                 const int32_t* start_idx, int32_t* idx_out, float* new_xyz_out, void* stream);
 
+/* ---- batches of clouds with different point counts ("ragged" entry points) ---------------------
+ * No reference counterpart (the reference's loaders resample every cloud to one size, data_utils/modelnet40_loader.py:116-119);
+ * each ragged entry point computes, per cloud, what its dense neighbour computes on that cloud alone.
+ * Convention: a batch is still [B,N,.] with N the CAPACITY; n_valid is int32 [B] on the device, cloud b consists of rows
+ * 0 .. n_valid[b]-1, and the rows from n_valid[b] on are pad rows whose contents (NaN included) influence no result.
+ * On the device every count is clamped to [1, N], so a bad count can never index outside the batch; anything stricter
+ * (m <= n_valid[b], start_idx[b] < n_valid[b]) is the caller's contract.  Raggedness lives in the FIRST level of PointNet++
+ * only: once FPS has drawn its m centres per cloud from the cloud's own points everything downstream is dense again, and the
+ * grouping / set-abstraction kernels reach the cloud only through idx, which never names a pad row.
+ *
+ * pcl_fps_f32 per cloud on its first n_valid[b] points: points k >= n_valid[b] are dead (never sampled, as the skipped
+ * near-origin points of misc/ops.py:162-163 are); the tie order (bitreverse(k mod S), k) does not depend on N, so idx_out /
+ * new_xyz_out equal those of the cloud alone for the same tie_stride.  Requires 1 <= m <= N; contract m <= n_valid[b] <= N. */
+int pcl_fps_ragged_f32(const float* xyz, const int32_t* n_valid, int B, int N, int m, int tie_stride, double skip_sqnorm_le,
+                       const int32_t* start_idx, int32_t* idx_out, float* new_xyz_out, void* stream);
+
 /* ---- ball query -------------------------------------------------------------------------------
  * Replaces query_ball_point_kernel, misc/ops.py:291-330 (launch :332-337).
  *   new_xyz [B,m,3], xyz [B,N,3] -> idx_out [B,m,nsample], cnt_out [B,m] (nullable).
@@ -88,6 +104,15 @@ int pcl_ball_query_f32(const float* new_xyz, const float* xyz, int B, int m, int
  * [B,m,nsamples[r]], cnt_out[r] [B,m] on the device.  Every list is identical to pcl_ball_query_f32's for that radius. */
 int pcl_ball_query_multi_f32(const float* new_xyz, const float* xyz, int B, int m, int N, int n_radii, const float* radii,
                              const int32_t* nsamples, int32_t* const* idx_out, int32_t* const* cnt_out, void* stream);
+/* reference: query_ball_point_kernel, misc/ops.py:291-330, per cloud on its first n_valid[b] points (see the ragged convention
+ * above): only those are staged and scanned; lists, first-hit padding and cnt as for the cloud alone, no index >= n_valid[b]
+ * is ever written (a row without a hit is zero-filled with cnt 0). */
+int pcl_ball_query_ragged_f32(const float* new_xyz, const float* xyz, const int32_t* n_valid, int B, int m, int N, float radius,
+                              int nsample, int32_t* idx_out, int32_t* cnt_out, void* stream);
+/* reference: as pcl_ball_query_multi_f32, per cloud on its first n_valid[b] points */
+int pcl_ball_query_multi_ragged_f32(const float* new_xyz, const float* xyz, const int32_t* n_valid, int B, int m, int N, int n_radii,
+                                    const float* radii, const int32_t* nsamples, int32_t* const* idx_out, int32_t* const* cnt_out,
+                                    void* stream);
 
 /* ---- grouping ---------------------------------------------------------------------------------
  * Replaces the three Var.reindex gathers + subtract + concat of BallQueryGrouper.execute,
@@ -160,6 +185,11 @@ int pcl_knn_point_matmul_f32(const float* xyz, const float* new_xyz, int B, int 
  *   interp fwd: out[b,n,:] = sum_j w3[b,n,j] * points2[b,idx3[b,n,j],:];  bwd zero-fills gpoints2. */
 int pcl_three_nn_f32(const float* xyz1, const float* xyz2, int B, int N, int S, int32_t* idx3,
                      float* w3, void* stream);
+/* reference: misc/ops.py:83-93 per cloud on its first n1_valid[b] targets and n2_valid[b] sources (ragged convention above;
+ * either count pointer may be NULL: that side dense).  Sources beyond n2_valid[b] are not scanned and the S == 1 / S == 2 rules
+ * apply to n2_valid[b]; target rows beyond n1_valid[b] get idx 0, w 0 (defined, finite) without a scan. */
+int pcl_three_nn_ragged_f32(const float* xyz1, const int32_t* n1_valid, const float* xyz2, const int32_t* n2_valid, int B, int N,
+                            int S, int32_t* idx3, float* w3, void* stream);
 /* reference: replaces the weighted index_points sum of PointNetFeaturePropagation, misc/ops.py:90-93 */
 int pcl_three_interp_f32(const float* points2, const int32_t* idx3, const float* w3, int B, int N,
                          int S, int D, float* out, void* stream);
@@ -781,6 +811,14 @@ int pcl_fp_level_infer_f32(const float* Us, const float* skip_small, const float
                            const int32_t* idx3, const float* w3, int S, const float* cloud_bias, int B, int N, int L,
                            const int32_t* widths, const float* const* W, const float* const* scale, const float* const* shift,
                            int act_mask, float slope, float* out, int ldo, float* tap, int tap_layer, int ldt, void* stream);
+/* reference: as pcl_fp_level_infer_f32, with n_valid [B] target rows per cloud (ragged convention above): a 64-row tile wholly
+ * beyond n_valid[b] does no layer work; pad rows of out (and of the tap) are written as exact zeros; pad rows of Us /
+ * skip_small (NaN included) never reach a valid row's result.  idx3 / w3 from pcl_three_nn_ragged_f32. */
+int pcl_fp_level_infer_ragged_f32(const float* Us, const float* skip_small, const float* Ws_small, int CS, int ldw, const float* Uc,
+                                  const int32_t* idx3, const float* w3, int S, const float* cloud_bias, const int32_t* n_valid,
+                                  int B, int N, int L, const int32_t* widths, const float* const* W, const float* const* scale,
+                                  const float* const* shift, int act_mask, float slope, float* out, int ldo, float* tap,
+                                  int tap_layer, int ldt, void* stream);
 
 #ifdef __cplusplus
 }

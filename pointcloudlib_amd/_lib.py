@@ -66,6 +66,12 @@ _SIGS = {
     "pcl_last_error": (ctypes.c_char_p, []),
     "pcl_optimal_block": (c_int, [c_int]),
     "pcl_fps_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_double, _P, _P, _P, _P]),
+    "pcl_fps_ragged_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_double, _P, _P, _P, _P]),
+    "pcl_ball_query_ragged_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P]),
+    "pcl_ball_query_multi_ragged_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "pcl_three_nn_ragged_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "pcl_fp_level_infer_ragged_f32": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P,
+                                              c_int, c_float, _P, c_int, _P, c_int, c_int, _P]),
     "pcl_ball_query_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P]),
     "pcl_ball_query_multi_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "pcl_group_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),

@@ -100,8 +100,14 @@ __device__ long long g_fps_ph[8];
 // in parallel, after it); (2) the next centre's LDS read is issued before the step's index store; (3) the four in-row DPP stages move
 // the key without first copying it (dpp_f64_perm); (4) with several waves, lane 63 stores the wave's maximum itself instead of going
 // through two v_readlane + a move back into a vector register.  Same arithmetic, same keys, same winners.
-template <int T, int PPT>
-__global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, int N, int m, int log2S,
+//
+// RAGGED (pcl_fps_ragged_f32): cloud b is its first n = clamp(n_valid[b], 1, N) rows.  The rows from n on are dead the way skipped
+// near-origin points are -- key 0, never staged, never read -- and the tie rank of a point does not depend on how many follow it
+// (rank' is order-isomorphic to (bitrev(k mod S), k) for ANY table size RT >= n), so the picks are those of the cloud alone.
+// n is uniform per workgroup (one scalar load ahead of the chain); nothing on the dependent step changes.  The dense instantiation
+// (RAGGED = false) does not read n_valid and compiles to the code it was.
+template <int T, int PPT, bool RAGGED>
+__global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ n_valid, int N, int m, int log2S,
                                                 double skip_thr, const int32_t* __restrict__ start_idx,
                                                 int32_t* __restrict__ idx_out, float* __restrict__ new_xyz_out, int prio) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -117,6 +123,8 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, i
     const float* p = xyz + (size_t)b * N * 3;
     int32_t* out = idx_out + (size_t)b * m;
     float* oxyz = new_xyz_out ? new_xyz_out + (size_t)b * m * 3 : nullptr;
+    int n = N;                                                           // the cloud's own point count (a bad count is clamped, never trusted)
+    if constexpr (RAGGED) n = min(max(__builtin_amdgcn_readfirstlane(n_valid[b]), 1), N);
     // a serial chain: `prio` (pcl_set_fps_tuning) decides who wins issue arbitration when it is co-resident with throughput kernels.
     // Inline in a forward pass the chain IS the critical path (3); one batch ahead on a side stream it has a whole backward pass to
     // finish in and every slot it takes is taken from a kernel the step waits for (0).
@@ -144,7 +152,7 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, i
     };
 
     // stage the cloud: coalesced dword reads of the AoS xyz, scattered into the float4 slot of the point's rank
-    for (int i = tid; i < 3 * N; i += T) {
+    for (int i = tid; i < 3 * n; i += T) {
         const int k = i / 3, c = i - 3 * k;
         s_flat[ES * rank_of((unsigned)k) + c] = p[i];
     }
@@ -157,7 +165,7 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, i
     for (int j = 0; j < PPT; ++j) {
         const unsigned k = (unsigned)(tid + j * T);
         px[j] = py[j] = pz[j] = 0.f; md[j] = 0.f; lo[j] = 0u;
-        if (k < (unsigned)N) {
+        if (k < (unsigned)n) {
             const unsigned rk = rank_of(k);
             const float4 v = entry(rk);
             px[j] = v.x; py[j] = v.y; pz[j] = v.z;
@@ -171,7 +179,7 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, i
 
     // NOTE: nothing is stored to global memory inside the chain: a global store per step would be drained
     // (vmcnt(0)) by every __syncthreads(), adding an HBM round trip to each of the m-1 dependent steps.
-    const int old0 = start_idx ? min(max(start_idx[b], 0), N - 1) : 0;   // a caller's start index is clamped into the cloud, never trusted
+    const int old0 = start_idx ? min(max(start_idx[b], 0), n - 1) : 0;   // a caller's start index is clamped into the cloud, never trusted
     unsigned r = rank_of((unsigned)old0);
     if (tid == 0) s_out[0] = r;
     const int lane = tid & 63, wid = tid >> 6;
@@ -237,9 +245,10 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, i
 
 // Large-cloud variant (N*16 B does not fit LDS next to the slots): only the running min-distance
 // (4 B/point, -1 = never a candidate) lives in LDS, coordinates are re-read from L2 every step.
-// Same arithmetic and tie rule as above.  Clouds beyond ~40k points are refused (PCL_ENOSUP).
-template <int T>
-__global__ __launch_bounds__(T) void fps_kernel_lds(const float* __restrict__ xyz, int N, int m, int log2S,
+// Same arithmetic and tie rule as above.  Clouds beyond ~40k points are refused (PCL_ENOSUP).  RAGGED: only the cloud's own
+// n points are initialised and scanned (`cnt` keeps the capacity's value: the rank order does not depend on it).
+template <int T, bool RAGGED>
+__global__ __launch_bounds__(T) void fps_kernel_lds(const float* __restrict__ xyz, const int32_t* __restrict__ n_valid, int N, int m, int log2S,
                                                     double skip_thr, const int32_t* __restrict__ start_idx,
                                                     int32_t* __restrict__ idx_out, float* __restrict__ new_xyz_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -252,13 +261,15 @@ __global__ __launch_bounds__(T) void fps_kernel_lds(const float* __restrict__ xy
     float* oxyz = new_xyz_out ? new_xyz_out + (size_t)b * m * 3 : nullptr;
     const unsigned S = 1u << log2S;
     const unsigned cnt = ((unsigned)N + S - 1) >> log2S;
-    for (int k = tid; k < N; k += T) {
+    int n = N;
+    if constexpr (RAGGED) n = min(max(__builtin_amdgcn_readfirstlane(n_valid[b]), 1), N);
+    for (int k = tid; k < n; k += T) {
         const float x = p[3 * k], y = p[3 * k + 1], z = p[3 * k + 2];
         const float mag = __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
         s_md[k] = ((double)mag <= skip_thr) ? -1.0f : 1e10f;
     }
     __syncthreads();
-    int old = start_idx ? min(max(start_idx[b], 0), N - 1) : 0;      // a caller's start index is clamped into the cloud, never trusted
+    int old = start_idx ? min(max(start_idx[b], 0), n - 1) : 0;      // a caller's start index is clamped into the cloud, never trusted
     if (tid == 0) out[0] = old;
     const int lane = tid & 63, wid = tid >> 6;
     for (int step = 1; step < m; ++step) {
@@ -266,7 +277,7 @@ __global__ __launch_bounds__(T) void fps_kernel_lds(const float* __restrict__ xy
         if (tid == 0 && oxyz) { oxyz[(step - 1) * 3 + 0] = cx; oxyz[(step - 1) * 3 + 1] = cy; oxyz[(step - 1) * 3 + 2] = cz; }
         float best = -1.0f;
         unsigned bestr = 0xFFFFFFFFu, bestk = 0;
-        for (int k = tid; k < N; k += T) {
+        for (int k = tid; k < n; k += T) {
             const float mdk = s_md[k];
             const float d = sq_dist3(p[3 * k], p[3 * k + 1], p[3 * k + 2], cx, cy, cz);
             const float d2 = fminf(d, mdk);
@@ -311,17 +322,60 @@ static size_t fps_lds_bytes(int N, int m, int log2S, int entry_floats) {
     return 256 + (((size_t)entry_floats * 4 * (RT + 1) + 15) & ~(size_t)15) + sizeof(int) * (size_t)m;
 }
 
-template <int T, int PPT>
-static int launch_fps(const float* xyz, int B, int N, int m, int log2S, double thr, const int32_t* start,
+template <int T, int PPT, bool RAGGED>
+static int launch_fps(const char* who, const float* xyz, const int32_t* n_valid, int B, int N, int m, int log2S, double thr, const int32_t* start,
                       int32_t* idx, float* nx, hipStream_t st) {
     const size_t lds = fps_lds_bytes(N, m, log2S, T * PPT > 1024 ? 3 : 4);           // slots + rank-indexed xyz + sampled ranks
-    auto kern = fps_kernel<T, PPT>;
+    auto kern = fps_kernel<T, PPT, RAGGED>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(PCL_EHIP, "fps: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
     }
-    hipLaunchKernelGGL(kern, dim3(B), dim3(T), lds, st, xyz, N, m, log2S, thr, start, idx, nx, g_fps_prio);
-    return check_launch("pcl_fps_f32");
+    hipLaunchKernelGGL(kern, dim3(B), dim3(T), lds, st, xyz, n_valid, N, m, log2S, thr, start, idx, nx, g_fps_prio);
+    return check_launch(who);
+}
+
+// the body of pcl_fps_f32 (RAGGED = false: the dense instantiations, n_valid unused) and of pcl_fps_ragged_f32
+template <bool RAGGED>
+static int fps_run(const char* who, const float* xyz, const int32_t* n_valid, int B, int N, int m, int tie_stride, double skip_sqnorm_le,
+                   const int32_t* start_idx, int32_t* idx_out, float* new_xyz_out, void* stream) {
+    PCL_REQUIRE(xyz && idx_out && (!RAGGED || n_valid), "%s: null pointer", who);
+    PCL_REQUIRE(B >= 0 && N >= 1 && m >= 1 && m <= N, "%s: need 1 <= m <= N (B=%d N=%d m=%d)", who, B, N, m);
+    PCL_REQUIRE(tie_stride >= 1 && tie_stride <= 512 && (tie_stride & (tie_stride - 1)) == 0,
+                "%s: tie_stride must be a power of two in [1,512], got %d", who, tie_stride);
+    if (B == 0) return PCL_OK;
+    int log2S = 0;
+    while ((1 << log2S) < tie_stride) ++log2S;
+    hipStream_t st = as_stream(stream);
+    // threads per cloud: ~4-8 points per lane keeps the VALU part and the cross-wave part balanced
+    // (raced on MI355X, B = 32 / 16, round 4 -- ns per dependent step at T = 64 / 128 / 256 / 512 / 1024:
+    //  N = 512: 336 / 355 / 374 / - / -;  N = 1024: 479 / 410 / 381 / 416 / 736;  N = 2048: - / 550 / 450 / 475 / 766;  N = 4096: - / - / 589 / 611 / 869.
+    //  One wave per cloud -- no barrier, no LDS exchange, DPP only -- wins up to 512 points; beyond, four waves: the cross-wave
+    //  exchange costs less than the eight more distance evaluations per lane)
+    int T = g_fps_threads > 0 ? g_fps_threads : (N <= 512 ? 64 : N <= 4096 ? 256 : N <= 8192 ? 512 : 1024);
+    const int ppt = (N + T - 1) / T;
+#define PCL_FPS_CASE(TT, PP) \
+    if (T == TT && ppt <= PP) return launch_fps<TT, PP, RAGGED>(who, xyz, n_valid, B, N, m, log2S, skip_sqnorm_le, start_idx, idx_out, new_xyz_out, st);
+    if (fps_lds_bytes(N, m, log2S, N > 1024 ? 3 : 4) <= 158 * 1024) {
+        PCL_FPS_CASE(64, 1) PCL_FPS_CASE(64, 2) PCL_FPS_CASE(64, 4) PCL_FPS_CASE(64, 8) PCL_FPS_CASE(64, 16) PCL_FPS_CASE(64, 32)
+        PCL_FPS_CASE(128, 1) PCL_FPS_CASE(128, 2) PCL_FPS_CASE(128, 4) PCL_FPS_CASE(128, 8) PCL_FPS_CASE(128, 16)
+        PCL_FPS_CASE(256, 1) PCL_FPS_CASE(256, 2) PCL_FPS_CASE(256, 4) PCL_FPS_CASE(256, 8) PCL_FPS_CASE(256, 16)
+        PCL_FPS_CASE(512, 1) PCL_FPS_CASE(512, 2) PCL_FPS_CASE(512, 4) PCL_FPS_CASE(512, 8) PCL_FPS_CASE(512, 16)
+        PCL_FPS_CASE(1024, 1) PCL_FPS_CASE(1024, 2) PCL_FPS_CASE(1024, 4) PCL_FPS_CASE(1024, 8)
+        // (1024 threads x 16 points per lane does not fit the 128 registers of a 1024-thread workgroup -- it spilled 16 of them into the step
+        //  loop; clouds of 8 193 .. 10 100 points take the LDS-resident kernel below like the larger ones)
+    }
+#undef PCL_FPS_CASE
+    // large clouds: min-distance array in LDS (4 B/point), coordinates re-read from L2 each step
+    const size_t lds = sizeof(FpsSlot) * 2 * 16 + sizeof(float) * (size_t)N;
+    if (lds > 160 * 1024) return fail(PCL_ENOSUP, "%s: N=%d exceeds the LDS-resident limit (%d points)", who, N, (160 * 1024 - 512) / 4);
+    auto kern = fps_kernel_lds<1024, RAGGED>;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return fail(PCL_EHIP, "fps: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(kern, dim3(B), dim3(1024), lds, st, xyz, n_valid, N, m, log2S, skip_sqnorm_le, start_idx, idx_out, new_xyz_out);
+    return check_launch(who);
 }
 
 }  // namespace pcl
@@ -343,41 +397,10 @@ extern "C" void pcl_set_fps_tuning(int threads_per_cloud, int issue_priority) {
 
 extern "C" int pcl_fps_f32(const float* xyz, int B, int N, int m, int tie_stride, double skip_sqnorm_le,
                            const int32_t* start_idx, int32_t* idx_out, float* new_xyz_out, void* stream) {
-    PCL_REQUIRE(xyz && idx_out, "pcl_fps_f32: null pointer");
-    PCL_REQUIRE(B >= 0 && N >= 1 && m >= 1 && m <= N, "pcl_fps_f32: need 1 <= m <= N (B=%d N=%d m=%d)", B, N, m);
-    PCL_REQUIRE(tie_stride >= 1 && tie_stride <= 512 && (tie_stride & (tie_stride - 1)) == 0,
-                "pcl_fps_f32: tie_stride must be a power of two in [1,512], got %d", tie_stride);
-    if (B == 0) return PCL_OK;
-    int log2S = 0;
-    while ((1 << log2S) < tie_stride) ++log2S;
-    hipStream_t st = as_stream(stream);
-    // threads per cloud: ~4-8 points per lane keeps the VALU part and the cross-wave part balanced
-    // (raced on MI355X, B = 32 / 16, round 4 -- ns per dependent step at T = 64 / 128 / 256 / 512 / 1024:
-    //  N = 512: 336 / 355 / 374 / - / -;  N = 1024: 479 / 410 / 381 / 416 / 736;  N = 2048: - / 550 / 450 / 475 / 766;  N = 4096: - / - / 589 / 611 / 869.
-    //  One wave per cloud -- no barrier, no LDS exchange, DPP only -- wins up to 512 points; beyond, four waves: the cross-wave
-    //  exchange costs less than the eight more distance evaluations per lane)
-    int T = g_fps_threads > 0 ? g_fps_threads : (N <= 512 ? 64 : N <= 4096 ? 256 : N <= 8192 ? 512 : 1024);
-    const int ppt = (N + T - 1) / T;
-#define PCL_FPS_CASE(TT, PP) \
-    if (T == TT && ppt <= PP) return launch_fps<TT, PP>(xyz, B, N, m, log2S, skip_sqnorm_le, start_idx, idx_out, new_xyz_out, st);
-    if (fps_lds_bytes(N, m, log2S, N > 1024 ? 3 : 4) <= 158 * 1024) {
-        PCL_FPS_CASE(64, 1) PCL_FPS_CASE(64, 2) PCL_FPS_CASE(64, 4) PCL_FPS_CASE(64, 8) PCL_FPS_CASE(64, 16) PCL_FPS_CASE(64, 32)
-        PCL_FPS_CASE(128, 1) PCL_FPS_CASE(128, 2) PCL_FPS_CASE(128, 4) PCL_FPS_CASE(128, 8) PCL_FPS_CASE(128, 16)
-        PCL_FPS_CASE(256, 1) PCL_FPS_CASE(256, 2) PCL_FPS_CASE(256, 4) PCL_FPS_CASE(256, 8) PCL_FPS_CASE(256, 16)
-        PCL_FPS_CASE(512, 1) PCL_FPS_CASE(512, 2) PCL_FPS_CASE(512, 4) PCL_FPS_CASE(512, 8) PCL_FPS_CASE(512, 16)
-        PCL_FPS_CASE(1024, 1) PCL_FPS_CASE(1024, 2) PCL_FPS_CASE(1024, 4) PCL_FPS_CASE(1024, 8)
-        // (1024 threads x 16 points per lane does not fit the 128 registers of a 1024-thread workgroup -- it spilled 16 of them into the step
-        //  loop; clouds of 8 193 .. 10 100 points take the LDS-resident kernel below like the larger ones)
-    }
-#undef PCL_FPS_CASE
-    // large clouds: min-distance array in LDS (4 B/point), coordinates re-read from L2 each step
-    const size_t lds = sizeof(FpsSlot) * 2 * 16 + sizeof(float) * (size_t)N;
-    if (lds > 160 * 1024) return fail(PCL_ENOSUP, "pcl_fps_f32: N=%d exceeds the LDS-resident limit (%d points)", N, (160 * 1024 - 512) / 4);
-    auto kern = fps_kernel_lds<1024>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PCL_EHIP, "fps: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kern, dim3(B), dim3(1024), lds, st, xyz, N, m, log2S, skip_sqnorm_le, start_idx, idx_out, new_xyz_out);
-    return check_launch("pcl_fps_f32(lds)");
+    return fps_run<false>("pcl_fps_f32", xyz, nullptr, B, N, m, tie_stride, skip_sqnorm_le, start_idx, idx_out, new_xyz_out, stream);
+}
+
+extern "C" int pcl_fps_ragged_f32(const float* xyz, const int32_t* n_valid, int B, int N, int m, int tie_stride, double skip_sqnorm_le,
+                                  const int32_t* start_idx, int32_t* idx_out, float* new_xyz_out, void* stream) {
+    return fps_run<true>("pcl_fps_ragged_f32", xyz, n_valid, B, N, m, tie_stride, skip_sqnorm_le, start_idx, idx_out, new_xyz_out, stream);
 }

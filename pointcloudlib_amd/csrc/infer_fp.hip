@@ -14,6 +14,11 @@
 //   3. the last layer's tile goes straight from the accumulators to out[rows, ldo] (its first `ncols` columns; the last
 //      layer may be padded to a 32-multiple with zero weights).  Optionally one intermediate layer is also stored (tap).
 // Nothing but the final tile (and the tap) is written to memory; no atomics, so two calls give identical bits.
+//
+// RAGGED (pcl_fp_level_infer_ragged_f32): cloud b's target rows are its first n = clamp(n_valid[b], 1, N); every wave forms the tile's
+// 64-bit row-validity mask with one ballot.  A tile without a valid row stores its zeros and leaves before any layer work; in a mixed
+// tile the pad rows ride along (every row of the MFMA products depends on its own row of X only, so whatever a pad row of Us / fs
+// holds -- NaN included -- stays in that row) and are stored as exact zeros.  The dense instantiation is the code it was.
 #include "common.h"
 #include "infer_mfma.h"
 
@@ -39,6 +44,7 @@ struct FpArgs {
     int act_mask; float slope;
     float* out; int ldo, ncols;
     float* tap; int ldt, tap_layer;
+    const int32_t* n_valid; int tapw;             // ragged only: target rows per cloud [B]; columns of the tapped layer
 };
 
 template <int L, int C1, int C2, int C3, int C4, int C5>
@@ -49,8 +55,9 @@ struct FpShape {
 };
 
 // layer l >= 1 (0-based): z = act?(scale W_l x + shift) from X (LDS) into Y (LDS), or -- LAST -- into out
-template <int l, int K, int LDX, int CO, int LDY, bool LAST>
-__device__ __forceinline__ void fp_layer(const FpArgs& a, const float* X, float* Y, int wave, int lane, int row0, int nvalid) {
+template <int l, int K, int LDX, int CO, int LDY, bool LAST, bool RAGGED>
+__device__ __forceinline__ void fp_layer(const FpArgs& a, const float* X, float* Y, int wave, int lane, int row0, int nvalid,
+                                         unsigned long long vmask) {
     constexpr int NCB = CO / 32, NJ = (NCB + 3) / 4;
     const int lr = lane & 31, lh = lane >> 5;
     f32x16 acc[2][NJ];
@@ -70,18 +77,20 @@ __device__ __forceinline__ void fp_layer(const FpArgs& a, const float* X, float*
                     const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     float z = sc * acc[rb][j][r] + sh;
                     if (do_act) z = act(z, a.slope);
+                    float zs = z;                                          // what is stored: exact zeros on a cloud's pad rows
+                    if constexpr (RAGGED) zs = (vmask >> row) & 1 ? z : 0.f;
                     if (LAST) {
-                        if (row < nvalid && col < a.ncols) a.out[(size_t)(row0 + row) * a.ldo + col] = z;
+                        if (row < nvalid && col < a.ncols) a.out[(size_t)(row0 + row) * a.ldo + col] = zs;
                     } else {
                         Y[(size_t)row * LDY + col] = z;
-                        if (tap && row < nvalid) tap[(size_t)(row0 + row) * a.ldt + col] = z;
+                        if (tap && row < nvalid) tap[(size_t)(row0 + row) * a.ldt + col] = zs;
                     }
                 }
         }
     }
 }
 
-template <int L, int C1, int C2, int C3, int C4, int C5>
+template <int L, int C1, int C2, int C3, int C4, int C5, bool RAGGED>
 __global__ __launch_bounds__(FP_T, 2) void fp_level_infer_kernel(const FpArgs a) {
     using S = FpShape<L, C1, C2, C3, C4, C5>;
     constexpr int LDA = S::LDA, LDB = S::LDB;
@@ -91,6 +100,17 @@ __global__ __launch_bounds__(FP_T, 2) void fp_level_infer_kernel(const FpArgs a)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int row0 = blockIdx.x * FP_RT;
     const int nvalid = min(FP_RT, a.R - row0);
+    unsigned long long vmask = ~0ull;                        // bit r: tile row r is a point of its cloud (ragged)
+    if constexpr (RAGGED) {
+        const int gr = row0 + min(lane, nvalid - 1), b = gr / a.N;
+        vmask = __ballot(lane < nvalid && gr - b * a.N < min(max(a.n_valid[b], 1), a.N));      // the same in every wave
+        if (vmask == 0) {                                    // pad rows only: zeros, no layer work (uniform exit, ahead of every barrier)
+            for (int i = tid; i < nvalid * a.ncols; i += FP_T) a.out[(size_t)(row0 + i / a.ncols) * a.ldo + i % a.ncols] = 0.f;
+            if (a.tap_layer >= 0)
+                for (int i = tid; i < nvalid * a.tapw; i += FP_T) a.tap[(size_t)(row0 + i / a.tapw) * a.ldt + i % a.tapw] = 0.f;
+            return;
+        }
+    }
 
     // 1. layer 1 (the folded first conv): a thread always works on the same four channels (FP_T is a multiple of C1 / 4)
     static_assert(FP_T % (C1 / 4) == 0, "layer-1 channel split");
@@ -148,36 +168,36 @@ __global__ __launch_bounds__(FP_T, 2) void fp_level_infer_kernel(const FpArgs a)
     __syncthreads();
     // 2. layers 2..L on the MFMA; the last one to out
     if constexpr (L == 2) {
-        fp_layer<1, C1, LDA, C2, 0, true>(a, X1, nullptr, wave, lane, row0, nvalid);
+        fp_layer<1, C1, LDA, C2, 0, true, RAGGED>(a, X1, nullptr, wave, lane, row0, nvalid, vmask);
     } else {
-        fp_layer<1, C1, LDA, C2, LDB, false>(a, X1, X2, wave, lane, row0, nvalid);
+        fp_layer<1, C1, LDA, C2, LDB, false, RAGGED>(a, X1, X2, wave, lane, row0, nvalid, vmask);
         __syncthreads();
         if constexpr (L == 3) {
-            fp_layer<2, C2, LDB, C3, 0, true>(a, X2, nullptr, wave, lane, row0, nvalid);
+            fp_layer<2, C2, LDB, C3, 0, true, RAGGED>(a, X2, nullptr, wave, lane, row0, nvalid, vmask);
         } else {
             static_assert(L == 5, "FP level kernels: L = 2, 3 or 5");
-            fp_layer<2, C2, LDB, C3, LDA, false>(a, X2, X1, wave, lane, row0, nvalid);
+            fp_layer<2, C2, LDB, C3, LDA, false, RAGGED>(a, X2, X1, wave, lane, row0, nvalid, vmask);
             __syncthreads();
-            fp_layer<3, C3, LDA, C4, LDB, false>(a, X1, X2, wave, lane, row0, nvalid);
+            fp_layer<3, C3, LDA, C4, LDB, false, RAGGED>(a, X1, X2, wave, lane, row0, nvalid, vmask);
             __syncthreads();
-            fp_layer<4, C4, LDB, C5, 0, true>(a, X2, nullptr, wave, lane, row0, nvalid);
+            fp_layer<4, C4, LDB, C5, 0, true, RAGGED>(a, X2, nullptr, wave, lane, row0, nvalid, vmask);
         }
     }
 }
 
-template <int L, int C1, int C2, int C3, int C4, int C5>
-int launch_fp(const FpArgs& a, hipStream_t st) {
+template <int L, int C1, int C2, int C3, int C4, int C5, bool RAGGED>
+int launch_fp(const char* who, const FpArgs& a, hipStream_t st) {
     using S = FpShape<L, C1, C2, C3, C4, C5>;
     constexpr size_t lds = S::lds_bytes;
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
-    auto kern = fp_level_infer_kernel<L, C1, C2, C3, C4, C5>;
+    auto kern = fp_level_infer_kernel<L, C1, C2, C3, C4, C5, RAGGED>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PCL_EHIP, "pcl_fp_level_infer_f32: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(PCL_EHIP, "%s: hipFuncSetAttribute(%zu): %s", who, lds, hipGetErrorString(e));
     }
     const int blocks = (a.R + FP_RT - 1) / FP_RT;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(FP_T), lds, st, a);
-    return check_launch("pcl_fp_level_infer_f32");
+    return check_launch(who);
 }
 
 // the widths after the fold that have a kernel: the FP levels of networks/seg/pointnet2_partseg.py (SSG and MSG) and FP1 with
@@ -199,32 +219,34 @@ extern "C" int pcl_fp_level_infer_supported(int L, int C1, int C2, int C3, int C
     return L >= 1 && L <= FP_MAXL && fp_shape_id(L, w) >= 0;
 }
 
-extern "C" int pcl_fp_level_infer_f32(const float* Us, const float* skip_small, const float* Ws_small, int CS, int ldw, const float* Uc,
-                                      const int32_t* idx3, const float* w3, int S, const float* cloud_bias, int B, int N, int L,
-                                      const int32_t* widths, const float* const* W, const float* const* scale, const float* const* shift,
-                                      int act_mask, float slope, float* out, int ldo, float* tap, int tap_layer, int ldt, void* stream) {
-    PCL_REQUIRE(widths && W && scale && shift, "pcl_fp_level_infer_f32: null host array");
-    PCL_REQUIRE(L >= 1 && L <= FP_MAXL, "pcl_fp_level_infer_f32: L=%d", L);
+template <bool RAGGED>
+static int fp_run(const char* who, const float* Us, const float* skip_small, const float* Ws_small, int CS, int ldw, const float* Uc,
+                  const int32_t* idx3, const float* w3, int S, const float* cloud_bias, const int32_t* n_valid, int B, int N, int L,
+                  const int32_t* widths, const float* const* W, const float* const* scale, const float* const* shift,
+                  int act_mask, float slope, float* out, int ldo, float* tap, int tap_layer, int ldt, void* stream) {
+    PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", who);
+    PCL_REQUIRE(!RAGGED || n_valid, "%s: null pointer (n_valid)", who);
+    PCL_REQUIRE(L >= 1 && L <= FP_MAXL, "%s: L=%d", who, L);
     int w[FP_MAXL] = {0, 0, 0, 0, 0};
     for (int l = 0; l < L; ++l) w[l] = widths[l];
     const int sid = fp_shape_id(L, w);
-    PCL_REQUIRE(sid >= 0, "pcl_fp_level_infer_f32: no kernel for L=%d widths %d/%d/%d/%d/%d (pcl_fp_level_infer_supported)", L, w[0], w[1],
+    PCL_REQUIRE(sid >= 0, "%s: no kernel for L=%d widths %d/%d/%d/%d/%d (pcl_fp_level_infer_supported)", who, L, w[0], w[1],
                 w[2], w[3], w[4]);
-    PCL_REQUIRE(out, "pcl_fp_level_infer_f32: null pointer (out)");
-    PCL_REQUIRE(Us || CS > 0 || Uc || cloud_bias, "pcl_fp_level_infer_f32: layer 1 has no input (Us, skip_small, Uc or cloud_bias)");
+    PCL_REQUIRE(out, "%s: null pointer (out)", who);
+    PCL_REQUIRE(Us || CS > 0 || Uc || cloud_bias, "%s: layer 1 has no input (Us, skip_small, Uc or cloud_bias)", who);
     PCL_REQUIRE(CS >= 0 && CS <= FP_MAXCS && (CS == 0 || (skip_small && Ws_small && ldw >= CS)),
-                "pcl_fp_level_infer_f32: CS=%d inline skip channels (<= %d, with skip_small, Ws_small and ldw >= CS)", CS, FP_MAXCS);
-    PCL_REQUIRE(!Uc || (idx3 && w3 && S >= 1), "pcl_fp_level_infer_f32: Uc needs idx3, w3 and S >= 1 (null pointer)");
-    PCL_REQUIRE(B >= 1 && N >= 1, "pcl_fp_level_infer_f32: bad sizes B=%d N=%d", B, N);
-    PCL_REQUIRE((size_t)B * N < (1u << 31) && (!Uc || (size_t)B * S < (1u << 31)), "pcl_fp_level_infer_f32: too many points");
-    for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "pcl_fp_level_infer_f32: layer %d: null pointer", l);
+                "%s: CS=%d inline skip channels (<= %d, with skip_small, Ws_small and ldw >= CS)", who, CS, FP_MAXCS);
+    PCL_REQUIRE(!Uc || (idx3 && w3 && S >= 1), "%s: Uc needs idx3, w3 and S >= 1 (null pointer)", who);
+    PCL_REQUIRE(B >= 1 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
+    PCL_REQUIRE((size_t)B * N < (1u << 31) && (!Uc || (size_t)B * S < (1u << 31)), "%s: too many points", who);
+    for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", who, l);
     const int CL = w[L - 1];
-    PCL_REQUIRE(ldo >= CL, "pcl_fp_level_infer_f32: ldo=%d for %d channels", ldo, CL);
+    PCL_REQUIRE(ldo >= CL, "%s: ldo=%d for %d channels", who, ldo, CL);
     PCL_REQUIRE(!tap || (tap_layer >= 1 && tap_layer <= L - 2 && ldt >= w[tap_layer]),
-                "pcl_fp_level_infer_f32: tap_layer=%d (an intermediate MFMA layer, 1..L-2) ldt=%d", tap_layer, ldt);
+                "%s: tap_layer=%d (an intermediate MFMA layer, 1..L-2) ldt=%d", who, tap_layer, ldt);
     bool al16 = ((reinterpret_cast<uintptr_t>(Us) | reinterpret_cast<uintptr_t>(Uc) | reinterpret_cast<uintptr_t>(cloud_bias)) & 15) == 0;
     for (int l = 1; l < L; ++l) al16 = al16 && (reinterpret_cast<uintptr_t>(W[l]) & 15) == 0;
-    PCL_REQUIRE(al16, "pcl_fp_level_infer_f32: Us, Uc, cloud_bias and the weights must be 16-byte aligned");
+    PCL_REQUIRE(al16, "%s: Us, Uc, cloud_bias and the weights must be 16-byte aligned", who);
     FpArgs a = {};
     a.Us = Us; a.fs = skip_small; a.Wfs = Ws_small; a.CS = CS; a.ldw = ldw;
     a.Uc = Uc; a.idx3 = idx3; a.w3 = w3; a.S = S; a.cb = cloud_bias;
@@ -233,12 +255,30 @@ extern "C" int pcl_fp_level_infer_f32(const float* Us, const float* skip_small, 
     a.act_mask = act_mask; a.slope = slope;
     a.out = out; a.ldo = ldo; a.ncols = CL;
     a.tap = tap; a.ldt = ldt; a.tap_layer = tap ? tap_layer : -1;
+    a.n_valid = n_valid; a.tapw = tap ? w[tap_layer] : 0;
     hipStream_t st = as_stream(stream);
     switch (sid) {
-        case 0: return launch_fp<2, 256, 256, 0, 0, 0>(a, st);
-        case 1: return launch_fp<2, 256, 128, 0, 0, 0>(a, st);
-        case 2: return launch_fp<3, 128, 128, 128, 0, 0>(a, st);
-        case 3: return launch_fp<5, 128, 128, 128, 128, 32>(a, st);
-        default: return launch_fp<5, 128, 128, 128, 128, 64>(a, st);
+        case 0: return launch_fp<2, 256, 256, 0, 0, 0, RAGGED>(who, a, st);
+        case 1: return launch_fp<2, 256, 128, 0, 0, 0, RAGGED>(who, a, st);
+        case 2: return launch_fp<3, 128, 128, 128, 0, 0, RAGGED>(who, a, st);
+        case 3: return launch_fp<5, 128, 128, 128, 128, 32, RAGGED>(who, a, st);
+        default: return launch_fp<5, 128, 128, 128, 128, 64, RAGGED>(who, a, st);
     }
+}
+
+extern "C" int pcl_fp_level_infer_f32(const float* Us, const float* skip_small, const float* Ws_small, int CS, int ldw, const float* Uc,
+                                      const int32_t* idx3, const float* w3, int S, const float* cloud_bias, int B, int N, int L,
+                                      const int32_t* widths, const float* const* W, const float* const* scale, const float* const* shift,
+                                      int act_mask, float slope, float* out, int ldo, float* tap, int tap_layer, int ldt, void* stream) {
+    return fp_run<false>("pcl_fp_level_infer_f32", Us, skip_small, Ws_small, CS, ldw, Uc, idx3, w3, S, cloud_bias, nullptr, B, N, L, widths, W,
+                         scale, shift, act_mask, slope, out, ldo, tap, tap_layer, ldt, stream);
+}
+
+extern "C" int pcl_fp_level_infer_ragged_f32(const float* Us, const float* skip_small, const float* Ws_small, int CS, int ldw, const float* Uc,
+                                             const int32_t* idx3, const float* w3, int S, const float* cloud_bias, const int32_t* n_valid,
+                                             int B, int N, int L, const int32_t* widths, const float* const* W, const float* const* scale,
+                                             const float* const* shift, int act_mask, float slope, float* out, int ldo, float* tap,
+                                             int tap_layer, int ldt, void* stream) {
+    return fp_run<true>("pcl_fp_level_infer_ragged_f32", Us, skip_small, Ws_small, CS, ldw, Uc, idx3, w3, S, cloud_bias, n_valid, B, N, L,
+                        widths, W, scale, shift, act_mask, slope, out, ldo, tap, tap_layer, ldt, stream);
 }

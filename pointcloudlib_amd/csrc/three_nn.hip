@@ -23,15 +23,31 @@ __device__ __forceinline__ void tn_insert(float d, int s, float& d0, int& i0, fl
 // part-seg step (16.8 M distances).  Eight lanes per target each scan every eighth source in ascending order (strict <: among equal distances
 // the lower index stays ahead, as in the single scan), branch-free inserts, then three xor-shuffle rounds merge the eight triples by
 // (distance, index) -- the same top-3 in the same order as the sequential scan, whatever the split.
-__global__ __launch_bounds__(TN_T) void three_nn_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2,
-                                                        int N, int S, int chunk, int32_t* __restrict__ idx3,
+//
+// RAGGED (pcl_three_nn_ragged_f32): n1_valid / n2_valid (either may be null: that side dense) give the clouds' own target / source
+// counts, clamped to [1, N] / [1, S].  Only the first S_b sources are staged and scanned and the S == 1 / S == 2 rules apply to S_b,
+// so a valid target's triple is that of the clouds alone; target rows from N_b on get idx 0, w 0.  A workgroup wholly beyond N_b
+// stores its zeros and leaves before the scan (uniform exit: ahead of every barrier).
+template <bool RAGGED>
+__global__ __launch_bounds__(TN_T) void three_nn_kernel(const float* __restrict__ xyz1, const int32_t* __restrict__ n1_valid,
+                                                        const float* __restrict__ xyz2, const int32_t* __restrict__ n2_valid,
+                                                        int N, int S_cap, int chunk, int32_t* __restrict__ idx3,
                                                         float* __restrict__ w3) {
     extern __shared__ __attribute__((aligned(16))) float s_src[];   // x[chunk] y[chunk] z[chunk]
     const int b = blockIdx.y, tid = threadIdx.x, sub = tid % TN_S;
     const int n = blockIdx.x * (TN_T / TN_S) + tid / TN_S;
-    const float* P2 = xyz2 + (size_t)b * S * 3;
+    const float* P2 = xyz2 + (size_t)b * S_cap * 3;
+    int S = S_cap, N1 = N;
+    if constexpr (RAGGED) {
+        if (n2_valid) S = min(max(__builtin_amdgcn_readfirstlane(n2_valid[b]), 1), S_cap);
+        if (n1_valid) N1 = min(max(__builtin_amdgcn_readfirstlane(n1_valid[b]), 1), N);
+        if ((int)(blockIdx.x * (TN_T / TN_S)) >= N1) {                 // every target row of this workgroup is a pad row
+            if (n < N && sub < 3) { idx3[((size_t)b * N + n) * 3 + sub] = 0; w3[((size_t)b * N + n) * 3 + sub] = 0.f; }
+            return;
+        }
+    }
     float px = 0.f, py = 0.f, pz = 0.f;
-    if (n < N) { const float* p = xyz1 + ((size_t)b * N + n) * 3; px = p[0]; py = p[1]; pz = p[2]; }
+    if (n < N1) { const float* p = xyz1 + ((size_t)b * N + n) * 3; px = p[0]; py = p[1]; pz = p[2]; }
     float d0 = INFINITY, d1 = INFINITY, d2 = INFINITY;
     int i0 = 0x7fffffff, i1 = 0x7fffffff, i2 = 0x7fffffff;          // (empty slots lose every (distance, index) comparison)
     for (int s0 = 0; s0 < S; s0 += chunk) {
@@ -63,6 +79,7 @@ __global__ __launch_bounds__(TN_T) void three_nn_kernel(const float* __restrict_
     if (n >= N || sub != 0) return;
     int32_t* oi = idx3 + ((size_t)b * N + n) * 3;
     float* ow = w3 + ((size_t)b * N + n) * 3;
+    if (RAGGED && n >= N1) { oi[0] = oi[1] = oi[2] = 0; ow[0] = ow[1] = ow[2] = 0.f; return; }
     if (S == 1) { oi[0] = oi[1] = oi[2] = 0; ow[0] = 1.f; ow[1] = 0.f; ow[2] = 0.f; return; }
     if (S == 2) { d2 = d1; i2 = i1; }
     const float r0 = __fdiv_rn(1.0f, __fadd_rn(d0, 1e-8f));
@@ -115,15 +132,26 @@ static inline int grid_for(size_t total) {
 }  // namespace pcl
 using namespace pcl;
 
-extern "C" int pcl_three_nn_f32(const float* xyz1, const float* xyz2, int B, int N, int S, int32_t* idx3, float* w3,
-                                void* stream) {
-    PCL_REQUIRE(xyz1 && xyz2 && idx3 && w3, "pcl_three_nn_f32: null pointer");
-    PCL_REQUIRE(B >= 0 && N >= 0 && S >= 1 && B <= 65535, "pcl_three_nn_f32: bad sizes B=%d N=%d S=%d", B, N, S);
+template <bool RAGGED>
+static int three_nn_run(const char* who, const float* xyz1, const int32_t* n1_valid, const float* xyz2, const int32_t* n2_valid, int B, int N,
+                        int S, int32_t* idx3, float* w3, void* stream) {
+    PCL_REQUIRE(xyz1 && xyz2 && idx3 && w3, "%s: null pointer", who);
+    PCL_REQUIRE(B >= 0 && N >= 0 && S >= 1 && B <= 65535, "%s: bad sizes B=%d N=%d S=%d", who, B, N, S);
     if (B == 0 || N == 0) return PCL_OK;
     const int chunk = S < 4096 ? S : 4096;
-    hipLaunchKernelGGL(three_nn_kernel, dim3((N + TN_T / TN_S - 1) / (TN_T / TN_S), B), dim3(TN_T), sizeof(float) * 3 * chunk,
-                       as_stream(stream), xyz1, xyz2, N, S, chunk, idx3, w3);
-    return check_launch("pcl_three_nn_f32");
+    hipLaunchKernelGGL(three_nn_kernel<RAGGED>, dim3((N + TN_T / TN_S - 1) / (TN_T / TN_S), B), dim3(TN_T), sizeof(float) * 3 * chunk,
+                       as_stream(stream), xyz1, n1_valid, xyz2, n2_valid, N, S, chunk, idx3, w3);
+    return check_launch(who);
+}
+
+extern "C" int pcl_three_nn_f32(const float* xyz1, const float* xyz2, int B, int N, int S, int32_t* idx3, float* w3,
+                                void* stream) {
+    return three_nn_run<false>("pcl_three_nn_f32", xyz1, nullptr, xyz2, nullptr, B, N, S, idx3, w3, stream);
+}
+
+extern "C" int pcl_three_nn_ragged_f32(const float* xyz1, const int32_t* n1_valid, const float* xyz2, const int32_t* n2_valid, int B, int N,
+                                       int S, int32_t* idx3, float* w3, void* stream) {
+    return three_nn_run<true>("pcl_three_nn_ragged_f32", xyz1, n1_valid, xyz2, n2_valid, B, N, S, idx3, w3, stream);
 }
 
 extern "C" int pcl_three_interp_f32(const float* points2, const int32_t* idx3, const float* w3, int B, int N, int S,

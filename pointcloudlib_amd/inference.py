@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .misc.head import MAX_ROWS, fc_head
-from .misc.ops import _p, _stream, group_all, group_points, three_nn
+from .misc.ops import _p, _stream, group_all, group_points, three_interpolate, three_nn
 from .networks.cls.pointnet2 import PointNet2_cls
 from .networks.seg.pointnet2_partseg import PointNet2_partseg
 
@@ -30,9 +30,11 @@ __all__ = ["frozen", "FrozenPointNet2", "FrozenPointNet2Partseg"]
 
 
 def frozen(net):
-    """A frozen evaluator of ``net``: ``PointNet2_cls`` or ``PointNetMSG`` (classification) -> ``fnet(xyz, feature, sampling=None)
-    -> [B, n_classes]``; ``PointNet2_partseg`` or its ``PointNetMSG`` (part segmentation) -> ``fnet(xyz, feature, cls_label,
-    sampling=None) -> [B, part_num, N]``."""
+    """A frozen evaluator of ``net``: ``PointNet2_cls`` or ``PointNetMSG`` (classification) -> ``fnet(xyz, feature, sampling=None,
+    lengths=None) -> [B, n_classes]``; ``PointNet2_partseg`` or its ``PointNetMSG`` (part segmentation) -> ``fnet(xyz, feature,
+    cls_label, sampling=None, lengths=None) -> [B, part_num, N]``.  ``lengths`` [B]: per-cloud point counts of a ragged batch
+    (capacity N; rows from lengths[b] on are pad rows, any contents): every cloud's result is that of the cloud alone; the
+    part-seg logits and ``fp1`` feature of pad points are exact zeros."""
     if isinstance(net, PointNet2_cls):
         return FrozenPointNet2(net)
     if isinstance(net, PointNet2_partseg):
@@ -164,13 +166,14 @@ class _FrozenEncoder:
             self.levels.append(plans)
             C = sum(mlp.spec[-1] for mlp in module.mlps)
 
-    def _encode(self, xyz, feature, sampling):
-        """-> [(xyz, feature) after every set-abstraction level] (xyz None after the GroupAll level)."""
+    def _encode(self, xyz, feature, sampling, lengths=None):
+        """-> [(xyz, feature) after every set-abstraction level] (xyz None after the GroupAll level).  ``lengths``: only the first
+        level's sampling reads them; the level kernels reach the cloud through idx, which never names a pad row."""
         net = self.net
         net.adopt_sampling(sampling)
         out = []
         for i, (module, plans) in enumerate(zip(net.pointnet_modules, self.levels)):
-            s = sampling["levels"][i] if sampling is not None else module.sample(xyz)
+            s = sampling["levels"][i] if sampling is not None else (module.sample(xyz, lengths) if i == 0 else module.sample(xyz))
             xyz, feature = self._level(module, plans, xyz, feature, s)
             out.append((xyz, feature))
         return out
@@ -212,13 +215,14 @@ class FrozenPointNet2(_FrozenEncoder):
         self.head = self._copy("head", self.net.fc_layer)
         return self
 
-    def __call__(self, xyz, feature, sampling=None):
-        return self.run(xyz, feature, sampling)[1]
+    def __call__(self, xyz, feature, sampling=None, lengths=None):
+        return self.run(xyz, feature, sampling, lengths)[1]
 
     @torch.no_grad()
-    def run(self, xyz, feature, sampling=None):
-        """-> ([feature of every set-abstraction level], logits [B, n_classes])."""
-        feats = [f for _, f in self._encode(xyz, feature, sampling)]
+    def run(self, xyz, feature, sampling=None, lengths=None):
+        """-> ([feature of every set-abstraction level], logits [B, n_classes]).  ``lengths``: see ``frozen``."""
+        lengths = self.net.resolve_lengths(xyz, sampling, lengths, self.net.pointnet_modules[0].n_points)
+        feats = [f for _, f in self._encode(xyz, feature, sampling, lengths)]
         feature = feats[-1].squeeze(dim=1)
         logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, feature.shape[0], MAX_ROWS)]
         return feats, logits[0] if len(logits) == 1 else torch.cat(logits)
@@ -281,9 +285,10 @@ class _FusedFP:
                   tag=f"pt{Cin}x{Cout}")
         return Y
 
-    def run(self, xyz1, xyz2, skip, coarse, onehot=None):
+    def run(self, xyz1, xyz2, skip, coarse, onehot=None, lengths=None):
         """xyz1 [B,N,3], xyz2 [B,S,3], skip [B,N,D1 - n_onehot] (or None), coarse [B,S,D2], onehot [B, n_onehot]
-        -> (out [B, N, widths[-1]], tap [B, N, widths[tap_layer]] or None)."""
+        -> (out [B, N, widths[-1]], tap [B, N, widths[tap_layer]] or None).  ``lengths`` (device int32 [B]): the targets'
+        per-cloud counts; rows beyond them come out as exact zeros."""
         B, N, _ = xyz1.shape
         S = coarse.shape[1]
         dev = xyz1.device
@@ -292,7 +297,7 @@ class _FusedFP:
         if S == 1:                                                   # a one-row coarse level: a per-cloud bias
             cb, Uc = Uc, None
         else:
-            idx3, w3 = three_nn(xyz1, xyz2)
+            idx3, w3 = three_nn(xyz1, xyz2, lengths1=lengths)
             cb = None
         if self.Woh is not None:
             c = self._rows(onehot.reshape(B, self.n_onehot).float().contiguous(), self.Woh, B)
@@ -304,10 +309,14 @@ class _FusedFP:
                 Us, fs = self._rows(fs, self.Wsk, B * N), None
         out = torch.empty((B, N, self.widths[-1]), dtype=torch.float32, device=dev)
         tap = None if self.tap_layer is None else torch.empty((B, N, self.widths[self.tap_layer]), dtype=torch.float32, device=dev)
-        _lib.call("pcl_fp_level_infer_f32", _p(Us), _p(fs), _p(self.Wsk) if fs is not None else None, self.CS if fs is not None else 0,
-                  self.W0.shape[1], _p(Uc), _p(idx3), _p(w3), S, _p(cb), B, N, len(self.widths), self.c_widths, self.c_W, self.c_scale,
-                  self.c_shift, self.act_mask, self.slope, _p(out), out.shape[-1], _p(tap), -1 if tap is None else self.tap_layer,
-                  0 if tap is None else tap.shape[-1], _stream())
+        head = (_p(Us), _p(fs), _p(self.Wsk) if fs is not None else None, self.CS if fs is not None else 0, self.W0.shape[1], _p(Uc),
+                _p(idx3), _p(w3), S, _p(cb))
+        tail = (B, N, len(self.widths), self.c_widths, self.c_W, self.c_scale, self.c_shift, self.act_mask, self.slope, _p(out),
+                out.shape[-1], _p(tap), -1 if tap is None else self.tap_layer, 0 if tap is None else tap.shape[-1], _stream())
+        if lengths is None:
+            _lib.call("pcl_fp_level_infer_f32", *head, *tail)
+        else:
+            _lib.call("pcl_fp_level_infer_ragged_f32", *head, _p(lengths), *tail)
         return out, tap
 
 
@@ -350,33 +359,53 @@ class FrozenPointNet2Partseg(_FrozenEncoder):
         self.head = None if self.head_fused else (self._copy("head1", net.head1), self._copy("head2", net.head2))
         return self
 
-    def __call__(self, xyz, feature, cls_label, sampling=None):
-        return self.run(xyz, feature, cls_label, sampling)[1]
+    def __call__(self, xyz, feature, cls_label, sampling=None, lengths=None):
+        return self.run(xyz, feature, cls_label, sampling, lengths)[1]
 
-    def _fp(self, name, xyz1, xyz2, skip, coarse, onehot=None):
+    @staticmethod
+    def _zero_pads(t, lengths):
+        """Exact zeros on the pad rows of t [B, N, C] (where, not a product: a pad row may hold NaN)."""
+        valid = torch.arange(t.shape[1], device=t.device).view(1, -1) < lengths.view(-1, 1)
+        return torch.where(valid.unsqueeze(-1), t, torch.zeros((), dtype=t.dtype, device=t.device))
+
+    def _fp(self, name, xyz1, xyz2, skip, coarse, onehot=None, lengths=None):
         kind, plan = self.fp[name]
         if kind == "fused":
-            return plan.run(xyz1, xyz2, skip, coarse, onehot)
+            return plan.run(xyz1, xyz2, skip, coarse, onehot, lengths)
         if onehot is not None:
             B, N, _ = xyz1.shape
             skip = torch.cat([onehot.view(B, 1, -1).expand(B, N, onehot.shape[-1]), skip], 2)
-        return plan(xyz1, xyz2, skip, coarse), None
+        if lengths is None:
+            return plan(xyz1, xyz2, skip, coarse), None
+        # the level's own module on a ragged batch: ragged 3-NN, then the eval-mode MLP (row-wise), then zeros on the pad rows
+        B, N, _ = xyz1.shape
+        if xyz2.shape[1] == 1:
+            interp = coarse.expand(B, N, coarse.shape[2])
+        else:
+            idx3, w3 = three_nn(xyz1, xyz2, lengths1=lengths)
+            interp = three_interpolate(coarse, idx3, w3)
+        x = torch.cat([self._zero_pads(skip, lengths), interp], dim=-1) if skip is not None else interp
+        return self._zero_pads(plan.mlp(x.contiguous()), lengths), None
 
     @torch.no_grad()
-    def run(self, xyz, feature, cls_label, sampling=None):
-        """-> ([sa1, sa2, sa3, fp3, fp2, fp1] level features, logits [B, part_num, N] (the network's layout and view))."""
+    def run(self, xyz, feature, cls_label, sampling=None, lengths=None):
+        """-> ([sa1, sa2, sa3, fp3, fp2, fp1] level features, logits [B, part_num, N] (the network's layout and view)).
+        ``lengths``: see ``frozen``; only FP1 (3-NN back onto the raw cloud, one row per raw point) sees them after level 1."""
         B, N, _ = xyz.shape
         xyz = xyz.contiguous()
-        (l1_xyz, l1), (l2_xyz, l2), (_, l3) = self._encode(xyz, feature, sampling)
+        lengths = self.net.resolve_lengths(xyz, sampling, lengths, self.net.pointnet_modules[0].n_points)
+        (l1_xyz, l1), (l2_xyz, l2), (_, l3) = self._encode(xyz, feature, sampling, lengths)
         l3_xyz = torch.zeros((B, 1, 3), device=xyz.device, dtype=xyz.dtype)
         f3, _ = self._fp("fp3", l2_xyz, l3_xyz, l2, l3)
         f2, _ = self._fp("fp2", l1_xyz, l2_xyz, l1, f3)
         onehot = cls_label.reshape(B, self.N_ONEHOT).float()
-        out, tap = self._fp("fp1", xyz, l1_xyz, torch.cat([xyz, feature.float()], 2), f2, onehot)
+        out, tap = self._fp("fp1", xyz, l1_xyz, torch.cat([xyz, feature.float()], 2), f2, onehot, lengths)
         if self.head_fused:
             f1, logits = tap, out
         else:
             f1 = out
             h1, h2 = self.head
             logits = h2(h1(f1))
+            if lengths is not None:                          # the head's bias / shift on FP1's zero pad rows
+                logits = self._zero_pads(logits, lengths)
         return [l1, l2, l3, f3, f2, f1], logits.permute(0, 2, 1)

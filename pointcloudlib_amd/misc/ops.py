@@ -44,18 +44,60 @@ def _stream():
     return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device())
 
 
+def _lengths(lengths, B, N, device, name="lengths", n_samples=None):
+    """Per-cloud point counts of a ragged batch -> device int32 [B] (``None`` stays ``None``: the dense path).
+
+    A batch is [B, N, .] with N the capacity; cloud b is its first ``lengths[b]`` rows, the rest are pad rows that influence no
+    result.  A Python sequence or a CPU tensor is validated here (shape [B], ``1 <= lengths[b] <= N`` and, for FPS,
+    ``n_samples <= lengths[b]``) and copied once.  A device tensor must be int32 [B] and is NOT read back (no host
+    synchronisation): the same bounds are the caller's precondition, and the kernels clamp every count to [1, N]."""
+    if lengths is None:
+        return None
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int32:
+            raise TypeError(f"{name}: a device tensor must be torch.int32, got {lengths.dtype}")
+        if lengths.dim() != 1 or lengths.shape[0] != B:
+            raise ValueError(f"{name}: expected shape [{B}], got {tuple(lengths.shape)}")
+        if lengths.device != device:
+            raise ValueError(f"{name}: on {lengths.device}, the clouds on {device}")
+        return lengths.contiguous()
+    host = lengths.detach() if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths)
+    if host.dtype.is_floating_point or host.dtype == torch.bool or host.dtype.is_complex:
+        raise TypeError(f"{name}: expected integers, got {host.dtype}")
+    if host.dim() != 1 or host.shape[0] != B:
+        raise ValueError(f"{name}: expected shape [{B}] (one count per cloud), got {tuple(host.shape)}")
+    vals = host.tolist()
+    for b, v in enumerate(vals):
+        if not 1 <= v <= N:
+            raise ValueError(f"{name}[{b}]={v} must be in [1, N={N}]")
+        if n_samples is not None and v < n_samples:
+            raise ValueError(f"{name}[{b}]={v} is less than n_samples={n_samples}: a cloud cannot be sampled beyond its own points")
+    return torch.tensor(vals, dtype=torch.int32).to(device)
+
+
+def _xyz_shape(xyz, name="xyz"):
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError(f"{name} must be [B,N,3], got {tuple(getattr(xyz, 'shape', ()))}")
+    return xyz.shape[0], xyz.shape[1]
+
+
 def optimal_block(batch_size):
     """misc/ops.py:110-111 -- ``2 ** int(math.log(batch_size))`` (natural log, as written)."""
     return 2 ** int(math.log(batch_size)) if batch_size >= 1 else 1
 
 
 # ----------------------------------------------------------------------------- index producers
-def furthest_point_sample(xyz, n_samples, tie_stride=None, skip_sqnorm_le=1e-3, start_idx=None):
+def furthest_point_sample(xyz, n_samples, tie_stride=None, skip_sqnorm_le=1e-3, start_idx=None, lengths=None):
     """xyz [B,N,3] f32 -> (idx [B,n] int32, new_xyz [B,n,3]).  misc/ops.py:124-234, :280-284.
 
     ``tie_stride`` defaults to the reference's launch block size ``optimal_block(B)``, which fixes how
     exact distance ties are broken; ``skip_sqnorm_le=None`` disables the near-origin skip
-    (misc/pointconv_utils.py:74-116 has none)."""
+    (misc/pointconv_utils.py:74-116 has none).  ``lengths`` (see ``_lengths``): per-cloud point counts of a ragged batch --
+    every cloud is sampled from its own first ``lengths[b]`` points, with the picks of that cloud alone for the same
+    ``tie_stride`` (the default stride is a function of B: pass it explicitly to compare with a B = 1 call)."""
+    if lengths is not None:          # host-side length errors come first, before anything touches the device
+        Bh, Nh = _xyz_shape(xyz)
+        lengths = _lengths(lengths, Bh, Nh, xyz.device, n_samples=n_samples)
     xyz = _dev(xyz, "xyz")
     if xyz.dim() != 3 or xyz.shape[2] != 3:
         raise ValueError(f"xyz must be [B,N,3], got {tuple(xyz.shape)}")
@@ -68,13 +110,21 @@ def furthest_point_sample(xyz, n_samples, tie_stride=None, skip_sqnorm_le=1e-3, 
     idx = torch.empty((B, n_samples), dtype=torch.int32, device=xyz.device)
     new_xyz = torch.empty((B, n_samples, 3), dtype=torch.float32, device=xyz.device)
     thr = -1.0 if skip_sqnorm_le is None else float(skip_sqnorm_le)
+    if lengths is not None:
+        _lib.call("pcl_fps_ragged_f32", _p(xyz), _p(_dev(lengths, "lengths", torch.int32)), B, N, n_samples, int(tie_stride), thr,
+                  _p(start_idx), _p(idx), _p(new_xyz), _stream(), algo_bytes=B * (12 * N + 16 * n_samples))
+        return idx, new_xyz
     _lib.call("pcl_fps_f32", _p(xyz), B, N, n_samples, int(tie_stride), thr, _p(start_idx), _p(idx),
                                       _p(new_xyz), _stream(), algo_bytes=B * (12 * N + 16 * n_samples))
     return idx, new_xyz
 
 
-def ball_query(new_xyz, xyz, radius, n_samples, return_cnt=False):
-    """new_xyz [B,m,3], xyz [B,N,3] -> idx [B,m,ns] int32.  misc/ops.py:291-330."""
+def ball_query(new_xyz, xyz, radius, n_samples, return_cnt=False, lengths=None):
+    """new_xyz [B,m,3], xyz [B,N,3] -> idx [B,m,ns] int32.  misc/ops.py:291-330.  ``lengths``: per-cloud point counts of
+    ``xyz`` (ragged batch, see ``_lengths``): the lists of every cloud alone, no index >= lengths[b]."""
+    if lengths is not None:
+        Bh, Nh = _xyz_shape(xyz)
+        lengths = _lengths(lengths, Bh, Nh, xyz.device)
     new_xyz = _dev(new_xyz, "new_xyz")
     xyz = _dev(xyz, "xyz")
     if new_xyz.dim() != 3 or new_xyz.shape[2] != 3 or xyz.dim() != 3 or xyz.shape[2] != 3:
@@ -85,6 +135,10 @@ def ball_query(new_xyz, xyz, radius, n_samples, return_cnt=False):
     N = xyz.shape[1]
     idx = torch.empty((B, m, n_samples), dtype=torch.int32, device=xyz.device)
     cnt = torch.empty((B, m), dtype=torch.int32, device=xyz.device) if return_cnt else None
+    if lengths is not None:
+        _lib.call("pcl_ball_query_ragged_f32", _p(new_xyz), _p(xyz), _p(_dev(lengths, "lengths", torch.int32)), B, m, N, float(radius),
+                  int(n_samples), _p(idx), _p(cnt), _stream(), algo_bytes=B * (12 * (N + m) + 4 * m * n_samples))
+        return (idx, cnt) if return_cnt else idx
     _lib.call("pcl_ball_query_f32", _p(new_xyz), _p(xyz), B, m, N, float(radius), int(n_samples), _p(idx),
                                              _p(cnt), _stream(), algo_bytes=B * (12 * (N + m) + 4 * m * n_samples))
     return (idx, cnt) if return_cnt else idx
@@ -93,11 +147,14 @@ def ball_query(new_xyz, xyz, radius, n_samples, return_cnt=False):
 BALL_QUERY_MULTI_MAX = 4          # radii per pcl_ball_query_multi_f32 call
 
 
-def ball_query_multi(new_xyz, xyz, radii, n_samples, return_cnt=False):
+def ball_query_multi(new_xyz, xyz, radii, n_samples, return_cnt=False, lengths=None):
     """Ball queries of several radii around the same centres in ONE scan of the cloud (multi-scale grouping: one BallQueryGrouper per
     scale on the same new_xyz, reference networks/seg/pointnet2_partseg.py:93-103).  -> [idx [B,m,ns_r]] or [(idx, cnt)] per radius,
-    each identical to ``ball_query(new_xyz, xyz, radii[r], n_samples[r])``."""
+    each identical to ``ball_query(new_xyz, xyz, radii[r], n_samples[r])`` (``lengths`` as there)."""
     import ctypes
+    if lengths is not None:
+        Bh, Nh = _xyz_shape(xyz)
+        lengths = _lengths(lengths, Bh, Nh, xyz.device)
     new_xyz = _dev(new_xyz, "new_xyz")
     xyz = _dev(xyz, "xyz")
     if new_xyz.dim() != 3 or new_xyz.shape[2] != 3 or xyz.dim() != 3 or xyz.shape[2] != 3:
@@ -115,8 +172,12 @@ def ball_query_multi(new_xyz, xyz, radii, n_samples, return_cnt=False):
     c_s = (ctypes.c_int32 * n)(*[int(s) for s in n_samples])
     c_i = (ctypes.c_void_p * n)(*[t.data_ptr() for t in idx])
     c_c = (ctypes.c_void_p * n)(*[t.data_ptr() for t in cnt]) if return_cnt else None
-    _lib.call("pcl_ball_query_multi_f32", _p(new_xyz), _p(xyz), B, m, N, n, c_r, c_s, c_i, c_c, _stream(),
-              algo_bytes=B * (12 * (N + m) + 4 * m * sum(int(s) for s in n_samples)))
+    if lengths is not None:
+        _lib.call("pcl_ball_query_multi_ragged_f32", _p(new_xyz), _p(xyz), _p(_dev(lengths, "lengths", torch.int32)), B, m, N, n, c_r, c_s,
+                  c_i, c_c, _stream(), algo_bytes=B * (12 * (N + m) + 4 * m * sum(int(s) for s in n_samples)))
+    else:
+        _lib.call("pcl_ball_query_multi_f32", _p(new_xyz), _p(xyz), B, m, N, n, c_r, c_s, c_i, c_c, _stream(),
+                  algo_bytes=B * (12 * (N + m) + 4 * m * sum(int(s) for s in n_samples)))
     return list(zip(idx, cnt)) if return_cnt else idx
 
 
@@ -163,14 +224,26 @@ def knn_lists(x_q, x_r, k):
     return knn_indices(x_q, x_r, k).permute(0, 2, 1).contiguous()
 
 
-def three_nn(xyz1, xyz2):
-    """xyz1 [B,N,3] targets, xyz2 [B,S,3] sources -> (idx [B,N,3] int32, weight [B,N,3])."""
+def three_nn(xyz1, xyz2, lengths1=None, lengths2=None):
+    """xyz1 [B,N,3] targets, xyz2 [B,S,3] sources -> (idx [B,N,3] int32, weight [B,N,3]).  ``lengths1`` / ``lengths2``: per-cloud
+    counts of the targets / sources (ragged batch, see ``_lengths``; either may be None): valid targets get the triple of the
+    clouds alone (no source index >= lengths2[b]), target rows beyond lengths1[b] get idx 0, weight 0."""
+    if lengths1 is not None:
+        Bh, Nh = _xyz_shape(xyz1, "xyz1")
+        lengths1 = _lengths(lengths1, Bh, Nh, xyz1.device, "lengths1")
+    if lengths2 is not None:
+        Bh, Sh = _xyz_shape(xyz2, "xyz2")
+        lengths2 = _lengths(lengths2, Bh, Sh, xyz2.device, "lengths2")
     xyz1 = _dev(xyz1, "xyz1")
     xyz2 = _dev(xyz2, "xyz2")
     B, N, _ = xyz1.shape
     S = xyz2.shape[1]
     idx = torch.empty((B, N, 3), dtype=torch.int32, device=xyz1.device)
     w = torch.empty((B, N, 3), dtype=torch.float32, device=xyz1.device)
+    if lengths1 is not None or lengths2 is not None:
+        _lib.call("pcl_three_nn_ragged_f32", _p(xyz1), _p(_dev(lengths1, "lengths1", torch.int32)), _p(xyz2),
+                  _p(_dev(lengths2, "lengths2", torch.int32)), B, N, S, _p(idx), _p(w), _stream())
+        return idx, w
     _lib.call("pcl_three_nn_f32", _p(xyz1), _p(xyz2), B, N, S, _p(idx), _p(w), _stream())
     return idx, w
 
@@ -442,8 +515,8 @@ class FurthestPointSampler(_Module):
         self.n_samples = n_samples
         self.tie_stride = tie_stride
 
-    def forward(self, x, return_idx=False):
-        idx, y = furthest_point_sample(x, self.n_samples, self.tie_stride)
+    def forward(self, x, return_idx=False, lengths=None):
+        idx, y = furthest_point_sample(x, self.n_samples, self.tie_stride, lengths=lengths)
         return (y, idx) if return_idx else y
 
 
@@ -456,8 +529,8 @@ class BallQueryGrouper(_Module):
         self.n_samples = n_samples
         self.use_xyz = use_xyz
 
-    def forward(self, new_xyz, pointset, feature, return_idx=False):
-        idx = ball_query(new_xyz, pointset, self.radius, self.n_samples)
+    def forward(self, new_xyz, pointset, feature, return_idx=False, lengths=None):
+        idx = ball_query(new_xyz, pointset, self.radius, self.n_samples, lengths=lengths)
         if self.use_xyz or feature is not None:
             out = group_points(pointset, new_xyz, feature, idx, self.use_xyz)
         else:

@@ -17,7 +17,7 @@ from torch import nn
 from ...misc.head import fc_head
 from ...misc.layers import PointwiseMLP
 from ...misc.ops import (BALL_QUERY_MULTI_MAX, BallQueryGrouper, FurthestPointSampler, GroupAll, ball_query, ball_query_multi, group_offsets,
-                         group_offsets_multi, group_points)
+                         group_offsets_multi, group_points, _lengths)
 
 
 _MULTI_BALL_QUERY = os.environ.get("PCL_MULTI_BALL_QUERY", "1") != "0"        # lab switch for A/B timing on one box
@@ -38,19 +38,25 @@ class PointNetModuleBase(nn.Module):
             spec[0] += 3
         return PointwiseMLP(spec, bias=not bn, bn=bn, slope=0.0)
 
-    def sample(self, xyz: torch.Tensor):
+    def sample(self, xyz: torch.Tensor, lengths=None):
         """The index-producing half of ``forward`` (no gradients, depends on xyz only): FPS centres and the
-        ball-query neighbour lists of every grouper.  Returns (new_xyz, [idx per grouper])."""
+        ball-query neighbour lists of every grouper.  Returns (new_xyz, [idx per grouper]).  ``lengths``: per-cloud point
+        counts of a ragged batch (misc/ops.py ``_lengths``): centres and lists of every cloud alone; the result is dense.
+        Host-side lengths are validated and copied to the device ONCE, here; the operators below get the device tensor."""
         if self.n_points is None:
+            if lengths is not None:
+                raise NotImplementedError("GroupAll directly on a ragged cloud needs a masked max (out of scope, DESIGN.md section 14)")
             return None, [None] * len(self.groupers)
-        new_xyz = self.sampler(xyz)                                             # :45
+        if lengths is not None:
+            lengths = _lengths(lengths, xyz.shape[0], xyz.shape[1], xyz.device, n_samples=self.n_points)
+        new_xyz = self.sampler(xyz, lengths=lengths)                            # :45
         out = []
         gs = list(self.groupers)
         if 1 < len(gs) <= BALL_QUERY_MULTI_MAX and _MULTI_BALL_QUERY:
             # multi-scale grouping: every scale's list from one scan of the cloud (same lists as one ball_query per scale)
-            lists = ball_query_multi(new_xyz, xyz, [g.radius for g in gs], [g.n_samples for g in gs], return_cnt=True)
+            lists = ball_query_multi(new_xyz, xyz, [g.radius for g in gs], [g.n_samples for g in gs], return_cnt=True, lengths=lengths)
         else:
-            lists = [ball_query(new_xyz, xyz, g.radius, g.n_samples, return_cnt=True) for g in gs]
+            lists = [ball_query(new_xyz, xyz, g.radius, g.n_samples, return_cnt=True, lengths=lengths) for g in gs]
         if self.compact_duplicates and 1 < len(gs) <= BALL_QUERY_MULTI_MAX and _MULTI_BALL_QUERY:
             offs = group_offsets_multi([cnt for _, cnt in lists])
         else:
@@ -59,10 +65,13 @@ class PointNetModuleBase(nn.Module):
             out.append((idx, cnt, off))
         return new_xyz, out
 
-    def forward(self, xyz: torch.Tensor, feature: Optional[torch.Tensor], sampling=None):
+    def forward(self, xyz: torch.Tensor, feature: Optional[torch.Tensor], sampling=None, lengths=None):
         """xyz [B,N,3], feature [B,N,C] -> (new_xyz [B,n_points,3] | None, new_feature [B,n_points,C']).
-        ``sampling`` = a precomputed result of ``sample(xyz)`` (see PointNet2_cls.precompute_sampling)."""
-        new_xyz, idxs = sampling if sampling is not None else self.sample(xyz)
+        ``sampling`` = a precomputed result of ``sample(xyz)`` (see PointNet2_cls.precompute_sampling).  ``lengths``: per-cloud
+        point counts of a ragged batch, used by ``sample`` only -- the grouped kernels reach the cloud through idx, which never
+        names a pad row.  Training caveat: the per-point GEMM of a folded first layer runs over all B*N rows and its weight
+        gradient multiplies pad features by a zero gradient, so pad rows must be FINITE when training."""
+        new_xyz, idxs = sampling if sampling is not None else self.sample(xyz, lengths)
         new_feature_list = []
         for grouper, mlp, ic in zip(self.groupers, self.mlps, idxs):
             if ic is None:
@@ -139,12 +148,17 @@ class SamplingPrefetch:
     """For networks with a ``pointnet_modules`` list: every index-producing op (FPS + ball query per level) depends on xyz
     only, so the set for a batch can be produced ahead of its forward pass, on another stream."""
 
-    def precompute_sampling(self, xyz, stream=None):
+    def precompute_sampling(self, xyz, stream=None, lengths=None):
         """Run every index-producing op of the network (FPS + ball query per level: they depend on xyz only) for a
         batch, optionally on a side stream so that it overlaps other work -- the sampling of batch t+1 hides under
         the backward pass of batch t, the way an input pipeline would prepare it.  Returns a handle for
         ``forward(xyz, feature, sampling=handle)``.  The chain of m-1 dependent FPS steps occupies only B
-        workgroups, so it costs nothing to run it beside the MFMA kernels."""
+        workgroups, so it costs nothing to run it beside the MFMA kernels.
+        ``lengths``: per-cloud point counts of a ragged batch; only the first level sees them (its output is dense), and the
+        device tensor is kept in the handle (``handle["lengths"]``, None for a dense batch) for consumers that write per raw point."""
+        if lengths is not None:
+            first = self.pointnet_modules[0]
+            lengths = _lengths(lengths, xyz.shape[0], xyz.shape[1], xyz.device, n_samples=first.n_points)
         cur = torch.cuda.current_stream()
         stream, owned = sampling_stream(self, stream, xyz.device)
         if stream is None:
@@ -163,10 +177,12 @@ class SamplingPrefetch:
             # ... and may be a temporary of the caller (x.transpose(1, 2).contiguous()): it dies when this call returns, and the
             # consumer stream's allocator pool would hand its memory out again while the producer stream still reads it
             xyz.record_stream(stream)
+            if lengths is not None:
+                lengths.record_stream(stream)
         out = []
         with torch.cuda.stream(stream), torch.no_grad():
-            for module in self.pointnet_modules:
-                s = module.sample(xyz)
+            for i, module in enumerate(self.pointnet_modules):
+                s = module.sample(xyz, lengths) if i == 0 else module.sample(xyz)
                 out.append(s)
                 if s[0] is not None:
                     xyz = s[0]
@@ -175,7 +191,22 @@ class SamplingPrefetch:
         # "owned" + "fed_from": every batch of work on the network's private stream starts by waiting for this consumer stream (the
         # wait_stream above), so memory of this handle that the host frees after enqueueing its consumers can only be handed out
         # again -- by the per-stream pools of the caching allocator, to a LATER call of this function -- behind those consumers.
-        return {"levels": out, "event": ev, "stream": stream, "fed_from": cur, "owned": owned}
+        # (lengths lives on the CONSUMER stream's pool -- made before the stream switch -- and the producer's use is recorded above)
+        return {"levels": out, "event": ev, "stream": stream, "fed_from": cur, "owned": owned, "lengths": lengths}
+
+    @staticmethod
+    def resolve_lengths(xyz, sampling, lengths, n_samples=None):
+        """The per-cloud counts of a ragged batch as a device int32 [B] (None: a dense batch), from ``lengths`` or from the
+        handle.  Given alone, ``lengths`` is converted once (``ops._lengths``: host values are validated, a device tensor is not
+        read back).  Given TOGETHER with a handle it must name the counts the handle was produced with, else ``ValueError``:
+        that one combination compares the two on the host, i.e. it synchronises unless ``lengths`` is the handle's own tensor."""
+        held = None if sampling is None else sampling.get("lengths")
+        if lengths is None:
+            return held
+        lengths = _lengths(lengths, xyz.shape[0], xyz.shape[1], xyz.device, n_samples=n_samples)
+        if sampling is not None and (held is None or (held is not lengths and not torch.equal(held, lengths))):
+            raise ValueError("lengths differ from those the sampling handle was produced with")
+        return lengths
 
     @staticmethod
     def adopt_sampling(sampling):
@@ -196,6 +227,8 @@ class SamplingPrefetch:
                 for t in [new_xyz] + [u for ic in idxs if ic is not None for u in ic]:
                     if t is not None:
                         t.record_stream(cur)
+            if sampling.get("lengths") is not None:               # allocated on the stream the handle was fed from, maybe not this one
+                sampling["lengths"].record_stream(cur)
 
 
 class PointNet2_cls(SamplingPrefetch, nn.Module):
@@ -218,10 +251,15 @@ class PointNet2_cls(SamplingPrefetch, nn.Module):
             nn.Dropout(0.5), nn.Linear(256, self.n_classes),
         )
 
-    def forward(self, xyz, feature, sampling=None):
+    def forward(self, xyz, feature, sampling=None, lengths=None):
+        """``lengths``: per-cloud point counts of a ragged batch (or carried by the handle; both given and different:
+        ``ValueError``, see ``resolve_lengths``).  Everything after the first level's sampling is dense, so grouped rows, BatchNorm
+        statistics and gradients only ever see valid points; when training, pad rows must be finite (see
+        PointNetModuleBase.forward)."""
+        lengths = self.resolve_lengths(xyz, sampling, lengths, self.pointnet_modules[0].n_points)
         self.adopt_sampling(sampling)
         for i, module in enumerate(self.pointnet_modules):
-            xyz, feature = module(xyz, feature, None if sampling is None else sampling["levels"][i])
+            xyz, feature = module(xyz, feature, None if sampling is None else sampling["levels"][i], lengths if i == 0 else None)
         feature = feature.squeeze(dim=1)                                                         # :157
         return fc_head(self.fc_layer, feature)
 

@@ -47,9 +47,14 @@ class PointNet2_partseg(SamplingPrefetch, nn.Module):
         self.drop = nn.Dropout(0.5)
         self.head2 = PointwiseMLP([128, self.part_num], bias=True, bn=False, last_act=False)   # Conv1d(128, part_num, 1)
 
-    def forward(self, xyz, feature, cls_label, sampling=None):
+    def forward(self, xyz, feature, cls_label, sampling=None, lengths=None):
         """xyz [B,N,3], feature [B,N,3], cls_label one-hot [B,16] -> [B,part_num,N].  ``sampling``: a handle from
-        ``precompute_sampling(xyz)`` (the encoder's FPS / ball-query indices produced ahead, e.g. on a side stream)."""
+        ``precompute_sampling(xyz)`` (the encoder's FPS / ball-query indices produced ahead, e.g. on a side stream).
+        ``lengths`` (a ragged batch) is not supported here: FP1 and the head run per raw point and their BatchNorm would count
+        the pad rows.  ``pointcloudlib_amd.inference.frozen(net)`` evaluates ragged batches."""
+        if lengths is not None or (sampling is not None and sampling.get("lengths") is not None):
+            raise NotImplementedError("PointNet2_partseg.forward(lengths=...): FP1's BatchNorm would count pad rows (a masked BatchNorm is "
+                                      "a separate change); use pointcloudlib_amd.inference.frozen(net)(xyz, feature, cls_label, lengths=...)")
         B, N, _ = xyz.shape
         self.adopt_sampling(sampling)
         lv = [None, None, None] if sampling is None else sampling["levels"]

@@ -8,6 +8,11 @@ compare three forms: ``eval`` (the network's default accumulation, fp64 flush ev
 ``set_accumulation(copy, 0)``: plain fp32 chains) and ``frozen``.
 
     python tools/bench_infer.py [--windows 7] [--iters 5] [--warmup 3] [--batch 32 256] [--nets ssg msg] [--points 1024]
+
+``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
+lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
+(a) ``dense`` frozen at N, (b) ``ragged_full`` with every length = N, (c) ``ragged`` with the drawn lengths, (d) ``loop``: B calls
+with B = 1, each on a cloud's own points.  The JSON line also goes to profiles/infer_ragged_bench_line.json.
 """
 import argparse
 import copy
@@ -42,6 +47,42 @@ def _peak(fn):
     return torch.cuda.max_memory_allocated() - base
 
 
+def _ragged_case(kind, fnet, xyz, nrm, extra, a):
+    """The four forms of --ragged for one net and batch (same window estimator as the dense rows)."""
+    import numpy as np
+    B, N, _ = xyz.shape
+    dev = xyz.device
+    lengths = np.random.default_rng(12345).integers(N // 2, N + 1, B)
+    lengths[int(lengths.argmax())] = N
+    full = torch.full((B,), N, dtype=torch.int32, device=dev)
+    drawn = torch.from_numpy(lengths.astype(np.int32)).to(dev)
+    own = [(xyz[b:b + 1, :n].contiguous(), nrm[b:b + 1, :n].contiguous(), *(e[b:b + 1] for e in extra)) for b, n in enumerate(lengths.tolist())]
+
+    def loop():
+        return [fnet(*args) for args in own]
+
+    forms = [("dense", lambda: fnet(xyz, nrm, *extra)), ("ragged_full", lambda: fnet(xyz, nrm, *extra, lengths=full)),
+             ("ragged", lambda: fnet(xyz, nrm, *extra, lengths=drawn)), ("loop", loop)]
+    for _ in range(a.warmup):
+        for _, fn in forms:
+            fn()
+    times = {name: [] for name, _ in forms}
+    for w in range(a.windows):
+        for name, fn in (forms if w % 2 == 0 else forms[::-1]):
+            times[name].append(_window(fn, a.iters))
+    case = {"net": kind, "B": B, "N": N, "mean_length": round(float(lengths.mean()), 1), "min_length": int(lengths.min())}
+    for name, fn in forms:
+        case[f"{name}_ms"] = round(statistics.median(times[name]), 4)
+        case[f"{name}_ms_min"] = round(min(times[name]), 4)
+        case[f"{name}_ms_max"] = round(max(times[name]), 4)
+        if name != "loop":
+            case[f"{name}_peak_mib"] = round(_peak(fn) / 2**20, 2)
+    case["ragged_full_vs_dense"] = round(case["ragged_full_ms"] / case["dense_ms"], 4)
+    case["ragged_vs_dense"] = round(case["ragged_ms"] / case["dense_ms"], 4)
+    case["loop_vs_ragged"] = round(case["loop_ms"] / case["ragged_ms"], 2)
+    return case
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
@@ -51,6 +92,7 @@ def main():
     ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg"])
     ap.add_argument("--points", type=int, default=None, help="default: 1024 (cls), 2048 (part-seg)")
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
+    ap.add_argument("--ragged", action="store_true", help="ragged batches: dense / ragged at full length / ragged / per-cloud loop")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_infer.py needs a GPU")
@@ -60,6 +102,8 @@ def main():
     dev = torch.device("cuda")
     cls_only = all(k in ("ssg", "msg") for k in a.nets)
     res = {"N": (a.points or 1024) if cls_only else (a.points or 2048), "windows": a.windows, "iters": a.iters, "cases": []}
+    if a.ragged:
+        del res["N"]                 # every --ragged case carries its own N (classifiers and part-seg nets share one line)
     for kind in a.nets:
         seg = kind.startswith("partseg")
         N = a.points or (2048 if seg else 1024)
@@ -88,6 +132,9 @@ def main():
             def frozen_fwd():
                 return fnet(xyz, nrm, *extra)
 
+            if a.ragged:
+                res["cases"].append(_ragged_case(kind, fnet, xyz, nrm, extra, a))
+                continue
             if a.frozen_only:
                 forms = [("frozen", frozen_fwd)]
             elif seg:
@@ -115,6 +162,10 @@ def main():
                     case["max_abs_logit_diff"] = float((eval_fwd() - frozen_fwd()).abs().max())
             res["cases"].append(case)
     print(json.dumps(res))
+    if a.ragged:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "infer_ragged_bench_line.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
 
 
 if __name__ == "__main__":
