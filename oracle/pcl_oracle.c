@@ -5,16 +5,31 @@
  * or call this file; only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg use it, and there only as the checker / the CPU baseline.
  *
- * PARITY UNPINNED: the reference (Jittor/PointCloudLib) ships no golden
- * vectors, no tests and no CPU path for these ops (they exist only as CUDA
- * strings handed to jt.code, misc/ops.py:278,376,656) and Jittor is not
- * installable here.  This file restates the *source-level* semantics of that
- * CUDA text in plain C, one function per kernel, single-rounded IEEE fp32
- * operations in the order the source writes them (compile with
- * -ffp-contract=off; what nvcc's default -fmad=true did to the original is
- * not knowable here).  It is cross-checked against an independent NumPy
- * restatement (oracle/np_oracle.py) and hand-derived known answers
- * (tests/test_oracle_kat.py).
+ * The reference (Jittor/PointCloudLib) ships no golden vectors, no tests and
+ * no CPU path for these ops (they exist only as CUDA strings handed to
+ * jt.code, misc/ops.py:278,376,656) and Jittor is not installable here.  This
+ * file restates the *source-level* semantics of that CUDA text in plain C, one
+ * function per kernel, single-rounded IEEE fp32 operations in the order the
+ * source writes them (compile with -ffp-contract=off).
+ *
+ * PINNED (FPS, ball query, k-NN): the three __global__ kernels are plain CUDA
+ * C.  oracle/ref_kernels.py cuts their text out of a reference checkout and
+ * hipcc compiles it for gfx950 with -ffp-contract=off; on an MI355X that build
+ * returns the same indices as pclo_fps_f32, pclo_ball_query_f32 and
+ * pclo_knn_f32 (tests/test_reference_kernels_gpu.py: every block size of the
+ * reduction tree on all-tie clouds, the `mag <= 1e-3` float-against-double
+ * boundary, the 1e10 cap, d2 == fl(r*r), k == Nr, the stable sort), and its
+ * recorded output is a fixture these functions must reproduce on every machine
+ * (tests/test_reference_golden_cpu.py).  The one deliberate definition is the
+ * row of a ball query without a hit (unwritten there, zeros here).  The
+ * independent NumPy restatement (oracle/np_oracle.py) and the hand-derived
+ * known answers (tests/test_oracle_kat.py) remain.
+ *
+ * STILL UNPINNED: what nvcc's default -fmad=true did to the original (hipcc's
+ * contraction of a three-term sum need not be nvcc's), and everything the
+ * reference does through Jittor ops: argsort, matmul, reindex, the 3-NN of
+ * misc/ops.py:83-93, PointConv's Python FPS and knn_point (the functions
+ * further down that restate those say so themselves).
  *
  * SECOND READING ("fma" mode, pclo_set_contract(1)): nvcc's default -fmad=true
  * contracts a multiply feeding an add into one fused multiply-add.  For the
@@ -26,8 +41,10 @@
  * own.  Mode 1 exists to MEASURE how many indices depend on that choice
  * (tools/contraction_sensitivity.py -> profiles/r03_contraction_sensitivity.txt)
  * and as the checker of the library's named second definition
- * (PCL_KNN_CONTRACT=fma).  Neither reading is pinned by anything the
- * reference holds.
+ * (PCL_KNN_CONTRACT=fma).  Mode 0 is pinned as above.  Mode 1 is pinned for
+ * k-NN only, where one contraction exists: the -ffp-contract=fast build of
+ * the reference's kernels equals it on every k-NN case; for the three-term
+ * sums it stays a model of nvcc that nothing here can run.
  *
  * All citations are into /root/reference/.
  */
