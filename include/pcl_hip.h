@@ -820,6 +820,49 @@ int pcl_fp_level_infer_ragged_f32(const float* Us, const float* skip_small, cons
                                   const float* const* shift, int act_mask, float slope, float* out, int ldo, float* tap,
                                   int tap_layer, int ldt, void* stream);
 
+/* ---- packed rows of a ragged batch (csrc/pack.hip) ------------------------------------------------
+ * No reference counterpart.  What runs once per raw point of a ragged batch (FP1, the head and the loss of PointNet++ part
+ * segmentation) runs on R = sum_b n_b rows, cloud after cloud without a pad row: n_b = n_valid[b] clamped to [1, N] (ragged
+ * convention above), row_off int32 [B+1] = the exclusive scan of the n_b, point i < n_b of cloud b is packed row row_off[b] + i.
+ * n_rows is the number of rows the packed buffer holds (R; the host knows it without reading row_off back when it knows the
+ * counts): no packed row >= n_rows is read or written, so a wrong n_rows loses rows and never leaves the buffer.  The caller
+ * owns every buffer; the calls are stream-ordered, allocate nothing and never synchronise; B <= 65535 (grid.y).
+ *
+ * pcl_row_offsets_i32: n_valid [B] -> row_off [B+1], row_off[B] = R.  One workgroup. */
+int pcl_row_offsets_i32(const int32_t* n_valid, int B, int N, int32_t* row_off, void* stream);
+/* reference: misc/ops.py:83-96 (interpolate, concatenate) on the valid points only -- one launch.
+ *   onehot [B, n_onehot] (NULL when n_onehot == 0), skip [B, N, CS] (NULL when CS == 0), points2 [B, S, D2], idx3 / w3 [B, N, 3]
+ *   from pcl_three_nn_ragged_f32 (NULL when S == 1)  ->  rows [n_rows, ld], ld = n_onehot + CS + D2:
+ *   rows[row_off[b] + i] = [ onehot[b] | skip[b, i] | sum_k w3[b,i,k] * points2[b, idx3[b,i,k]] ]   for i < n_b,
+ * the sum evaluated as pcl_three_interp_f32 does (products and sums rounded one by one, k = 0, 1, 2), so the rows equal
+ * pcl_three_interp_f32 + a concatenation bit for bit; S == 1 copies points2[b, 0] (the reference's expand).  Pad rows of skip,
+ * idx3 and w3 are never read (NaN, indices out of range); idx3 is clamped to [0, S).  8-byte pieces when D2 and n_onehot + CS are
+ * even and points2 / rows are 8-byte aligned, one float per lane otherwise. */
+int pcl_fp_pack_rows_f32(const float* onehot, int n_onehot, const float* skip, int CS, const float* points2, const int32_t* idx3,
+                         const float* w3, const int32_t* n_valid, const int32_t* row_off, int B, int N, int S, int D2, int n_rows,
+                         float* rows, void* stream);
+/* reference: gradient of misc/ops.py:83-96 w.r.t. points2 and points1, from the packed rows' gradient grows [n_rows, ld].
+ *   gpoints2 [B, S, D2]: zero-filled here, then gpoints2[b, idx3[b,i,k]] += w3[b,i,k] * grows[row_off[b] + i, n_onehot + CS:] with
+ *   fp32 atomic adds (as pcl_three_interp_bwd_f32: the sum's order, hence its last bits, may differ from run to run); each atomic
+ *   wave-instruction covers 64 consecutive floats of one row.  S == 1: a plain column sum per cloud in a fixed order, no atomics,
+ *   run-to-run identical.
+ *   gskip [B, N, CS] (NULL: not wanted): columns [n_onehot, n_onehot + CS) of grows, pad rows exact zeros (pcl_unpack_rows_b32).
+ * The one-hot block gets no gradient. */
+int pcl_fp_pack_rows_bwd_f32(const float* grows, int n_onehot, int CS, const int32_t* idx3, const float* w3, const int32_t* n_valid,
+                             const int32_t* row_off, int B, int N, int S, int D2, int n_rows, float* gpoints2, float* gskip,
+                             void* stream);
+/* Rows of W 32-bit words (any 4-byte type; an 8-byte type with W doubled).  The packed operand is a window of wider rows: row
+ * stride ld words, first column col0, col0 + W <= ld.
+ *   pack:   dense [B, N, W] -> packed[(row_off[b] + i) * ld + col0 + c] = dense[b, i, c] for i < n_b; pad rows are never read,
+ *           nothing outside the window is written.
+ *   unpack: packed -> dense [B, N, W]; pad rows (and rows >= n_rows) are written as zero bits.
+ * Each is the other's gradient (labels, logits, the skip window of pcl_fp_pack_rows_bwd_f32). */
+int pcl_pack_rows_b32(const void* dense, const int32_t* n_valid, const int32_t* row_off, int B, int N, int W, int ld, int col0,
+                      int n_rows, void* packed, void* stream);
+/* reference: none (see pcl_pack_rows_b32) */
+int pcl_unpack_rows_b32(const void* packed, const int32_t* n_valid, const int32_t* row_off, int B, int N, int W, int ld, int col0,
+                        int n_rows, void* dense, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

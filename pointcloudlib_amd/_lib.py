@@ -72,6 +72,11 @@ _SIGS = {
     "pcl_three_nn_ragged_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "pcl_fp_level_infer_ragged_f32": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P,
                                               c_int, c_float, _P, c_int, _P, c_int, c_int, _P]),
+    "pcl_row_offsets_i32": (c_int, [_P, c_int, c_int, _P, _P]),
+    "pcl_fp_pack_rows_f32": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "pcl_fp_pack_rows_bwd_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "pcl_pack_rows_b32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "pcl_unpack_rows_b32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "pcl_ball_query_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P]),
     "pcl_ball_query_multi_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "pcl_group_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),

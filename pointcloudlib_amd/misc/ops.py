@@ -19,7 +19,8 @@ from .. import _lib
 __all__ = [
     "optimal_block", "furthest_point_sample", "ball_query", "ball_query_multi", "group_offsets_multi", "group_points", "group_points_compact", "RowSet", "group_all",
     "index_points",
-    "knn_indices", "edge_features", "three_nn", "three_interpolate", "FurthestPointSampler", "BallQueryGrouper", "GroupAll",
+    "knn_indices", "edge_features", "three_nn", "three_interpolate", "row_offsets", "pack_rows", "unpack_rows", "interpolate_pack",
+    "FurthestPointSampler", "BallQueryGrouper", "GroupAll",
     "KNN", "PointNetFeaturePropagation",
 ]
 
@@ -501,6 +502,164 @@ def three_interpolate(points2, idx3, w3):
     return _ThreeInterpolate.apply(points2, idx3, w3)
 
 
+# ----------------------------------------------------------------------------- packed rows of a ragged batch (csrc/pack.hip)
+def row_offsets(lengths, B, N, device, n_rows=None):
+    """Per-cloud counts of a ragged batch -> (row_off int32 [B+1] on the device, R): the exclusive scan of the counts and their
+    sum.  Packed row ``row_off[b] + i`` is point i of cloud b; R rows in all.  Host-side ``lengths`` (a
+    sequence or a CPU tensor, validated as by ``_lengths``) give R as a host sum: no synchronisation.  A device tensor is not read
+    back when the caller states ``n_rows``; that it equals the sum is then the caller's precondition (a wrong value loses rows,
+    the kernels never leave the buffers).  A device tensor WITHOUT ``n_rows`` costs one ``.item()``: a host synchronisation."""
+    if lengths is None:
+        raise ValueError("row_offsets: lengths is None (a dense batch has no packed rows to offset)")
+    on_device = isinstance(lengths, torch.Tensor) and lengths.is_cuda
+    if not on_device and n_rows is None:
+        host = lengths.detach() if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths)
+    lengths = _lengths(lengths, B, N, device)
+    if not lengths.is_cuda:
+        raise RuntimeError(f"row_offsets: expected the GPU as device (libpcl_hip has no CPU path), got {lengths.device}")
+    row_off = torch.empty((B + 1,), dtype=torch.int32, device=lengths.device)
+    _lib.call("pcl_row_offsets_i32", _p(lengths), B, N, _p(row_off), _stream())
+    if n_rows is None:
+        n_rows = int(row_off[B].item()) if on_device else int(host.sum())
+    return row_off, int(n_rows)
+
+
+def _words(t, name):
+    if t.dtype.itemsize not in (4, 8) or t.dtype.is_complex:
+        raise TypeError(f"{name}: rows move as 32-bit words: a dtype of 4 or 8 bytes, got {t.dtype}")
+    return t.dtype.itemsize // 4
+
+
+def _move_rows(pack, src, lengths, row_off, N, R):
+    """pack: src [B, N, ...] -> [R, ...];  unpack: src [R, ...] -> [B, N, ...] with zero pad rows."""
+    if not src.is_cuda:
+        raise RuntimeError(f"{'pack_rows' if pack else 'unpack_rows'}: expected a tensor on the GPU (libpcl_hip has no CPU path), got {src.device}")
+    src = src.contiguous()
+    B = lengths.shape[0]
+    tail = tuple(src.shape[2:] if pack else src.shape[1:])
+    W = _words(src, "rows") * int(math.prod(tail))
+    if W == 0:
+        raise ValueError("rows without columns")
+    out = torch.empty(((R,) if pack else (B, N)) + tail, dtype=src.dtype, device=src.device)
+    _lib.call("pcl_pack_rows_b32" if pack else "pcl_unpack_rows_b32", _p(src), _p(lengths), _p(row_off), B, N, W, W, 0, R, _p(out), _stream(),
+              algo_bytes=8 * R * W)
+    return out
+
+
+class _PackRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, lengths, row_off, R):
+        if t.dim() < 2 or t.shape[0] != lengths.shape[0]:
+            raise ValueError(f"pack_rows: expected [B={lengths.shape[0]}, N, ...], got {tuple(t.shape)}")
+        ctx.save_for_backward(lengths, row_off)
+        ctx.dims = (t.shape[1], R)
+        return _move_rows(True, t, lengths, row_off, t.shape[1], R)
+
+    @staticmethod
+    def backward(ctx, g):
+        lengths, row_off = ctx.saved_tensors
+        N, R = ctx.dims
+        return _move_rows(False, g, lengths, row_off, N, R), None, None, None
+
+
+class _UnpackRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, lengths, row_off, N):
+        ctx.save_for_backward(lengths, row_off)
+        ctx.dims = (N, rows.shape[0])
+        return _move_rows(False, rows, lengths, row_off, N, rows.shape[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        lengths, row_off = ctx.saved_tensors
+        N, R = ctx.dims
+        return _move_rows(True, g, lengths, row_off, N, R), None, None, None
+
+
+def _packed_args(lengths, row_off, B, N, device):
+    lengths = _dev(_lengths(lengths, B, N, device), "lengths", torch.int32)
+    row_off = _dev(row_off, "row_off", torch.int32)
+    if row_off.dim() != 1 or row_off.shape[0] != B + 1:
+        raise ValueError(f"row_off: expected shape [{B + 1}] (row_offsets), got {tuple(row_off.shape)}")
+    return lengths, row_off
+
+
+def pack_rows(t, lengths, row_off, R):
+    """t [B, N, ...] -> [R, ...]: the valid rows of every cloud, cloud after cloud (``row_off``, R from ``row_offsets``).  Any dtype of
+    4 or 8 bytes (features, logits, int64 labels); pad rows are never read.  Differentiable: the gradient is ``unpack_rows``."""
+    if t.dim() < 2:
+        raise ValueError(f"pack_rows: expected [B, N, ...], got {tuple(t.shape)}")
+    lengths, row_off = _packed_args(lengths, row_off, t.shape[0], t.shape[1], t.device)
+    return _PackRows.apply(t, lengths, row_off, int(R))
+
+
+def unpack_rows(rows, lengths, row_off, N):
+    """rows [R, ...] -> [B, N, ...] with every pad row zero bits; the inverse of ``pack_rows`` on the valid rows, and its gradient."""
+    B = row_off.shape[0] - 1
+    lengths, row_off = _packed_args(lengths, row_off, B, int(N), rows.device)
+    return _UnpackRows.apply(rows, lengths, row_off, int(N))
+
+
+class _InterpolatePack(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points2, skip, onehot, idx3, w3, lengths, row_off, N, R):
+        points2 = _dev(points2, "points2")
+        skip, onehot = _dev(skip, "skip"), _dev(onehot, "onehot")
+        idx3, w3 = _dev(idx3, "idx3", torch.int32), _dev(w3, "w3")
+        B, S, D2 = points2.shape
+        CS = 0 if skip is None else skip.shape[2]
+        n1 = 0 if onehot is None else onehot.shape[1]
+        rows = torch.empty((R, n1 + CS + D2), dtype=torch.float32, device=points2.device)
+        _lib.call("pcl_fp_pack_rows_f32", _p(onehot), n1, _p(skip), CS, _p(points2), _p(idx3), _p(w3), _p(lengths), _p(row_off), B, N, S, D2,
+                  R, _p(rows), _stream(), algo_bytes=4 * R * (n1 + 2 * CS + D2 + 6) + 4 * B * S * D2)
+        ctx.save_for_backward(idx3, w3, lengths, row_off)
+        ctx.dims = (B, N, S, D2, CS, n1, R)
+        return rows
+
+    @staticmethod
+    def backward(ctx, grows):
+        idx3, w3, lengths, row_off = ctx.saved_tensors
+        B, N, S, D2, CS, n1, R = ctx.dims
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 9
+        grows = _dev(grows, "grad")
+        gskip = torch.empty((B, N, CS), dtype=torch.float32, device=grows.device) if ctx.needs_input_grad[1] else None
+        if not ctx.needs_input_grad[0]:           # the skip alone: the column window of the gradient, pad rows zero
+            _lib.call("pcl_unpack_rows_b32", _p(grows), _p(lengths), _p(row_off), B, N, CS, n1 + CS + D2, n1, R, _p(gskip), _stream())
+            return None, gskip, None, None, None, None, None, None, None
+        g2 = torch.empty((B, S, D2), dtype=torch.float32, device=grows.device)
+        _lib.call("pcl_fp_pack_rows_bwd_f32", _p(grows), n1, CS, _p(idx3), _p(w3), _p(lengths), _p(row_off), B, N, S, D2, R, _p(g2),
+                  _p(gskip), _stream(), algo_bytes=4 * R * (4 * D2 + 6 + 2 * CS))
+        return g2, gskip, None, None, None, None, None, None, None
+
+
+def interpolate_pack(points2, idx3, w3, lengths, row_off, n_rows, N, skip=None, onehot=None):
+    """Feature propagation's "interpolate, concatenate" written straight as the packed rows of a ragged batch, one launch:
+    ``[n_rows, n_onehot + CS + D2]``, row ``row_off[b] + i`` = ``[onehot[b] | skip[b, i] | sum_k w3[b,i,k] points2[b, idx3[b,i,k]]]`` for
+    ``i < lengths[b]`` -- bit for bit ``three_interpolate`` + ``cat`` on the cloud's own rows.  points2 [B,S,D2]; idx3 / w3 [B,N,3] from
+    ``three_nn(lengths1=lengths)`` (None when S == 1: the one source row is broadcast); skip [B,N,CS] and onehot [B,n_onehot] optional.
+    Gradients reach points2 (fp32 atomic adds like ``three_interpolate``'s; S == 1: a fixed-order sum) and skip (zero on pad rows);
+    the one-hot block is a label and gets none."""
+    if points2.dim() != 3:
+        raise ValueError(f"points2 must be [B,S,D2], got {tuple(points2.shape)}")
+    B, S, _ = points2.shape
+    if onehot is not None and onehot.requires_grad:
+        raise ValueError("interpolate_pack: onehot is a per-cloud label block and gets no gradient")
+    if (idx3 is None or w3 is None) and S != 1:
+        raise ValueError(f"interpolate_pack: idx3 / w3 may be None only for S == 1, S = {S}")
+    for name, t, shape in (("idx3", idx3, (B, N, 3)), ("w3", w3, (B, N, 3))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected {list(shape)}, got {tuple(t.shape)}")
+    if skip is not None and (skip.dim() != 3 or tuple(skip.shape[:2]) != (B, N)):
+        raise ValueError(f"skip: expected [{B},{N},CS], got {tuple(skip.shape)}")
+    if onehot is not None and (onehot.dim() != 2 or onehot.shape[0] != B):
+        raise ValueError(f"onehot: expected [{B},n_onehot], got {tuple(onehot.shape)}")
+    lengths, row_off = _packed_args(lengths, row_off, B, int(N), points2.device)
+    if S == 1:
+        idx3 = w3 = None
+    return _InterpolatePack.apply(points2, skip, onehot, idx3, w3, lengths, row_off, int(N), int(n_rows))
+
+
 # ----------------------------------------------------------------------------- modules (reference names)
 class _Module(nn.Module):
     def execute(self, *a, **k):   # Jittor's name for forward
@@ -581,3 +740,20 @@ class PointNetFeaturePropagation(_Module):
             interpolated = three_interpolate(points2, idx, w)              # :86-93
         new_points = torch.cat([points1, interpolated], dim=-1) if points1 is not None else interpolated
         return self.mlp(new_points.contiguous())
+
+    def forward_packed(self, xyz1, xyz2, points1, points2, lengths, row_off, n_rows, onehot=None):
+        """The same level on a ragged batch whose TARGETS have ``lengths[b]`` valid rows (sources dense), as packed rows:
+        -> [n_rows, mlp[-1]], row ``row_off[b] + i`` = target i of cloud b (``row_offsets``).  The MLP's input is built directly as
+        ``[n_rows, n_onehot + D1 + D2]`` rows (``interpolate_pack``; ``onehot`` [B, n_onehot]: a per-cloud block in front of points1 that
+        is never expanded to [B, N, n_onehot]), so its training-mode BatchNorm takes its statistics over the valid points alone and
+        no pad row of xyz1 / points1 is read.  When points1 needs no gradient the MLP's input gradient is produced from the first
+        interpolated column on (``x_grad_from``)."""
+        B, N, _ = xyz1.shape
+        S = xyz2.shape[1]
+        lengths = _lengths(lengths, B, N, xyz1.device)
+        idx = w = None
+        if S > 1:
+            idx, w = three_nn(xyz1, xyz2, lengths1=lengths)
+        rows = interpolate_pack(points2, idx, w, lengths, row_off, n_rows, N, skip=points1, onehot=onehot)
+        skip_grad = points1 is not None and points1.requires_grad and torch.is_grad_enabled()
+        return self.mlp(rows, x_grad_from=0 if skip_grad else rows.shape[1] - points2.shape[2])

@@ -155,10 +155,16 @@ class SamplingPrefetch:
         ``forward(xyz, feature, sampling=handle)``.  The chain of m-1 dependent FPS steps occupies only B
         workgroups, so it costs nothing to run it beside the MFMA kernels.
         ``lengths``: per-cloud point counts of a ragged batch; only the first level sees them (its output is dense), and the
-        device tensor is kept in the handle (``handle["lengths"]``, None for a dense batch) for consumers that write per raw point."""
+        device tensor is kept in the handle (``handle["lengths"]``, None for a dense batch) for consumers that write per raw point.
+        ``handle["n_rows"]``: the sum of host-side lengths (the packed-row count, ``ops.row_offsets``), None for a device tensor or a
+        dense batch."""
+        n_rows = None
         if lengths is not None:
             first = self.pointnet_modules[0]
+            host = None if isinstance(lengths, torch.Tensor) and lengths.is_cuda else lengths
             lengths = _lengths(lengths, xyz.shape[0], xyz.shape[1], xyz.device, n_samples=first.n_points)
+            if host is not None:                          # (validated just above)
+                n_rows = int(torch.as_tensor(host).sum())
         cur = torch.cuda.current_stream()
         stream, owned = sampling_stream(self, stream, xyz.device)
         if stream is None:
@@ -192,7 +198,7 @@ class SamplingPrefetch:
         # wait_stream above), so memory of this handle that the host frees after enqueueing its consumers can only be handed out
         # again -- by the per-stream pools of the caching allocator, to a LATER call of this function -- behind those consumers.
         # (lengths lives on the CONSUMER stream's pool -- made before the stream switch -- and the producer's use is recorded above)
-        return {"levels": out, "event": ev, "stream": stream, "fed_from": cur, "owned": owned, "lengths": lengths}
+        return {"levels": out, "event": ev, "stream": stream, "fed_from": cur, "owned": owned, "lengths": lengths, "n_rows": n_rows}
 
     @staticmethod
     def resolve_lengths(xyz, sampling, lengths, n_samples=None):

@@ -54,7 +54,8 @@ class PointNet2_partseg(SamplingPrefetch, nn.Module):
         the pad rows.  ``pointcloudlib_amd.inference.frozen(net)`` evaluates ragged batches."""
         if lengths is not None or (sampling is not None and sampling.get("lengths") is not None):
             raise NotImplementedError("PointNet2_partseg.forward(lengths=...): FP1's BatchNorm would count pad rows (a masked BatchNorm is "
-                                      "a separate change); use pointcloudlib_amd.inference.frozen(net)(xyz, feature, cls_label, lengths=...)")
+                                      "a separate change); use pointcloudlib_amd.inference.frozen(net)(xyz, feature, cls_label, lengths=...) "
+                                      "to evaluate, or forward_packed(xyz, feature, cls_label, lengths=...) (packed rows) to train")
         B, N, _ = xyz.shape
         self.adopt_sampling(sampling)
         lv = [None, None, None] if sampling is None else sampling["levels"]
@@ -68,6 +69,38 @@ class PointNet2_partseg(SamplingPrefetch, nn.Module):
         feature = self.fp1(xyz, l1_xyz, torch.cat([one_hot, xyz, feature], 2), l1_feature)   # :173
         x = self.drop(self.head1(feature))
         return self.head2(x).permute(0, 2, 1)
+
+    def forward_packed(self, xyz, feature, cls_label, lengths=None, sampling=None, n_rows=None):
+        """A ragged batch (capacity N, cloud b = its first ``lengths[b]`` rows) in training or evaluation mode, as PACKED ROWS:
+        -> (logits [R, part_num], row_off int32 [B+1]) with R = sum(lengths) and row ``row_off[b] + i`` = point i of cloud b
+        (``misc.ops.row_offsets``).  Encoder, FP3 and FP2 run as in ``forward`` (dense after the first level's
+        sampling); FP1, the head and whatever follows run on the R valid points only, so every BatchNorm statistic and gradient is
+        that of the valid points.  ``seg_cross_entropy_loss(logits, pack_rows(seg, lengths, row_off, R))`` is the loss.
+        ``lengths``: as for ``precompute_sampling`` (or carried by the handle); None = a dense batch (R = B * N).  ``n_rows``: R when the
+        caller knows it and ``lengths`` is a device tensor (else one ``.item()``); a handle made from host-side lengths carries it.
+        When training, pad rows must be finite (the encoder's folded first layer, see PointNetModuleBase.forward)."""
+        from ...misc.ops import row_offsets
+        B, N, _ = xyz.shape
+        held = None if sampling is None else sampling.get("lengths")
+        lengths = self.resolve_lengths(xyz, sampling, lengths, self.pointnet_modules[0].n_points)
+        if n_rows is None and held is not None:          # (lengths given beside the handle were checked against its own just above)
+            n_rows = sampling.get("n_rows")
+        ragged = lengths
+        if lengths is None:
+            lengths, n_rows = torch.full((B,), N, dtype=torch.int32, device=xyz.device), B * N
+        row_off, R = row_offsets(lengths, B, N, xyz.device, n_rows=n_rows)
+        self.adopt_sampling(sampling)
+        lv = [None, None, None] if sampling is None else sampling["levels"]
+        l1_xyz, l1_feature = self.pointnet_modules[0](xyz, feature, lv[0], ragged)
+        l2_xyz, l2_feature = self.pointnet_modules[1](l1_xyz, l1_feature, lv[1])
+        _, l3_feature = self.pointnet_modules[2](l2_xyz, l2_feature, lv[2])
+        l3_xyz = torch.zeros((B, 1, 3), device=xyz.device, dtype=xyz.dtype)
+        l2_feature = self.fp3(l2_xyz, l3_xyz, l2_feature, l3_feature)
+        l1_feature = self.fp2(l1_xyz, l2_xyz, l1_feature, l2_feature)
+        # FP1's rows [cls_label | xyz | feature | interpolated] (the column order of forward) for the valid points only
+        rows = self.fp1.forward_packed(xyz, l1_xyz, torch.cat([xyz, feature], 2), l1_feature, lengths, row_off, R, onehot=cls_label)
+        x = self.drop(self.head1(rows))
+        return self.head2(x), row_off
 
     def execute(self, *a, **k):
         return self(*a, **k)
