@@ -863,6 +863,38 @@ int pcl_pack_rows_b32(const void* dense, const int32_t* n_valid, const int32_t* 
 int pcl_unpack_rows_b32(const void* packed, const int32_t* n_valid, const int32_t* row_off, int B, int N, int W, int ld, int col0,
                         int n_rows, void* dense, void* stream);
 
+/* ---- pooling over the clouds of packed rows (csrc/segpool.hip) -----------------------------------------
+ * No reference counterpart.  PointNet, its T-Nets and PointNet part segmentation on the packed rows above: row_off int32 [B+1]
+ * from pcl_row_offsets_i32, cloud b owns the packed rows row_off[b] .. row_off[b+1] - 1 of an [n_rows, C] matrix.  The caller
+ * owns every buffer; the calls are stream-ordered, allocate nothing and never synchronise; 1 <= B <= 65535 (grid.y), C >= 1,
+ * n_rows >= 0; no packed row >= n_rows is read or written; plain vector stores, no atomics.
+ *
+ * pcl_row_cloud_i32: row_cloud[r] = the cloud b with row_off[b] <= r < row_off[b+1] for r < n_rows (rows at or beyond row_off[B]:
+ * B - 1).  Made once per batch; the two entry points that walk rows (the pooling backward, the broadcast) read it instead of
+ * searching row_off per row, and clamp what they read to [0, B). */
+int pcl_row_cloud_i32(const int32_t* row_off, int B, int n_rows, int32_t* row_cloud, void* stream);
+/* reference: none.  The segmented form of pcl_bn_act_max_mean_f32's max half:
+ *   out[b, c] = max over the rows r of cloud b of lrelu(fmaf(scale[c], Y[r, c], shift[c]), slope)        out, arg [B, C]
+ *   arg[b, c] = the first row WITHIN the cloud (r - row_off[b]) that attains it
+ * with the same fmaf + lrelu expression as pcl_bn_act_f32 / pcl_bn_act_max_mean_f32: per cloud the result equals theirs bit for
+ * bit.  Y is read once.  float4 pieces when C % 4 == 0 and Y / scale / shift are 16-byte aligned, one float per lane otherwise.
+ * An empty segment (only possible when n_rows < row_off[B] cuts a cloud off entirely) gives out = -inf, arg = 0. */
+int pcl_bn_act_seg_max_f32(const float* Y, const int32_t* row_off, const float* scale, const float* shift, float slope, int B, int C,
+                           int n_rows, float* out, int32_t* arg, void* stream);
+/* reference: none.  Backward of pcl_bn_act_seg_max_f32 w.r.t. the PRE-BatchNorm Y; gmax [B, ldg] (ldg >= C: a column slice of a
+ * wider gradient is read in place):
+ *   du[r, c] = act'(fmaf(scale[c], Y[r, c], shift[c])) * (r - row_off[b] == arg[b, c] ? gmax[b, c] : 0),  b = row_cloud[r]
+ * and the BatchNorm-backward sums (sum du, sum du*Y) as fp64 partial rows stats_ws [*stat_rows_out <= 1024][2][C]: the protocol of
+ * pcl_bn_act_max_mean_bwd_f32 (ext_stats of a deferring pcl_mlp_stack_bwd_f32).  stats_ws holds 1024 * 2 * C doubles. */
+int pcl_bn_act_seg_max_bwd_f32(const float* gmax, int ldg, const int32_t* arg, const float* Y, const float* scale, const float* shift,
+                               float slope, const int32_t* row_off, const int32_t* row_cloud, int B, int C, int n_rows, float* du,
+                               double* stats_ws, int* stat_rows_out, void* stream);
+/* reference: none (the reference's expand over a dense axis).  dst[r, :] = src[row_cloud[r], :] for r < n_rows; src [B, C]. */
+int pcl_seg_broadcast_rows_f32(const float* src, const int32_t* row_cloud, int B, int C, int n_rows, float* dst, void* stream);
+/* reference: none.  The broadcast's gradient: gsrc[b, c] = sum over the rows r of cloud b of g[r, c], accumulated in fp64 in a
+ * fixed order and rounded once (run-to-run identical).  Every element of gsrc [B, C] is written (an empty segment: 0). */
+int pcl_seg_sum_rows_f32(const float* g, const int32_t* row_off, int B, int C, int n_rows, float* gsrc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,11 @@ _SIGS = {
     "pcl_fp_pack_rows_bwd_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "pcl_pack_rows_b32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "pcl_unpack_rows_b32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "pcl_row_cloud_i32": (c_int, [_P, c_int, c_int, _P, _P]),
+    "pcl_bn_act_seg_max_f32": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P]),
+    "pcl_bn_act_seg_max_bwd_f32": (c_int, [_P, c_int, _P, _P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, _P, _P, ctypes.POINTER(c_int), _P]),
+    "pcl_seg_broadcast_rows_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
+    "pcl_seg_sum_rows_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "pcl_ball_query_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P]),
     "pcl_ball_query_multi_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "pcl_group_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),

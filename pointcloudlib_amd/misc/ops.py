@@ -20,6 +20,7 @@ __all__ = [
     "optimal_block", "furthest_point_sample", "ball_query", "ball_query_multi", "group_offsets_multi", "group_points", "group_points_compact", "RowSet", "group_all",
     "index_points",
     "knn_indices", "edge_features", "three_nn", "three_interpolate", "row_offsets", "pack_rows", "unpack_rows", "interpolate_pack",
+    "row_cloud", "packed_layout", "segment_max", "mlp_segment_max", "broadcast_rows",
     "FurthestPointSampler", "BallQueryGrouper", "GroupAll",
     "KNN", "PointNetFeaturePropagation",
 ]
@@ -658,6 +659,134 @@ def interpolate_pack(points2, idx3, w3, lengths, row_off, n_rows, N, skip=None, 
     if S == 1:
         idx3 = w3 = None
     return _InterpolatePack.apply(points2, skip, onehot, idx3, w3, lengths, row_off, int(N), int(n_rows))
+
+
+# ----------------------------------------------------------------------------- pooling over the clouds of packed rows (csrc/segpool.hip)
+def row_cloud(row_off, B, R):
+    """row_off int32 [B+1] (``row_offsets``) -> int32 [R]: the cloud that owns each packed row.  Made once per batch; the pooling
+    backward and ``broadcast_rows`` read it."""
+    row_off = _dev(row_off, "row_off", torch.int32)
+    if row_off.dim() != 1 or row_off.shape[0] != B + 1:
+        raise ValueError(f"row_off: expected shape [{B + 1}] (row_offsets), got {tuple(row_off.shape)}")
+    out = torch.empty((int(R),), dtype=torch.int32, device=row_off.device)
+    _lib.call("pcl_row_cloud_i32", _p(row_off), int(B), int(R), _p(out), _stream())
+    return out
+
+
+def packed_layout(lengths, B, N, device, n_rows=None):
+    """Everything the packed form of a batch [B, N, .] needs, made once: (lengths int32 [B] on the device, row_off int32 [B+1], R,
+    row_cloud int32 [R]).  ``lengths`` as for ``row_offsets`` (host sequences are validated and give R without a synchronisation; a
+    device tensor wants ``n_rows`` or costs one ``.item()``); None = a dense batch, every cloud N rows."""
+    if lengths is None:
+        lengths, n_rows = torch.full((B,), N, dtype=torch.int32, device=device), B * N
+    elif isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        lengths = _lengths(lengths, B, N, device)
+    else:
+        given = lengths
+        lengths = _lengths(given, B, N, device)                      # validated on the host (its errors come first), copied once
+        if n_rows is None:
+            n_rows = int((given.detach() if isinstance(given, torch.Tensor) else torch.as_tensor(given)).sum())
+    row_off, R = row_offsets(lengths, B, N, device, n_rows=n_rows)
+    return lengths, row_off, R, row_cloud(row_off, B, R)
+
+
+class _SegmentMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Y, row_off, row_cloud, B, scale, shift, slope, link):
+        Y = _dev(Y, "Y")
+        if Y.dim() != 2:
+            raise ValueError(f"segment_max: expected packed rows [R, C], got {tuple(Y.shape)}")
+        R, C = Y.shape
+        out = torch.empty((B, C), dtype=torch.float32, device=Y.device)
+        arg = torch.empty((B, C), dtype=torch.int32, device=Y.device)
+        _lib.call("pcl_bn_act_seg_max_f32", _p(Y), _p(row_off), _p(scale), _p(shift), float(slope), B, C, R, _p(out), _p(arg), _stream(),
+                  algo_bytes=4 * R * C)
+        ctx.link, ctx.slope, ctx.B = link, float(slope), B
+        ctx.save_for_backward(Y, arg, scale, shift, row_off, row_cloud)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        import ctypes
+        Y, arg, scale, shift, row_off, row_cloud = ctx.saved_tensors
+        R, C = Y.shape
+        if gout.is_cuda and gout.dtype == torch.float32 and gout.stride(1) == 1 and C <= gout.stride(0) < 2 ** 31:
+            ldg = gout.stride(0)                                       # a column slice of a wider gradient is read in place
+        else:
+            gout, ldg = _dev(gout, "grad"), C
+        du = torch.empty_like(Y)
+        stats = torch.empty((1024, 2, C), dtype=torch.float64, device=Y.device)
+        rows = ctypes.c_int(0)
+        _lib.call("pcl_bn_act_seg_max_bwd_f32", _p(gout), ldg, _p(arg), _p(Y), _p(scale), _p(shift), ctx.slope, _p(row_off), _p(row_cloud),
+                  ctx.B, C, R, _p(du), _p(stats), ctypes.byref(rows), _stream(), algo_bytes=8 * R * C)
+        if ctx.link is not None:
+            ctx.link.stats, ctx.link.rows = stats, rows.value
+        return du, None, None, None, None, None, None, None
+
+
+def segment_max(Y, row_off, row_cloud, B, scale=None, shift=None, slope=1.0, link=None):
+    """Max over each cloud's packed rows: Y [R, C] -> [B, C], ``out[b] = max_r lrelu(scale * Y[r] + shift, slope)`` over the rows
+    ``row_off[b] .. row_off[b+1] - 1`` (csrc/segpool.hip).  Two forms, as ``edgeconv.conv_max_mean_pool``:
+    ``link`` = the ``DeferLink`` of ``mlp_hip.stack_plain_deferred``: Y is that stack's PRE-BatchNorm output, scale / shift / slope
+    are the link's, and the backward hands the stack du and its BatchNorm-backward sums through the link;
+    otherwise Y is pooled as it is (scale 1, shift 0, slope 1 unless given: ``fmaf(1, y, 0)`` is exact, a plain segmented max) and
+    the gradient w.r.t. Y is the winner's, scale / shift being constants.  ``mlp_segment_max`` chooses between them."""
+    if link is not None:
+        scale, shift, slope = link.scale, link.shift, link.slope
+    elif scale is None or shift is None:
+        if scale is not None or shift is not None:
+            raise ValueError("segment_max: scale and shift come together")
+        from .mlp_hip import _unit_consts
+        scale, shift = _unit_consts(Y.device, Y.shape[-1])
+    if not 1 <= B <= 65535 or row_off.shape[0] != B + 1:
+        raise ValueError(f"segment_max: B={B} (1 .. 65535) with row_off {tuple(row_off.shape)}")
+    if row_cloud.shape[0] != Y.shape[0]:
+        raise ValueError(f"segment_max: row_cloud holds {row_cloud.shape[0]} rows, Y {Y.shape[0]}")
+    return _SegmentMax.apply(Y, _dev(row_off, "row_off", torch.int32), _dev(row_cloud, "row_cloud", torch.int32), int(B),
+                             _dev(scale, "scale"), _dev(shift, "shift"), float(slope), link)
+
+
+def mlp_segment_max(mlp, rows, row_off, row_cloud, B):
+    """``segment_max(mlp(rows))`` for a ``PointwiseMLP`` on packed rows [R, C0] -> [B, CL].  Training on the per-stack path: the
+    stack stops at its last pre-BatchNorm output and the pooling applies BatchNorm + activation while it reduces, so the activated
+    [R, CL] tensor is never written.  Otherwise (evaluation, synchronised BatchNorm, the per-kernel path): ``mlp(rows)``, pooled."""
+    from . import mlp_hip
+    if rows.is_cuda and rows.dtype == torch.float32 and mlp.resolved_backend(rows) == "hip" and mlp.last_act:
+        r = mlp_hip.stack_plain_deferred(mlp, rows.contiguous())
+        if r is not None:
+            return segment_max(r[0], row_off, row_cloud, B, link=r[1])
+    return segment_max(mlp(rows), row_off, row_cloud, B)
+
+
+class _BroadcastRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v, row_off, row_cloud, R):
+        v = _dev(v, "v")
+        B, C = v.shape
+        out = torch.empty((R, C), dtype=torch.float32, device=v.device)
+        _lib.call("pcl_seg_broadcast_rows_f32", _p(v), _p(row_cloud), B, C, R, _p(out), _stream(), algo_bytes=4 * R * C)
+        ctx.save_for_backward(row_off)
+        ctx.dims = (B, C, R)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        row_off, = ctx.saved_tensors
+        B, C, R = ctx.dims
+        g = _dev(g, "grad")
+        gv = torch.empty((B, C), dtype=torch.float32, device=g.device)
+        _lib.call("pcl_seg_sum_rows_f32", _p(g), _p(row_off), B, C, R, _p(gv), _stream(), algo_bytes=4 * R * C)
+        return gv, None, None, None
+
+
+def broadcast_rows(v, row_off, row_cloud, R):
+    """A per-cloud vector onto the cloud's packed rows: v [B, C] -> [R, C], row r = ``v[row_cloud[r]]``.  The gradient is the
+    per-cloud column sum (fp64, a fixed order: run-to-run identical)."""
+    if v.dim() != 2 or not 1 <= v.shape[0] <= 65535 or row_off.shape[0] != v.shape[0] + 1:
+        raise ValueError(f"broadcast_rows: expected v [B, C] with row_off [B+1], got {tuple(v.shape)} and {tuple(row_off.shape)}")
+    if row_cloud.shape[0] != int(R):
+        raise ValueError(f"broadcast_rows: row_cloud holds {row_cloud.shape[0]} rows, R = {R}")
+    return _BroadcastRows.apply(v, _dev(row_off, "row_off", torch.int32), _dev(row_cloud, "row_cloud", torch.int32), int(R))
 
 
 # ----------------------------------------------------------------------------- modules (reference names)

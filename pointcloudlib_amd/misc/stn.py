@@ -26,6 +26,17 @@ class STNkd(nn.Module):
         iden = torch.eye(k, device=x.device, dtype=x.dtype).reshape(1, k * k)
         return (t + iden).reshape(B, k, k)
 
+    def forward_packed(self, rows, row_off, row_cloud, B):
+        """The same transform from the packed rows of a ragged batch (``misc.ops.packed_layout``): rows [R,k]
+        -> [B,k,k], the max taken per cloud over its own rows."""
+        from .ops import mlp_segment_max
+        k = rows.shape[-1]
+        assert rows.dim() == 2 and k == self.k
+        g = mlp_segment_max(self.convs, rows, row_off, row_cloud, B)
+        t = self.fc3(self.fcs(g))
+        iden = torch.eye(k, device=rows.device, dtype=rows.dtype).reshape(1, k * k)
+        return (t + iden).reshape(B, k, k)
+
     def execute(self, *a, **k):
         return self(*a, **k)
 
