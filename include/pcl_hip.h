@@ -789,6 +789,17 @@ int pcl_sa_level_infer_f32(const float* xyz, const float* new_xyz, const float* 
                            const float* Wf_small, int CF, int ldw, const int32_t* idx, const int32_t* cnt, int B, int N, int m, int ns,
                            int L, const int32_t* widths, const float* const* W, const float* const* scale, const float* const* shift,
                            float slope, float* out, int ldo, int col0, void* stream);
+/* No reference counterpart: the same level with bf16 matrix operands (frozen(net, precision="bf16")).  Arguments, checks, the
+ * "no kernel" error and the contract of pcl_sa_level_infer_f32, except that W[l], l >= 1, are bf16 [C_l, C_{l-1}] dense, 16-byte
+ * aligned; Wx, Wf_small, Uf, scale and shift stay fp32.  Numerics: layer 1 is the fp32 expression of pcl_sa_level_infer_f32,
+ * its result z_1 rounded to nearest even to bf16; y_l (l >= 2) = bf16 x bf16 products accumulated in fp32
+ * (v_mfma_f32_32x32x16_bf16, k ascending); z_l = act(scale_l * y_l + shift_l) in fp32, rounded to bf16 for the next layer; z_L
+ * is never rounded, the max and out are fp32.  A group's result depends only on its own rows (not on B or its place in the
+ * launch); no atomics, run-to-run identical.  pcl_sa_level_infer_supported answers for both precisions. */
+int pcl_sa_level_infer_bf16_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, const float* feat_small,
+                                const float* Wf_small, int CF, int ldw, const int32_t* idx, const int32_t* cnt, int B, int N, int m,
+                                int ns, int L, const int32_t* widths, const void* const* W, const float* const* scale,
+                                const float* const* shift, float slope, float* out, int ldo, int col0, void* stream);
 
 /* ---- Frozen inference: one PointNet++ feature-propagation level in evaluation mode as ONE launch ------------------------
  * misc/ops.py:54-107 (PointNetFeaturePropagation.execute: 3-NN inverse-distance interpolation, concat with the skip features,

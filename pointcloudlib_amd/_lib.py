@@ -103,6 +103,8 @@ _SIGS = {
     "pcl_sa_level_infer_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "pcl_sa_level_infer_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P,
                                        c_float, _P, c_int, c_int, _P]),
+    "pcl_sa_level_infer_bf16_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P,
+                                            c_float, _P, c_int, c_int, _P]),
     "pcl_fp_level_infer_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "pcl_fp_level_infer_f32": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P,
                                        c_int, c_float, _P, c_int, _P, c_int, c_int, _P]),

@@ -15,6 +15,20 @@
 //      LDS).  The wave owns its columns for every tile: no atomics.
 // The k order inside a block of 8 is permuted (lane half h holds k = 8q + 4h + i at k-step 4q + i) identically for A and
 // B, so each lane moves 16-byte pieces; the sum is the same set of products in a different order.
+//
+// The bf16 instantiation (pcl_sa_level_infer_bf16_f32) is the same kernel with layers 2 and 3 on v_mfma_f32_32x32x16_bf16.
+// Its numerics:
+//   - layer 1 is the fp32 expression above, unchanged (the same fmaf chain, act(scale1 y1 + shift1)); the result is rounded
+//     to nearest even into a bf16 X1;
+//   - layers 2 and 3 are bf16 x bf16 products accumulated in fp32, k-blocks of 16 in ascending order; the epilogue
+//     act(scale y + shift) runs in fp32 as in the fp32 kernel; z2 is rounded to nearest even into a bf16 X2;
+//   - z3 is never rounded: the max per group is taken in fp32 registers and the output is fp32;
+//   - Uf stays fp32 (pcl_linear_fwd_rows_f32, stats-free); Wx, Wf_small, scale and shift stay fp32;
+//   - a group's result depends only on its own rows: not on B, on the group's place in the launch or on GT;
+//   - no atomics, run-to-run identical; rounding is the plain C++ conversion (v_cvt_pk_bf16_f32).
+// X1 / X2 are [64][C + 8] bf16 (infer_mfma.h), half the bytes of the fp32 tiles.
+#include <type_traits>
+
 #include "common.h"
 #include "infer_mfma.h"
 
@@ -25,6 +39,8 @@ using infer::act;
 using infer::f32x16;
 using infer::imax;
 using infer::mfma_layer;
+using infer::mfma_layer_bf16;
+using infer::bf16x4;
 
 constexpr int IF_T = 256;        // threads per workgroup (4 waves)
 constexpr int IF_RT = 64;        // rows per tile (two 32-row MFMA blocks)
@@ -42,25 +58,28 @@ struct InferArgs {
     float* out; int ldo, col0;
 };
 
-template <int C1, int C2, int C3>
+template <int C1, int C2, int C3, bool BF16>
 struct InferShape {
-    static constexpr int LD1 = C1 + 4, LD2 = C2 + 4;                       // +4 floats: ds_read_b128 rows on distinct banks
+    // +4 floats / +8 bf16 (one 16-byte piece): ds_read_b128 rows on distinct banks
+    static constexpr int LD1 = BF16 ? C1 + 8 : C1 + 4, LD2 = BF16 ? C2 + 8 : C2 + 4;
+    static constexpr int ESZ = BF16 ? 2 : 4;                               // bytes per element of X1 / X2
     static size_t lds_bytes(int GT) {
-        return 4 * ((size_t)IF_RT * LD1 + IF_RT * LD2 + (size_t)GT * C3) + 32 * IF_RT + 8 * IF_RT + 4 * (IF_MAXGT + 4);
+        return ESZ * ((size_t)IF_RT * LD1 + IF_RT * LD2) + 4 * (size_t)GT * C3 + 32 * IF_RT + 8 * IF_RT + 4 * (IF_MAXGT + 4);
     }
 };
 
-template <int C1, int C2, int C3>
+template <int C1, int C2, int C3, bool BF16>
 __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs a) {
-    using S = InferShape<C1, C2, C3>;
+    using S = InferShape<C1, C2, C3, BF16>;
+    using XT = std::conditional_t<BF16, __bf16, float>;                    // element of X1 / X2
     constexpr int LD1 = S::LD1, LD2 = S::LD2;
     constexpr int NCB2 = C2 / 32, NCB3 = C3 / 32;
     constexpr int NJ2 = (NCB2 + 3) / 4, NJ3 = (NCB3 + 3) / 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int GT = a.GT;
-    float* X1 = smem;                                       // [RT][LD1]
-    float* X2 = X1 + IF_RT * LD1;                           // [RT][LD2]
-    float* rmax = X2 + IF_RT * LD2;                         // [GT][C3]
+    XT* X1 = reinterpret_cast<XT*>(smem);                   // [RT][LD1]
+    XT* X2 = X1 + IF_RT * LD1;                              // [RT][LD2]
+    float* rmax = reinterpret_cast<float*>(X2 + IF_RT * LD2);             // [GT][C3]
     float4* rloc = reinterpret_cast<float4*>(rmax + (size_t)GT * C3);     // [RT]
     float4* rfeat = rloc + IF_RT;                           // [RT]
     int* rsrc = reinterpret_cast<int*>(rfeat + IF_RT);      // [RT]
@@ -134,13 +153,21 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
                 y = fmaf(wf[i][3], F.w, fmaf(wf[i][2], F.z, fmaf(wf[i][1], F.y, fmaf(wf[i][0], F.x, y))));
                 z[i] = act(sc1[i] * y + sh1[i], a.slope);
             }
-            *reinterpret_cast<float4*>(X1 + (size_t)r * LD1 + c4) = make_float4(z[0], z[1], z[2], z[3]);
+            if constexpr (BF16) {
+                bf16x4 zb;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) zb[i] = (__bf16)z[i];
+                *reinterpret_cast<bf16x4*>(X1 + (size_t)r * LD1 + c4) = zb;
+            } else {
+                *reinterpret_cast<float4*>(X1 + (size_t)r * LD1 + c4) = make_float4(z[0], z[1], z[2], z[3]);
+            }
         }
         __syncthreads();
         // 3. layer 2
         {
             f32x16 acc[2][NJ2];
-            mfma_layer<C1, LD1, NJ2, NCB2>(X1, a.W2, wave, lane, acc);
+            if constexpr (BF16) mfma_layer_bf16<C1, LD1, NJ2, NCB2>(X1, reinterpret_cast<const __bf16*>(a.W2), wave, lane, acc);
+            else mfma_layer<C1, LD1, NJ2, NCB2>(X1, a.W2, wave, lane, acc);
 #pragma unroll
             for (int j = 0; j < NJ2; ++j) {
                 const int cb = wave + 4 * j;
@@ -152,7 +179,7 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                            X2[(size_t)row * LD2 + col] = act(sc * acc[rb][j][r] + sh, a.slope);
+                            X2[(size_t)row * LD2 + col] = (XT)act(sc * acc[rb][j][r] + sh, a.slope);
                         }
                 }
             }
@@ -161,7 +188,8 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
         // 4. layer 3 + running max per group
         {
             f32x16 acc[2][NJ3];
-            mfma_layer<C2, LD2, NJ3, NCB3>(X2, a.W3, wave, lane, acc);
+            if constexpr (BF16) mfma_layer_bf16<C2, LD2, NJ3, NCB3>(X2, reinterpret_cast<const __bf16*>(a.W3), wave, lane, acc);
+            else mfma_layer<C2, LD2, NJ3, NCB3>(X2, a.W3, wave, lane, acc);
             // the groups of this tile occupy consecutive row ranges: one masked max per group over the lane's 32 rows, then
             // across the two lane halves (same column, interleaved rows)
             const int glo = rgrp[0], ghi = rgrp[nvalid - 1];
@@ -199,21 +227,21 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
     }
 }
 
-template <int C1, int C2, int C3>
-int launch_infer(InferArgs a, hipStream_t st) {
-    using S = InferShape<C1, C2, C3>;
+template <int C1, int C2, int C3, bool BF16>
+int launch_infer(const char* fn, InferArgs a, hipStream_t st) {
+    using S = InferShape<C1, C2, C3, BF16>;
     int GT = min(IF_MAXGT, max(1, 512 / a.ns));
     while (GT > 1 && S::lds_bytes(GT) > IF_LDS_CAP) --GT;
     a.GT = GT;
     const size_t lds = S::lds_bytes(GT);
-    auto kern = sa_level_infer_kernel<C1, C2, C3>;
+    auto kern = sa_level_infer_kernel<C1, C2, C3, BF16>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PCL_EHIP, "pcl_sa_level_infer_f32: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(PCL_EHIP, "%s: hipFuncSetAttribute(%zu): %s", fn, lds, hipGetErrorString(e));
     }
     const int blocks = (a.G + GT - 1) / GT;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(IF_T), lds, st, a);
-    return check_launch("pcl_sa_level_infer_f32");
+    return check_launch(fn);
 }
 
 // the widths after the fold that have a kernel: the SA levels of networks/cls/pointnet2.py (SSG and MSG)
@@ -237,40 +265,64 @@ extern "C" int pcl_sa_level_infer_supported(int ns, int L, int C1, int C2, int C
     return ns >= 1 && ns <= IF_MAXNS && L >= 1 && L <= 4 && infer_shape_id(L, w) >= 0;
 }
 
-extern "C" int pcl_sa_level_infer_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, const float* feat_small,
-                                      const float* Wf_small, int CF, int ldw, const int32_t* idx, const int32_t* cnt, int B, int N, int m,
-                                      int ns, int L, const int32_t* widths, const float* const* W, const float* const* scale,
-                                      const float* const* shift, float slope, float* out, int ldo, int col0, void* stream) {
-    PCL_REQUIRE(widths && W && scale && shift, "pcl_sa_level_infer_f32: null host array");
-    PCL_REQUIRE(L >= 1 && L <= 4, "pcl_sa_level_infer_f32: L=%d", L);
+namespace pcl {
+namespace {
+
+// both precisions: every check runs before any HIP call.  W[l], l >= 1: fp32 (BF16 false) or bf16 (true) [C_l][C_{l-1}]
+template <bool BF16>
+int sa_level_infer(const char* fn, const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, const float* feat_small,
+                   const float* Wf_small, int CF, int ldw, const int32_t* idx, const int32_t* cnt, int B, int N, int m, int ns, int L,
+                   const int32_t* widths, const void* const* W, const float* const* scale, const float* const* shift, float slope,
+                   float* out, int ldo, int col0, void* stream) {
+    PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", fn);
+    PCL_REQUIRE(L >= 1 && L <= 4, "%s: L=%d", fn, L);
     const int sid = infer_shape_id(L, widths);
     PCL_REQUIRE(sid >= 0 && ns >= 1 && ns <= IF_MAXNS,
-                "pcl_sa_level_infer_f32: no kernel for ns=%d L=%d widths %d/%d/%d (pcl_sa_level_infer_supported)", ns, L, widths[0],
+                "%s: no kernel for ns=%d L=%d widths %d/%d/%d (pcl_sa_level_infer_supported)", fn, ns, L, widths[0],
                 L > 1 ? widths[1] : 0, L > 2 ? widths[2] : 0);
-    PCL_REQUIRE(idx && cnt && out, "pcl_sa_level_infer_f32: null pointer");
-    PCL_REQUIRE(Uf || Wx || CF > 0, "pcl_sa_level_infer_f32: need features (Uf or feat_small) and/or coordinates (Wx)");
-    PCL_REQUIRE(CF >= 0 && CF <= 4 && (CF == 0 || (feat_small && Wf_small)), "pcl_sa_level_infer_f32: CF=%d inline features (<= 4)", CF);
-    PCL_REQUIRE(!Wx || (xyz && new_xyz), "pcl_sa_level_infer_f32: Wx needs xyz and new_xyz");
-    PCL_REQUIRE(ldw >= (Wx ? 3 : 0) && ldw >= CF, "pcl_sa_level_infer_f32: ldw=%d", ldw);
-    PCL_REQUIRE(B >= 1 && N >= 1 && m >= 1, "pcl_sa_level_infer_f32: bad sizes B=%d N=%d m=%d", B, N, m);
-    PCL_REQUIRE((size_t)B * m < (1u << 31) && (size_t)B * N < (1u << 31), "pcl_sa_level_infer_f32: too many groups / points");
-    for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "pcl_sa_level_infer_f32: layer %d: null pointer", l);
+    PCL_REQUIRE(idx && cnt && out, "%s: null pointer", fn);
+    PCL_REQUIRE(Uf || Wx || CF > 0, "%s: need features (Uf or feat_small) and/or coordinates (Wx)", fn);
+    PCL_REQUIRE(CF >= 0 && CF <= 4 && (CF == 0 || (feat_small && Wf_small)), "%s: CF=%d inline features (<= 4)", fn, CF);
+    PCL_REQUIRE(!Wx || (xyz && new_xyz), "%s: Wx needs xyz and new_xyz", fn);
+    PCL_REQUIRE(ldw >= (Wx ? 3 : 0) && ldw >= CF, "%s: ldw=%d", fn, ldw);
+    PCL_REQUIRE(B >= 1 && N >= 1 && m >= 1, "%s: bad sizes B=%d N=%d m=%d", fn, B, N, m);
+    PCL_REQUIRE((size_t)B * m < (1u << 31) && (size_t)B * N < (1u << 31), "%s: too many groups / points", fn);
+    for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", fn, l);
     const int CL = widths[L - 1];
-    PCL_REQUIRE(col0 >= 0 && ldo >= col0 + CL, "pcl_sa_level_infer_f32: ldo=%d col0=%d for %d channels", ldo, col0, CL);
+    PCL_REQUIRE(col0 >= 0 && ldo >= col0 + CL, "%s: ldo=%d col0=%d for %d channels", fn, ldo, col0, CL);
     bool al16 = (reinterpret_cast<uintptr_t>(Uf) & 15) == 0;
     for (int l = 1; l < L; ++l) al16 = al16 && (reinterpret_cast<uintptr_t>(W[l]) & 15) == 0;
-    PCL_REQUIRE(al16, "pcl_sa_level_infer_f32: Uf and the weights must be 16-byte aligned");
+    PCL_REQUIRE(al16, "%s: Uf and the weights must be 16-byte aligned", fn);
     InferArgs a = {};
     a.xyz = xyz; a.new_xyz = new_xyz; a.Uf = Uf; a.Wx = Wx; a.fs = feat_small; a.Wfs = Wf_small; a.CF = CF; a.ldw = ldw;
     a.idx = idx; a.cnt = cnt; a.G = B * m; a.N = N; a.m = m; a.ns = ns;
-    a.W2 = W[1]; a.W3 = W[2];
+    a.W2 = static_cast<const float*>(W[1]); a.W3 = static_cast<const float*>(W[2]);
     a.sc1 = scale[0]; a.sh1 = shift[0]; a.sc2 = scale[1]; a.sh2 = shift[1]; a.sc3 = scale[2]; a.sh3 = shift[2];
     a.slope = slope; a.out = out; a.ldo = ldo; a.col0 = col0;
     hipStream_t st = as_stream(stream);
     switch (sid) {
-        case 0: return launch_infer<32, 32, 64>(a, st);
-        case 1: return launch_infer<64, 64, 128>(a, st);
-        case 2: return launch_infer<64, 96, 128>(a, st);
-        default: return launch_infer<128, 128, 256>(a, st);
+        case 0: return launch_infer<32, 32, 64, BF16>(fn, a, st);
+        case 1: return launch_infer<64, 64, 128, BF16>(fn, a, st);
+        case 2: return launch_infer<64, 96, 128, BF16>(fn, a, st);
+        default: return launch_infer<128, 128, 256, BF16>(fn, a, st);
     }
+}
+
+}  // namespace
+}  // namespace pcl
+
+extern "C" int pcl_sa_level_infer_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, const float* feat_small,
+                                      const float* Wf_small, int CF, int ldw, const int32_t* idx, const int32_t* cnt, int B, int N, int m,
+                                      int ns, int L, const int32_t* widths, const float* const* W, const float* const* scale,
+                                      const float* const* shift, float slope, float* out, int ldo, int col0, void* stream) {
+    return sa_level_infer<false>("pcl_sa_level_infer_f32", xyz, new_xyz, Uf, Wx, feat_small, Wf_small, CF, ldw, idx, cnt, B, N, m, ns, L,
+                                 widths, reinterpret_cast<const void* const*>(W), scale, shift, slope, out, ldo, col0, stream);
+}
+
+extern "C" int pcl_sa_level_infer_bf16_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, const float* feat_small,
+                                           const float* Wf_small, int CF, int ldw, const int32_t* idx, const int32_t* cnt, int B, int N,
+                                           int m, int ns, int L, const int32_t* widths, const void* const* W, const float* const* scale,
+                                           const float* const* shift, float slope, float* out, int ldo, int col0, void* stream) {
+    return sa_level_infer<true>("pcl_sa_level_infer_bf16_f32", xyz, new_xyz, Uf, Wx, feat_small, Wf_small, CF, ldw, idx, cnt, B, N, m, ns,
+                                L, widths, W, scale, shift, slope, out, ldo, col0, stream);
 }

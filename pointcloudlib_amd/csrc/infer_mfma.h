@@ -6,6 +6,12 @@
 // (lane half h holds k = 8q + 4h + i at k-step 4q + i) identically for A and B, so each lane moves 16-byte pieces; the sum
 // is the same set of products in a different order.  Accumulator element r of lane (lr, lh) is row
 // rb*32 + (r & 3) + 8*(r >> 2) + 4*lh, column cb*32 + lr.
+//
+// mfma_layer_bf16 is the same step with bf16 operands (v_mfma_f32_32x32x16_bf16, fp32 accumulation): the tile and the weight
+// matrix hold bf16, lane (lr, lh) takes A[row lr][k = 16q + 8lh + j] and W[col lr][k = 16q + 8lh + j], j < 8, as one 16-byte
+// piece each at k-block q; the k-blocks run in ascending order and no k permutation is needed.  Same ownership, same
+// accumulator map.  LDX = K + 8: rows of (2K + 16) bytes, an odd number of 16-byte pieces, so the 16-byte reads of
+// consecutive rows fall on distinct banks, and every row stays 16-byte aligned.
 #pragma once
 #include "common.h"
 
@@ -62,6 +68,54 @@ __device__ __forceinline__ void mfma_layer(const float* __restrict__ X, const fl
                 acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b[j].z, acc[1][j], 0, 0, 0);
                 acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b[j].w, acc[0][j], 0, 0, 0);
                 acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b[j].w, acc[1][j], 0, 0, 0);
+            }
+        }
+    }
+}
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+// acc[rb][j] += X[rb*32 + row][k] * W[(w + 4j)*32 + col][k] over k < K, bf16 products accumulated in fp32 (X in LDS with row
+// stride LDX elements, W [*, K] bf16 in global memory)
+template <int K, int LDX, int NJ, int NCB>
+__device__ __forceinline__ void mfma_layer_bf16(const __bf16* __restrict__ X, const __bf16* __restrict__ W, int wave, int lane,
+                                                f32x16 (&acc)[2][NJ]) {
+    static_assert(K % 16 == 0 && LDX % 8 == 0, "16-byte pieces");
+    const int lr = lane & 31, lh = lane >> 5;
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[rb][j][r] = 0.f;
+    const __bf16* xa0 = X + (size_t)lr * LDX + 8 * lh;
+    const __bf16* xa1 = X + (size_t)(32 + lr) * LDX + 8 * lh;
+    const __bf16* wb[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int cb = imax(0, wave + 4 * j < NCB ? wave + 4 * j : 0);
+        wb[j] = W + (size_t)(cb * 32 + lr) * K + 8 * lh;
+    }
+    bf16x8 bn[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) bn[j] = *reinterpret_cast<const bf16x8*>(wb[j]);
+#pragma unroll
+    for (int q = 0; q < K / 16; ++q) {
+        bf16x8 b[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) b[j] = bn[j];
+        if (q + 1 < K / 16) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) bn[j] = *reinterpret_cast<const bf16x8*>(wb[j] + 16 * (q + 1));
+        }
+        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(xa0 + 16 * q);
+        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(xa1 + 16 * q);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (wave + 4 * j < NCB) {
+                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b[j], acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b[j], acc[1][j], 0, 0, 0);
             }
         }
     }

@@ -14,7 +14,11 @@ The part-seg networks (``PointNet2_partseg`` / its ``PointNetMSG``) share that e
 the stats-free GEMMs of its folded first layer (``Uc = coarse W0c^T`` at the coarse resolution, ``Us = skip W0s^T`` per point, or
 the skip inline when it is narrow; the one-hot class label as a per-cloud bias) and then ONE ``pcl_fp_level_infer_f32`` launch.
 The last level carries the head (Conv1d + BN, Dropout = identity, Conv1d) in the same launch, which also stores the level's own
-output (the tap).  FP levels and heads of other widths run eval-mode copies of their own modules."""
+output (the tap).  FP levels and heads of other widths run eval-mode copies of their own modules.
+
+``frozen(net, precision="bf16")`` runs every fused set-abstraction launch as ``pcl_sa_level_infer_bf16_f32``: layers 2 and up
+take bf16 operands (activations rounded to nearest even, weights snapshot as bf16 once) and accumulate in fp32; the first layer,
+``Uf``, the epilogues, the max and every output stay fp32, and so do the GroupAll level, the FP levels and the heads."""
 import copy
 import ctypes
 
@@ -29,16 +33,22 @@ from .networks.seg.pointnet2_partseg import PointNet2_partseg
 __all__ = ["frozen", "FrozenPointNet2", "FrozenPointNet2Partseg"]
 
 
-def frozen(net):
+PRECISIONS = ("fp32", "bf16")
+
+
+def frozen(net, precision="fp32"):
     """A frozen evaluator of ``net``: ``PointNet2_cls`` or ``PointNetMSG`` (classification) -> ``fnet(xyz, feature, sampling=None,
     lengths=None) -> [B, n_classes]``; ``PointNet2_partseg`` or its ``PointNetMSG`` (part segmentation) -> ``fnet(xyz, feature,
     cls_label, sampling=None, lengths=None) -> [B, part_num, N]``.  ``lengths`` [B]: per-cloud point counts of a ragged batch
     (capacity N; rows from lengths[b] on are pad rows, any contents): every cloud's result is that of the cloud alone; the
-    part-seg logits and ``fp1`` feature of pad points are exact zeros."""
+    part-seg logits and ``fp1`` feature of pad points are exact zeros.  ``precision``: "fp32", or "bf16" for bf16 matrix operands
+    in the fused set-abstraction launches (module docstring); ``fnet.precision`` tells which."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"frozen(): precision must be one of {PRECISIONS}, got {precision!r}")
     if isinstance(net, PointNet2_cls):
-        return FrozenPointNet2(net)
+        return FrozenPointNet2(net, precision)
     if isinstance(net, PointNet2_partseg):
-        return FrozenPointNet2Partseg(net)
+        return FrozenPointNet2Partseg(net, precision)
     raise TypeError(f"frozen() takes PointNet2_cls or PointNetMSG (PointNet++ classification) or PointNet2_partseg / its PointNetMSG "
                     f"(PointNet++ part segmentation), got {type(net).__name__}")
 
@@ -58,9 +68,10 @@ def _eval_consts(mlp, l):
 
 
 class _Fused:
-    """Snapshot of one ball-query scale for pcl_sa_level_infer_f32."""
+    """Snapshot of one ball-query scale for pcl_sa_level_infer_f32 (or, ``precision="bf16"``, pcl_sa_level_infer_bf16_f32)."""
 
-    def __init__(self, mlp, use_xyz, C):
+    def __init__(self, mlp, use_xyz, C, precision="fp32"):
+        self.precision = precision
         W0 = mlp.weights[0].detach().float().contiguous().clone()
         self.use_xyz, self.C, self.slope = use_xyz, C, float(mlp.slope)
         off = 3 if use_xyz else 0
@@ -78,6 +89,11 @@ class _Fused:
         self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in self.Ws])
         self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
         self.c_shift = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.shifts])
+        self.entry = "pcl_sa_level_infer_f32"
+        if precision == "bf16":                                        # the bf16 operands of layers 2 and up, rounded once here
+            self.Ws_bf16 = [None] + [w.to(torch.bfloat16).contiguous() for w in self.Ws[1:]]
+            self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in self.Ws_bf16])
+            self.entry = "pcl_sa_level_infer_bf16_f32"
 
     def run(self, xyz, new_xyz, feature, idx, cnt, out, col0):
         B, N, _ = xyz.shape
@@ -90,7 +106,7 @@ class _Fused:
             Uf = torch.empty((B * N, C1), dtype=torch.float32, device=xyz.device)
             _lib.call("pcl_linear_fwd_rows_f32", _p(feat2), _p(self.Wf), None, None, None, 0.0, B * N, self.C, C1, _p(Uf), None, None, None,
                       st, tag=f"pt{self.C}x{C1}")
-        _lib.call("pcl_sa_level_infer_f32", _p(xyz), _p(new_xyz), _p(Uf), _p(self.Wx), _p(feat2) if self.inline else None,
+        _lib.call(self.entry, _p(xyz), _p(new_xyz), _p(Uf), _p(self.Wx), _p(feat2) if self.inline else None,
                   _p(self.Wf) if self.inline else None, self.C if self.inline else 0, self.ldw, _p(idx), _p(cnt), B, N, m, ns,
                   len(self.widths), self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(out), out.shape[-1], col0, st)
 
@@ -136,8 +152,9 @@ class _FrozenEncoder:
     """The set-abstraction levels of a PointNet++ network (``net.pointnet_modules``, input feature 3 wide): a plan per level and
     scale, and the eval-mode copies of modules without a fused kernel.  Shared by the classification and part-seg evaluators."""
 
-    def __init__(self, net):
+    def __init__(self, net, precision="fp32"):
         self.net = net
+        self.precision = precision
         self._copies = {}          # eval-mode copies of the heads and of levels without a fused kernel, kept across refresh()
         self.refresh()
 
@@ -160,7 +177,7 @@ class _FrozenEncoder:
                 if module.n_points is None:
                     plans.append(("all", _GroupAllPlan(mlp, use_xyz)))
                 elif _fusable(mlp, use_xyz, C, grouper.n_samples):
-                    plans.append(("fused", _Fused(mlp, use_xyz, C)))
+                    plans.append(("fused", _Fused(mlp, use_xyz, C, self.precision)))
                 else:
                     plans.append(("module", self._copy((i, j), mlp)))
             self.levels.append(plans)

@@ -8,6 +8,11 @@ compare three forms: ``eval`` (the network's default accumulation, fp64 flush ev
 ``set_accumulation(copy, 0)``: plain fp32 chains) and ``frozen``.
 
     python tools/bench_infer.py [--windows 7] [--iters 5] [--warmup 3] [--batch 32 256] [--nets ssg msg] [--points 1024]
+                                [--precision fp32 bf16]
+
+``--precision fp32 bf16`` adds ``frozen(net, precision="bf16")`` as one more form of every row (``frozen_bf16_*``; in the same
+interleaved windows, the same estimator), its ratio to the fp32 frozen form, the top-1 agreement of the two over the batch, and
+writes the JSON line to profiles/infer_bf16_bench_line.json as well.
 
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
@@ -47,7 +52,7 @@ def _peak(fn):
     return torch.cuda.max_memory_allocated() - base
 
 
-def _ragged_case(kind, fnet, xyz, nrm, extra, a):
+def _ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16=None):
     """The four forms of --ragged for one net and batch (same window estimator as the dense rows)."""
     import numpy as np
     B, N, _ = xyz.shape
@@ -63,6 +68,8 @@ def _ragged_case(kind, fnet, xyz, nrm, extra, a):
 
     forms = [("dense", lambda: fnet(xyz, nrm, *extra)), ("ragged_full", lambda: fnet(xyz, nrm, *extra, lengths=full)),
              ("ragged", lambda: fnet(xyz, nrm, *extra, lengths=drawn)), ("loop", loop)]
+    if fnet_bf16 is not None:
+        forms += [("dense_bf16", lambda: fnet_bf16(xyz, nrm, *extra)), ("ragged_bf16", lambda: fnet_bf16(xyz, nrm, *extra, lengths=drawn))]
     for _ in range(a.warmup):
         for _, fn in forms:
             fn()
@@ -80,6 +87,9 @@ def _ragged_case(kind, fnet, xyz, nrm, extra, a):
     case["ragged_full_vs_dense"] = round(case["ragged_full_ms"] / case["dense_ms"], 4)
     case["ragged_vs_dense"] = round(case["ragged_ms"] / case["dense_ms"], 4)
     case["loop_vs_ragged"] = round(case["loop_ms"] / case["ragged_ms"], 2)
+    if fnet_bf16 is not None:
+        case["dense_bf16_vs_fp32"] = round(case["dense_bf16_ms"] / case["dense_ms"], 4)
+        case["ragged_bf16_vs_fp32"] = round(case["ragged_bf16_ms"] / case["ragged_ms"], 4)
     return case
 
 
@@ -92,6 +102,8 @@ def main():
     ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg"])
     ap.add_argument("--points", type=int, default=None, help="default: 1024 (cls), 2048 (part-seg)")
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
+    ap.add_argument("--precision", nargs="+", default=["fp32"], choices=["fp32", "bf16"],
+                    help="fp32 bf16: frozen(net, precision='bf16') as one more form of every row")
     ap.add_argument("--ragged", action="store_true", help="ragged batches: dense / ragged at full length / ragged / per-cloud loop")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -116,6 +128,7 @@ def main():
         else:
             net = (PointNet2_cls if kind == "ssg" else PointNetMSG)().to(dev).eval()
         fnet = frozen(net)
+        fnet_bf16 = frozen(net, precision="bf16") if "bf16" in a.precision else None
         for B in a.batch or ([16, 64] if seg else [32, 256]):
             xyz = torch.from_numpy(synth.gauss_ball(B, N, 1)).to(dev)
             nrm = torch.from_numpy(synth.unit_normals(B, N, 2)).to(dev)
@@ -133,7 +146,7 @@ def main():
                 return fnet(xyz, nrm, *extra)
 
             if a.ragged:
-                res["cases"].append(_ragged_case(kind, fnet, xyz, nrm, extra, a))
+                res["cases"].append(_ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16))
                 continue
             if a.frozen_only:
                 forms = [("frozen", frozen_fwd)]
@@ -141,6 +154,8 @@ def main():
                 forms = [("eval", eval_fwd), ("eval_acc0", lambda: eval_fwd(net0)), ("frozen", frozen_fwd)]
             else:
                 forms = [("eval", eval_fwd), ("frozen", frozen_fwd)]
+            if fnet_bf16 is not None:
+                forms.append(("frozen_bf16", lambda: fnet_bf16(xyz, nrm, *extra)))
             for _ in range(a.warmup):
                 for _, fn in forms:
                     fn()
@@ -152,6 +167,8 @@ def main():
             for name, fn in forms:
                 case[f"{name}_ms"] = round(statistics.median(times[name]), 4)
                 case[f"{name}_ms_min"] = round(min(times[name]), 4)
+                if fnet_bf16 is not None:
+                    case[f"{name}_ms_max"] = round(max(times[name]), 4)
                 case[f"{name}_peak_mib"] = round(_peak(fn) / 2**20, 1)
             if not a.frozen_only:
                 case["speedup"] = round(case["eval_ms"] / case["frozen_ms"], 3)
@@ -160,8 +177,18 @@ def main():
                     case["mem_ratio"] = round(case["eval_peak_mib"] / max(case["frozen_peak_mib"], 0.1), 1)
                 with torch.no_grad():
                     case["max_abs_logit_diff"] = float((eval_fwd() - frozen_fwd()).abs().max())
+            if fnet_bf16 is not None:
+                case["bf16_vs_fp32"] = round(case["frozen_bf16_ms"] / case["frozen_ms"], 4)
+                case["bf16_below_fp32_min"] = case["frozen_bf16_ms"] < case["frozen_ms_min"]
+                lf, lb = frozen_fwd(), fnet_bf16(xyz, nrm, *extra)
+                case["max_abs_logit_diff_bf16_fp32"] = float((lf - lb).abs().max())
+                case["top1_agreement_bf16_fp32"] = float((lf.argmax(1) == lb.argmax(1)).float().mean())
             res["cases"].append(case)
     print(json.dumps(res))
+    if "bf16" in a.precision and not a.ragged:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "infer_bf16_bench_line.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
     if a.ragged:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "infer_ragged_bench_line.json"), "w") as f:
