@@ -34,173 +34,103 @@ def build(verbose=False):
     return _SO
 
 
+# ---------------------------------------------------------------- the C ABI, read from include/pcl_hip.h
+# The header is the one definition of the ABI (the compiler holds every .hip file to it).  The ctypes signatures and the
+# descriptor structs are derived from its text, once, at import; tests/test_abi_cpu.py holds this parser to the host compiler.
+_SCALAR = {"int": c_int, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
+           "uint64_t": ctypes.c_uint64, "float": c_float, "double": c_double, "size_t": c_size_t}
+_DECL = re.compile(r"(const\s+)?(\w+)((?:\s*\*\s*(?:const\b)?)*)\s*(\w+)?\s*(?:\[([^\]]*)\])?\s*$")
+_TOP = re.compile(r"""\s*(?: extern\s+"C"\s*\{ | \}
+                         | typedef\s+struct\s+\w*\s*\{ (?P<body>[^{}]*) \}\s*(?P<sname>\w+)\s*;
+                         | (?P<ret>[\w\s*]+?) \b(?P<fname>\w+)\s*\( (?P<params>[^;{}]*) \)\s*; )""", re.X)
+
+
+def parse_abi(text, origin=_HEADER):
+    """The declarations of an ABI header -> ({function: (restype, [argtypes])}, {struct: ctypes.Structure}, {macro: int}).
+
+    Every pointer is ``c_void_p`` except ``const char*`` (``c_char_p``).  Strict: text that is no function declaration,
+    ``typedef struct``, preprocessor line or ``extern "C"`` bracket raises, and so does a type outside ``_SCALAR``."""
+    def fail(where, what):
+        raise PclError(f"{origin}: {where}: {what}")
+
+    def declarator(decl, where):                   # ``const float* const* W`` | ``int32_t c[PCL_N + 1]`` -> (name, type | None for void)
+        m = None if "(" in decl or ":" in decl else _DECL.match(decl.strip())
+        if m is None:
+            fail(where, f"cannot type `{decl.strip()}` (function pointers and bit-fields are not part of the ABI)")
+        const, base, stars, name, dim = m.groups()
+        if stars:
+            if base not in _SCALAR and base not in structs and base not in ("void", "char"):
+                fail(where, f"unknown type `{base}`")
+            t = ctypes.c_char_p if const and base == "char" and stars.strip() == "*" else c_void_p
+        elif base == "void":
+            t = None
+        else:
+            t = _SCALAR.get(base) or structs.get(base) or fail(where, f"unknown type `{base}`")
+        if dim is not None:
+            try:
+                t = t * sum(int(x) if x.strip().isdigit() else defines[x.strip()] for x in dim.split("+"))
+            except (KeyError, TypeError):
+                fail(where, f"cannot size `{decl.strip()}`")
+        return name, t
+
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    defines = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)}
+    loose = set(re.findall(r"\b(pcl_[a-z0-9_]+)\s*\(", text))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    sigs, structs, pos = {}, {}, 0
+    while text[pos:].strip():
+        m = _TOP.match(text, pos)
+        if m is None:
+            fail("declaration", f"cannot parse `{' '.join(text[pos:].split())[:100]}`")
+        pos = m.end()
+        if m["sname"]:
+            fields = []
+            for stmt in filter(str.strip, m["body"].split(";")):           # ``int32_t K, N, bn_mode`` repeats the base type
+                first, *more = stmt.split(",")
+                base = re.match(r"\s*(?:const\s+)?\w*", first)[0]
+                for decl in [first] + [f"{base} {d}" for d in more]:
+                    name, t = declarator(decl, m["sname"])
+                    if name is None or t is None:
+                        fail(m["sname"], f"`{decl.strip()}` is no field")
+                    fields.append((name, t))
+            structs[m["sname"]] = type(m["sname"], (ctypes.Structure,), {"_fields_": fields})
+        elif m["fname"]:
+            args = []
+            for decl in [] if m["params"].strip() in ("", "void") else m["params"].split(","):
+                t = declarator(decl, m["fname"])[1]
+                if t is None or issubclass(t, (ctypes.Structure, ctypes.Array)):
+                    fail(m["fname"], f"`{decl.strip()}` is neither a scalar nor a pointer")
+                args.append(t)
+            sigs[m["fname"]] = (declarator(m["ret"], m["fname"])[1], args)
+    if loose != set(sigs):
+        fail("declaration", f"the grammar missed or misread {sorted(loose ^ set(sigs))}")
+    return sigs, structs, defines
+
+
+def _read_header():
+    try:
+        with open(_HEADER) as f:
+            return f.read()
+    except OSError as e:
+        raise PclError(f"{_HEADER} is needed at run time (the ctypes signatures are derived from it): {e}") from None
+
+
+_SIGS, _STRUCTS, _DEFINES = parse_abi(_read_header())
+
+
 def declared_symbols():
     """Every function name ``include/pcl_hip.h`` declares (used by the symbol-export test)."""
-    txt = open(_HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(pcl_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(_SIGS)
 
 
-_P = c_void_p
-_SIGS = {
-    "pcl_version": (c_int, []),
-    "pcl_time_next_launch": (None, [_P, _P]),
-    "pcl_time_tagged_launch": (None, [_P, _P, ctypes.c_char_p]),
-    "pcl_last_launch_kernel": (ctypes.c_char_p, []),
-    "pcl_mlp_stack_sizes": (c_int, [_P, _P, _P, _P]),
-    "pcl_mlp_stack_last": (c_int, [_P, _P, _P, _P]),
-    "pcl_pointconv_contract_bn_f32": (c_int, [_P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_pointconv_contract_bn_stat_rows": (c_int, [c_int]),
-    "pcl_pointconv_contract_bn_bwd_f32": (c_int, [_P, _P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-    "pcl_mlp_stack_fwd_f32": (c_int, [_P]),
-    "pcl_mlp_stack_bwd_f32": (c_int, [_P]),
-    "pcl_bn_rows_stats_f32": (c_int, [_P, _P, c_int, c_int, _P, ctypes.POINTER(c_int), _P]),
-    "pcl_bn_rows_bwd_apply_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
-    "pcl_fc_head_sizes": (c_int, [_P, _P, _P]),
-    "pcl_fc_head_fwd_f32": (c_int, [_P]),
-    "pcl_fc_head_bwd_f32": (c_int, [_P]),
-    "pcl_xconv_core_supported": (c_int, [c_int, c_int, c_int]),
-    "pcl_xconv_core_partials": (c_int, [c_int, c_int]),
-    "pcl_xconv_core_fwd_f32": (c_int, [_P, _P, c_int, _P, c_int, _P, _P, c_int, c_int, c_int, _P, _P]),
-    "pcl_xconv_core_bwd_f32": (c_int, [_P, _P, c_int, _P, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
-    "pcl_last_error": (ctypes.c_char_p, []),
-    "pcl_optimal_block": (c_int, [c_int]),
-    "pcl_fps_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_double, _P, _P, _P, _P]),
-    "pcl_fps_ragged_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_double, _P, _P, _P, _P]),
-    "pcl_ball_query_ragged_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P]),
-    "pcl_ball_query_multi_ragged_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-    "pcl_three_nn_ragged_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
-    "pcl_fp_level_infer_ragged_f32": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P,
-                                              c_int, c_float, _P, c_int, _P, c_int, c_int, _P]),
-    "pcl_row_offsets_i32": (c_int, [_P, c_int, c_int, _P, _P]),
-    "pcl_fp_pack_rows_f32": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_fp_pack_rows_bwd_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "pcl_pack_rows_b32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_unpack_rows_b32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_row_cloud_i32": (c_int, [_P, c_int, c_int, _P, _P]),
-    "pcl_bn_act_seg_max_f32": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P]),
-    "pcl_bn_act_seg_max_bwd_f32": (c_int, [_P, c_int, _P, _P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, _P, _P, ctypes.POINTER(c_int), _P]),
-    "pcl_seg_broadcast_rows_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
-    "pcl_seg_sum_rows_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
-    "pcl_ball_query_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P]),
-    "pcl_ball_query_multi_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-    "pcl_group_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_group_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_group_all_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_group_all_bwd_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_gather_rows_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_gather_rows_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_edge_feature_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_edge_feature_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "pcl_knn_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
-    "pcl_knn_fma_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
-    "pcl_knn_point_matmul_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_three_nn_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
-    "pcl_three_interp_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_three_interp_bwd_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_density_f32": (c_int, [_P, c_int, c_int, c_float, _P, _P]),
-    "pcl_sa_level_infer_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "pcl_sa_level_infer_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P,
-                                       c_float, _P, c_int, c_int, _P]),
-    "pcl_sa_level_infer_bf16_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P,
-                                            c_float, _P, c_int, c_int, _P]),
-    "pcl_fp_level_infer_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "pcl_fp_level_infer_f32": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P,
-                                       c_int, c_float, _P, c_int, _P, c_int, c_int, _P]),
-    "pcl_group_linear_stat_rows": (c_int, [c_int, c_int]),
-    "pcl_group_linear_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "pcl_group_linear_bwd_f32": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int, _P]),
-    "pcl_group_rows_transpose_supported": (c_int, [c_int, c_int, c_int]),
-    "pcl_group_rows_transpose_i32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "pcl_group_linear_bwd_gather_supported": (c_int, [c_int]),
-    "pcl_set_scatter_form": (None, [c_int]),
-    "pcl_set_pointconv_paths": (None, [c_int]),
-    "pcl_group_linear_bwd_gather_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_int, _P]),
-    "pcl_head_layer_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "pcl_head_layer_fwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "pcl_head_layer_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P, _P]),
-    "pcl_soft_ce_f32": (c_int, [_P, _P, c_float, c_int, c_int, _P, _P, _P]),
-    "pcl_soft_ce_rows_blocks": (c_int, [c_int]),
-    "pcl_soft_ce_rows_f32": (c_int, [_P, _P, c_float, c_int, c_int, _P, _P, _P, _P]),
-    "pcl_edgeconv_stat_rows": (c_int, [c_int, c_int]),
-    "pcl_edgeconv_wcat_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
-    "pcl_edgeconv_gather_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "pcl_edgeconv_gather_hilo_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "pcl_edgeconv_scatter_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-    "pcl_knn_transpose_i32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
-    "pcl_pointconv_contract_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_pointconv_contract_bwd_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcl_mlp_stat_rows": (c_int, [c_int, c_int, c_int]),
-    "pcl_linear_fwd_f32": (c_int, [_P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P]),
-    "pcl_linear_fwd_gmax_f32": (c_int, [_P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "pcl_group_minmax_finalize_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_int, c_int, _P, _P, _P, _P]),
-    "pcl_group_minmax_finalize2_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
-    "pcl_group_minmax_finalize_t_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P]),
-    "pcl_bn_finalize_f32": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P, _P]),
-    "pcl_bn_act_max_f32": (c_int, [_P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcl_bn_act_f32": (c_int, [_P, _P, _P, c_float, c_int, c_int, _P, _P]),
-    "pcl_bn_act_bwd_f32": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, _P, _P, ctypes.POINTER(c_int), _P]),
-    "pcl_bn_act_max_mean_f32": (c_int, [_P, _P, _P, c_float, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcl_bn_act_max_mean_bwd_f32": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, ctypes.POINTER(c_int), _P]),
-    "pcl_maxgrad_prep_f32": (c_int, [_P, _P, _P, c_float, c_int, c_int, _P, _P, ctypes.POINTER(c_int), _P]),
-    "pcl_bn_bwd_consts_f32": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "pcl_linear_bwd_dx_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_float,
-                                      _P, _P, _P]),
-    "pcl_group_offsets_i32": (c_int, [_P, c_int, _P, _P]),
-    "pcl_group_offsets_multi_i32": (c_int, [c_int, _P, c_int, _P, _P]),
-    "pcl_group_compact_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcl_linear_fwd_rows_f32": (c_int, [_P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-    "pcl_bn_act_max_rows_f32": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, _P, _P, _P, _P]),
-    "pcl_linear_bwd_dx_rows_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_float,
-                                           _P, _P, _P, _P, c_int, c_int, _P]),
-    "pcl_linear_bwd_dw_rows_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_float, c_int, c_int, c_int, _P,
-                                           _P, c_size_t, _P, _P, c_int, _P]),
-    "pcl_scatter_rows_add_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_linear_bwd_dw_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "pcl_frag_stat_rows": (c_int, [c_int]),
-    "pcl_frag_max_rows": (c_int, []),
-    "pcl_frag_set_tuning": (None, [c_int] * 7),
-    "pcl_frag_linear_fwd_f32": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_float, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P]),
-    "pcl_frag_dy_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, _P]),
-    "pcl_frag_linear_bwd_dx_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_float, _P, c_int, _P, c_int, _P]),
-    "pcl_frag_dw_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "pcl_frag_dw_counter_words": (c_int, [c_int, c_int, c_int]),
-    "pcl_frag_linear_bwd_dw_f32": (c_int, [_P, _P, c_int, _P, _P, c_float, c_int, c_int, c_int, _P, c_int, _P, c_size_t, c_int, _P]),
-    "pcl_set_fb_max_blocks": (None, [c_int]),
-    "pcl_set_fb_two_images": (None, [c_int]),
-    "pcl_get_fb_two_images": (c_int, []),
-    "pcl_set_kernel_paths": (None, [c_int, c_int, c_int]),
-    "pcl_sgd_momentum_f32": (c_int, [_P, _P, _P, _P, c_int, c_double, c_double, c_double, c_double, _P]),
-    "pcl_set_stack_overlap": (None, [c_int, c_int]),
-    "pcl_get_stack_overlap": (c_int, []),
-    "pcl_bn_bwd_dy_supported": (c_int, [c_int, c_int]),
-    "pcl_bn_bwd_dy_f32": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
-    "pcl_linear_bwd_dw_plain_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "pcl_linear_bwd_dw_plain_f32": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, c_size_t, c_int, _P]),
-    "pcl_mlp_fewrow_layer": (c_int, [c_int, c_int, c_int, c_int]),
-    "pcl_set_fewrow_backward": (None, [c_int]),
-    "pcl_get_fewrow_backward": (c_int, []),
-    "pcl_set_dw_tuning": (None, [c_int]),
-    "pcl_knn_nk_supported": (c_int, [c_int]),
-    "pcl_knn_nk_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcl_linear_bwd_pair_supported": (c_int, [c_int, c_int, c_int, c_int]),
-    "pcl_linear_bwd_pair_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, c_float, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_size_t, _P]),
-    "pcl_linear_bwd_pair_finish_f32": (c_int, [_P, c_size_t, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "pcl_set_bwd_pair": (None, [c_int]),
-    "pcl_get_bwd_pair": (c_int, []),
-    "pcl_set_matrix_form": (None, [c_int]),
-    "pcl_get_matrix_form": (c_int, []),
-    "pcl_set_fps_tuning": (None, [c_int, c_int]),
-    "pcl_linear_bwd_fused_supported": (c_int, [c_int, c_int]),
-    "pcl_linear_bwd_fused_stat_rows": (c_int, [c_int, c_int]),
-    "pcl_linear_bwd_fused_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "pcl_linear_bwd_fused_rows_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_float,
-                                               _P, _P, _P, c_size_t, _P, _P, _P]),
-    "pcl_linear_bwd_fused_finish_f32": (c_int, [_P, c_size_t, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "pcl_linear_bwd_dw_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_float, c_int, c_int, c_int, _P,
-                                      _P, c_size_t, _P]),
-}
+def struct(name):
+    """The ``ctypes.Structure`` of a ``typedef struct`` of the header (one class object per name)."""
+    return _STRUCTS[name]
+
+
+def define(name):
+    """An integer ``#define`` of the header (``PCL_STACK_MAX_LAYERS``, ...)."""
+    return _DEFINES[name]
 
 
 def lib():

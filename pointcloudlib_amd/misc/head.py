@@ -17,7 +17,7 @@ from .ops import _p, _stream
 
 MAX_ROWS = 64
 USE_STACK = os.environ.get("PCL_STACK", "1") != "0"       # the whole head as one C call per direction (pcl_fc_head_*_f32)
-_MAXL = 4
+_MAXL = _lib.define("PCL_HEAD_MAX_LAYERS")
 
 
 class _HeadLayer(torch.autograd.Function):
@@ -100,17 +100,8 @@ def head_layer(x, linear, bn=None, act=None):
     return _HeadLayer.apply(x, linear.weight, linear.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, cfg)
 
 
-class _CHeadLayer(ctypes.Structure):
-    _fields_ = ([(n, ctypes.c_void_p) for n in ("W", "bias", "gamma", "beta", "running_mean", "running_var", "dW", "dbias", "dgamma", "dbeta")]
-                + [(n, ctypes.c_int32) for n in ("K", "N", "bn_mode")] + [(n, ctypes.c_float) for n in ("eps", "momentum", "slope", "drop_p")]
-                + [("pad_", ctypes.c_int32)])
-
-
-class _CHead(ctypes.Structure):
-    _fields_ = [("struct_bytes", ctypes.c_int32), ("n_layers", ctypes.c_int32), ("R", ctypes.c_int32), ("pad_", ctypes.c_int32),
-                ("seed", ctypes.c_uint64), ("x", ctypes.c_void_p), ("layer", _CHeadLayer * _MAXL), ("out", ctypes.c_void_p),
-                ("save", ctypes.c_void_p), ("save_bytes", ctypes.c_size_t), ("tmp", ctypes.c_void_p), ("tmp_bytes", ctypes.c_size_t),
-                ("gout", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
+_CHeadLayer = _lib.struct("pcl_head_layer_t")
+_CHead = _lib.struct("pcl_fc_head_t")
 
 
 class _HeadPlan:

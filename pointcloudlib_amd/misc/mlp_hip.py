@@ -599,27 +599,13 @@ def grouped_mlp(module, xyz, new_xyz, feature, idx, cnt, group_off, use_xyz):
 # persistent + one transient buffer, one autograd node.  Eligible: training-mode BatchNorm on every layer with
 # process-local statistics; anything else (evaluation mode, SyncBN, bn=False, zero-padded input rows) keeps the path above.
 USE_STACK = os.environ.get("PCL_STACK", "1") != "0"
-_MAXL = 8
-
-
-class _CLayer(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("W", "bias", "gamma", "beta", "running_mean", "running_var", "dW", "dbias",
-                                               "dgamma", "dbeta")]
+_MAXL = _lib.define("PCL_STACK_MAX_LAYERS")
+_CLayer = _lib.struct("pcl_stack_layer_t")
+_CStack = _lib.struct("pcl_mlp_stack_t")
 
 
 _GOUT_IN_PLACE = __import__("os").environ.get("PCL_GOUT_IN_PLACE", "1") != "0"      # lab switch (A/B on one box)
 COUNTERS = {"strided_gout": 0}        # calls of the stack backward that read their gout in place from a wider gradient
-
-
-class _CStack(ctypes.Structure):
-    _fields_ = ([("struct_bytes", ctypes.c_int32), ("n_layers", ctypes.c_int32), ("c", ctypes.c_int32 * (_MAXL + 1))]
-                + [(n, ctypes.c_int32) for n in ("P", "pool", "grouped", "x_grad_from", "need_dx", "B", "N", "m", "Cf", "use_xyz")]
-                + [(n, ctypes.c_float) for n in ("slope", "out_slope", "eps", "momentum")]
-                + [(n, ctypes.c_void_p) for n in ("x", "xyz", "new_xyz", "feature", "Wf_dense", "idx", "cnt", "group_off")]
-                + [("layer", _CLayer * _MAXL), ("out", ctypes.c_void_p), ("save", ctypes.c_void_p), ("save_bytes", ctypes.c_size_t),
-                   ("tmp", ctypes.c_void_p), ("tmp_bytes", ctypes.c_size_t), ("gout", ctypes.c_void_p), ("dx", ctypes.c_void_p),
-                   ("stream", ctypes.c_void_p), ("defer_act", ctypes.c_int32), ("ext_stat_rows", ctypes.c_int32),
-                   ("ext_stats", ctypes.c_void_p), ("flush_k", ctypes.c_int32), ("gout_ld", ctypes.c_int32)])
 
 
 class _StackPlan:
