@@ -492,8 +492,13 @@ int pcl_get_fb_two_images(void);
 /* The optimiser step (reference: nn.SGD(net.parameters(), lr, momentum), train_cls.py:404; train_partseg.py: weight_decay 1e-4):
  *   g += weight_decay * p;  v = momentum * v + (1 - dampening) * g;  p -= lr * v        (no Nesterov, every tensor has its buffer v)
  * for n_tensors fp32 tensors in one launch per 96 tensors.  params / grads / bufs / numel are HOST arrays (device pointers, element
- * counts); pointers need 4-byte alignment only.  The arithmetic is torch.optim.SGD(fused=True)'s: products and sums in fp64 of the fp32
- * operands, one rounding per statement (tests/test_networks_gpu.py::test_lean_sgd_is_torch_fused_sgd: bit-identical). */
+ * counts); pointers need 4-byte alignment only, an entry with numel == 0 is skipped whatever its pointers.  The whole table is validated
+ * before the first launch: a call that returns PCL_EINVAL (a null pointer, numel < 0 or >= 2^32 - 4097 in ANY entry) has updated nothing.
+ * The arithmetic is torch.optim.SGD(fused=True)'s: products and sums in fp64 of the fp32 operands, one rounding per statement -- equal to
+ * the fp64 restatement of tests/sgd_ref.py bit for bit; torch's fused kernel, which contracts its fp64 products and sums, within 1 ulp
+ * per statement unless the two terms of a statement cancel exactly (then 0 here, an fp64 rounding residue there), and identical in every
+ * element seen at dampening = 0, lr = 0.02 (tests/test_sgd_gpu.py: more than 96 tensors, 1 to 2^20 elements, every alignment of the three
+ * pointers, the networks' own gradients). */
 int pcl_sgd_momentum_f32(const uint64_t* params, const uint64_t* grads, const uint64_t* bufs, const int64_t* numel, int n_tensors, double lr,
                          double momentum, double weight_decay, double dampening, void* stream);
 /* Lab switches of the kernel selection (no reference counterpart), 1 = on (default), 0 = off, negative = leave as is: the resident-weight

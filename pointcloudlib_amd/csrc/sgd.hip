@@ -5,9 +5,13 @@
 // The host loop used torch's multi-tensor fused SGD: 29.5 us for the 1.47 M parameters of PointNet++ SSG cls, 3 x 45 us for PointConv's
 // 19.6 M (335 MB of parameter, gradient and momentum traffic at 2.4 TB/s) -- its chunk table travels as kernel arguments 110 tensors at a
 // time and a block handles one 64 KB chunk.  Here: the same arithmetic (the products and sums in fp64 of the fp32 operands, rounded once per
-// statement -- what torch's kernel computes with its `double` hyper-parameters, so the two agree bit for bit), a table of
+// statement -- what torch's kernel computes with its `double` hyper-parameters, except that torch's build contracts the fp64 products and
+// sums into fused multiply-adds: within 1 ulp per statement of this kernel unless a statement's terms cancel exactly, identical where no
+// fp64 value sits on a rounding boundary), a table of
 // (p, g, v, first block) per tensor as kernel arguments, 16-byte accesses where the three pointers allow (gradients are slices of a
 // per-stack flat buffer: any 4-byte alignment), a block = 4 096 elements.
+// Equal to the fp64 restatement of tests/sgd_ref.py bit for bit (this library is built with -ffp-contract=off, so the CPU reproduces every
+// rounding); torch's fused kernel within 1 ulp per statement, exact cancellations aside: tests/test_sgd_gpu.py.
 #include "common.h"
 
 namespace pcl {
@@ -73,6 +77,13 @@ using namespace pcl;
 extern "C" int pcl_sgd_momentum_f32(const uint64_t* params, const uint64_t* grads, const uint64_t* bufs, const int64_t* numel, int n_tensors, double lr,
                                     double momentum, double weight_decay, double dampening, void* stream) {
     PCL_REQUIRE(params && grads && bufs && numel && n_tensors >= 0, "pcl_sgd_momentum_f32: null table");
+    // validate, then launch: the whole table is checked before the first launch, so a call that returns PCL_EINVAL has updated nothing
+    // (a bad entry behind the first 96 used to be found after their launch)
+    for (int i = 0; i < n_tensors; ++i) {
+        if (numel[i] == 0) continue;
+        PCL_REQUIRE(numel[i] > 0 && numel[i] < (int64_t)0xffffffffll - SGD_CHUNK, "pcl_sgd_momentum_f32: tensor %d: %lld elements", i, (long long)numel[i]);
+        PCL_REQUIRE(params[i] && grads[i] && bufs[i], "pcl_sgd_momentum_f32: tensor %d: null pointer", i);
+    }
     hipStream_t st = as_stream(stream);
     for (int t0 = 0; t0 < n_tensors; t0 += SGD_MAXT) {
         SgdTable t = {};
@@ -81,8 +92,6 @@ extern "C" int pcl_sgd_momentum_f32(const uint64_t* params, const uint64_t* grad
         int k = 0;
         for (int i = t0; i < n_tensors && i < t0 + SGD_MAXT; ++i) {
             if (numel[i] == 0) continue;
-            PCL_REQUIRE(params[i] && grads[i] && bufs[i], "pcl_sgd_momentum_f32: tensor %d: null pointer", i);
-            PCL_REQUIRE(numel[i] > 0 && numel[i] < (int64_t)0xffffffffll - SGD_CHUNK, "pcl_sgd_momentum_f32: tensor %d: %lld elements", i, (long long)numel[i]);
             t.p[k] = reinterpret_cast<float*>(params[i]); t.g[k] = reinterpret_cast<const float*>(grads[i]); t.v[k] = reinterpret_cast<float*>(bufs[i]);
             t.n[k] = (unsigned)numel[i]; t.first[k] = blocks;
             blocks += (unsigned)((numel[i] + SGD_CHUNK - 1) / SGD_CHUNK);

@@ -173,7 +173,7 @@ class _LeanFusedSGD(torch.optim.SGD):
         if any(x is None for x in grads):
             return super().step()
         if self._own is not None and not g["nesterov"] and not g["maximize"]:
-            # one launch of the library's own kernel per 96 tensors (csrc/sgd.hip: torch's arithmetic, bit-identical): the pointer tables of
+            # one launch of the library's own kernel per 96 tensors (csrc/sgd.hip: torch's arithmetic without its fp64 contraction): the pointer tables of
             # the parameters and the momentum buffers are built once, the gradients' every step (they are new slices of the stacks' flat
             # gradient buffers each backward)
             from . import _lib
