@@ -9,6 +9,8 @@
 //   backward: (1) wave = column n again: du = dout * act'(out), BatchNorm backward over the column, dy[:,n] stored;
 //                 dW[n,:] = sum_r dy[r] X[r,:] written coalesced; dgamma, dbeta, dbias.
 //             (2) dX[r,k] = sum_n dy[r,n] W[n,k]: lane = k, the n range split over waves, summed in a fixed order.
+//             Inside a whole head (pcl_fc_head_bwd_f32) the column workgroups of the layer below form the column of (2) they
+//             need themselves, in the same order, and (2) is launched for the first layer only (head_bwd_cols_kernel).
 // BatchNorm1d follows torch (the head is torch's BatchNorm1d in the counterpart networks): biased variance for the
 // normalisation, UNBIASED variance into running_var, momentum 0.1.
 #include "common.h"
@@ -137,27 +139,18 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
     head_epilogue(y, lane, n, bias, gamma, beta, rmean, rvar, R, N, bn_mode, eps, momentum, slope, Ypre, OUT, mean_out, invstd_out, drop);
 }
 
-// backward, column part: dy[:,n], dW[n,:], dbias[n], dgamma[n], dbeta[n].  One workgroup per column; every wave forms
-// the column's dy (R values, lane r) itself and writes its quarter of dW[n,:].
-template <int RMAX>
-__global__ __launch_bounds__(256) void head_bwd_col_kernel(const float* __restrict__ X, const float* __restrict__ dOUT,
-                                                           const float* __restrict__ OUT, const float* __restrict__ Ypre,
-                                                           const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                           const float* __restrict__ invstd, int R, int K, int N, int bn_mode,
-                                                           float slope, float* __restrict__ dY, float* __restrict__ dW,
-                                                           float* __restrict__ dbias, float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta, float* __restrict__ dX_zero, const Drop drop) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int n = blockIdx.x;
-    if (dX_zero) {                         // head_dx_mfma_kernel, which may follow, accumulates with atomics: clear its target here
-        const int total = R * K, chunk = (total + N - 1) / N;
-        for (int e = n * chunk + threadIdx.x; e < min((n + 1) * chunk, total); e += 256) dX_zero[e] = 0.f;
-    }
+// Column part of a layer's backward, one full wave per column (lane r = batch row r, `dout` = this lane's dOUT[r,n]): du = dout * act',
+// BatchNorm backward over the column; dy, dbias / dgamma / dbeta written where `store` (one wave of the column's workgroup; dY null: the
+// caller does not need it).  Returns this lane's dy.
+__device__ __forceinline__ float head_col_dy(int lane, int n, float dout, const float* __restrict__ OUT,
+                                             const float* __restrict__ Ypre, const float* __restrict__ gamma,
+                                             const float* __restrict__ mean, const float* __restrict__ invstd, int R, int N,
+                                             int bn_mode, float slope, float* __restrict__ dY, float* __restrict__ dbias,
+                                             float* __restrict__ dgamma, float* __restrict__ dbeta, const Drop drop, bool store) {
     const bool in = lane < R;
     const size_t o = (size_t)min(lane, R - 1) * N + n;
-    float du = in ? dOUT[o] * drop_scale(drop, (unsigned)o) : 0.f;     // (a dropped element: OUT = 0 and du = 0)
-    const float outv = OUT[o];
-    du = outv > 0.f ? du : du * slope;                      // act'(.) from the sign of the activation's output (slope >= 0)
+    float du = in ? dout * drop_scale(drop, (unsigned)o) : 0.f;     // (a dropped element: OUT = 0 and du = 0)
+    du = OUT[o] > 0.f ? du : du * slope;                            // act'(.) from the sign of the activation's output (slope >= 0)
     float dy = du;
     if (bn_mode != 0) {
         const float g = gamma ? gamma[n] : 1.f, mu = mean[n], is = invstd[n];
@@ -165,18 +158,24 @@ __global__ __launch_bounds__(256) void head_bwd_col_kernel(const float* __restri
         float s1 = du, s2 = du * xh;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-        if (lane == 0 && wave == 0) { if (dgamma) dgamma[n] = s2; if (dbeta) dbeta[n] = s1; }
+        if (lane == 0 && store) { if (dgamma) dgamma[n] = s2; if (dbeta) dbeta[n] = s1; }
         dy = bn_mode == 1 ? g * is * (du - s1 / (float)R - xh * s2 / (float)R) : g * is * du;
         if (!in) dy = 0.f;
     }
-    if (in && wave == 0) dY[o] = dy;
+    if (in && store && dY) dY[o] = dy;
     if (dbias) {
-        float s = dy;
+        float sb = dy;
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0 && wave == 0) dbias[n] = s;
+        for (int off = 32; off >= 1; off >>= 1) sb += __shfl_xor(sb, off);
+        if (lane == 0 && store) dbias[n] = sb;
     }
-    // dW[n, k] = sum_r dy[r] * X[r, k]: lane r holds dy[r]; broadcast it row by row
+    return dy;
+}
+
+// dW[n, k] = sum_r dy[r] * X[r, k]: lane r of every wave holds dy[r], broadcast row by row; the four waves split K in 256-wide chunks.
+template <int RMAX>
+__device__ __forceinline__ void head_col_dw(const float* __restrict__ X, float dy, int R, int K, int n, int wave, int lane,
+                                            float* __restrict__ dW) {
     const bool vec = (K & 3) == 0;
     for (int k0 = wave * HD_KC; k0 < K; k0 += 4 * HD_KC) {
         const int k = k0 + 4 * lane;
@@ -199,70 +198,122 @@ __global__ __launch_bounds__(256) void head_bwd_col_kernel(const float* __restri
     }
 }
 
-// Column part of a layer's backward, one full wave per column (lane r = batch row r): du = dout * act', BatchNorm backward over the
-// column, dy stored; dbias / dgamma / dbeta.  Returns this lane's dy.
-__device__ __forceinline__ float head_col_dy(int lane, int n, const float* __restrict__ dOUT, const float* __restrict__ OUT,
-                                             const float* __restrict__ Ypre, const float* __restrict__ gamma,
-                                             const float* __restrict__ mean, const float* __restrict__ invstd, int R, int N,
-                                             int bn_mode, float slope, float* __restrict__ dY, float* __restrict__ dbias,
-                                             float* __restrict__ dgamma, float* __restrict__ dbeta, const Drop drop) {
-    const bool in = lane < R;
-    const size_t o = (size_t)min(lane, R - 1) * N + n;
-    float du = in ? dOUT[o] * drop_scale(drop, (unsigned)o) : 0.f;
-    du = OUT[o] > 0.f ? du : du * slope;
-    float dy = du;
-    if (bn_mode != 0) {
-        const float g = gamma ? gamma[n] : 1.f, mu = mean[n], is = invstd[n];
-        const float xh = in ? (Ypre[o] - mu) * is : 0.f;
-        float s1 = du, s2 = du * xh;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-        if (lane == 0) { if (dgamma) dgamma[n] = s2; if (dbeta) dbeta[n] = s1; }
-        dy = bn_mode == 1 ? g * is * (du - s1 / (float)R - xh * s2 / (float)R) : g * is * du;
-        if (!in) dy = 0.f;
+// backward, column part: dy[:,n], dW[n,:], dbias[n], dgamma[n], dbeta[n].  One workgroup per column; every wave forms
+// the column's dy (R values, lane r) itself and writes its quarter of dW[n,:].
+template <int RMAX>
+__global__ __launch_bounds__(256) void head_bwd_col_kernel(const float* __restrict__ X, const float* __restrict__ dOUT,
+                                                           const float* __restrict__ OUT, const float* __restrict__ Ypre,
+                                                           const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                           const float* __restrict__ invstd, int R, int K, int N, int bn_mode,
+                                                           float slope, float* __restrict__ dY, float* __restrict__ dW,
+                                                           float* __restrict__ dbias, float* __restrict__ dgamma,
+                                                           float* __restrict__ dbeta, float* __restrict__ dX_zero, const Drop drop) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = blockIdx.x;
+    if (dX_zero) {                         // head_dx_mfma_kernel, which may follow, accumulates with atomics: clear its target here
+        const int total = R * K, chunk = (total + N - 1) / N;
+        for (int e = n * chunk + threadIdx.x; e < min((n + 1) * chunk, total); e += 256) dX_zero[e] = 0.f;
     }
-    if (in) dY[o] = dy;
-    if (dbias) {
-        float sb = dy;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sb += __shfl_xor(sb, off);
-        if (lane == 0) dbias[n] = sb;
-    }
-    return dy;
+    const float dout = dOUT[(size_t)min(lane, R - 1) * N + n];
+    const float dy = head_col_dy(lane, n, dout, OUT, Ypre, gamma, mean, invstd, R, N, bn_mode, slope, dY, dbias, dgamma, dbeta, drop, wave == 0);
+    head_col_dw<RMAX>(X, dy, R, K, n, wave, lane, dW);
 }
 
-// dX[r,k] = sum_n dy[r,n] * W[n,k]; grid (ceil(K/64), ceil(R/HD_RB)): lane = k, a workgroup owns HD_RB batch rows and the whole n
+// dX[r,k] = sum_n dy[r,n] * W[n,k]; grid (ceil(K/64), ceil(R/RB)): lane = k, a workgroup owns RB batch rows and the whole n
 // range, wave w of HD_W sums n = w, w + HD_W, ... in order and the waves meet in LDS in a fixed order.  dX is written once, no atomics: the
 // same inputs give the same bits on every run (the earlier split-n form added its partial sums with fp32 atomics in arrival order).
+// RB changes the grid, not a sum: 4 rows per workgroup, or 2 where that would leave compute units without a workgroup (head_dx_rb).  The
+// kernel waits on memory, not on arithmetic -- a wave's chain is N / 16 loads of W of 256 bytes each -- so eight of them are in flight per
+// wave, and dy[r, n], the same for all lanes, is read through the scalar cache (the wave index is made provably uniform for that).
 constexpr int HD_RB = 4, HD_W = 16;
+template <int RB>
 __global__ __launch_bounds__(64 * HD_W) void head_bwd_dx_kernel(const float* __restrict__ dY, const float* __restrict__ W, int R, int K,
                                                           int N, float* __restrict__ dX) {
-    __shared__ float sP[HD_W - 1][HD_RB][64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __shared__ float sP[HD_W - 1][RB][64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int k = blockIdx.x * 64 + lane, kc = min(k, K - 1);
-    const int r0 = blockIdx.y * HD_RB;
-    float acc[HD_RB];
+    const int r0 = blockIdx.y * RB;
+    float acc[RB];
 #pragma unroll
-    for (int r = 0; r < HD_RB; ++r) acc[r] = 0.f;
-#pragma unroll 4
+    for (int r = 0; r < RB; ++r) acc[r] = 0.f;
+#pragma unroll 8
     for (int n = wave; n < N; n += HD_W) {
         const float w = W[(size_t)n * K + kc];
 #pragma unroll
-        for (int r = 0; r < HD_RB; ++r) acc[r] = fmaf(r0 + r < R ? dY[(size_t)(r0 + r) * N + n] : 0.f, w, acc[r]);
+        for (int r = 0; r < RB; ++r) acc[r] = fmaf(r0 + r < R ? dY[(size_t)(r0 + r) * N + n] : 0.f, w, acc[r]);
     }
     if (wave > 0) {
 #pragma unroll
-        for (int r = 0; r < HD_RB; ++r) sP[wave - 1][r][lane] = acc[r];
+        for (int r = 0; r < RB; ++r) sP[wave - 1][r][lane] = acc[r];
     }
     __syncthreads();
     if (wave == 0 && k < K) {
 #pragma unroll
-        for (int r = 0; r < HD_RB; ++r) {
+        for (int r = 0; r < RB; ++r) {
             float v = acc[r];
             for (int w = 0; w < HD_W - 1; ++w) v += sP[w][r][lane];
             if (r0 + r < R) dX[(size_t)(r0 + r) * K + k] = v;
         }
     }
+}
+static inline int head_dx_rb(int R, int K) { return ((K + 63) / 64) * ((R + HD_RB - 1) / HD_RB) < 256 ? 2 : HD_RB; }
+
+// ---- the column part that forms its own dOUT: no dX launch between two layers of a head -----------------------------------------------
+// head_bwd_dx_kernel of layer l+1 exists so that column n of layer l can read dOUT_l[:, n] = dX_{l+1}[:, n] = sum_m dY_{l+1}[:, m] W_{l+1}[m, n].
+// The column's workgroup forms that sum itself from dY_{l+1} (R x Nn floats, L2-resident) and the strided column n of W_{l+1}, in
+// head_bwd_dx_kernel's order, so every bit stays: HD_W partial sums p_c over m = c, c + HD_W, ... (an fmaf chain from 0, ascending m),
+// then p_0 + p_1 + ... + p_15 from the left.  Thread t owns chain c = t & 15 of rows t >> 4, + 16, ...: a wave reads 64-byte pieces of
+// four dY rows per load, and the chains meet in LDS.  The launch boundary, the dX buffer and its 6.6 us kernel go.
+struct ColJob {
+    const float *X, *dOUT, *OUT, *Ypre, *gamma, *mean, *invstd;     // dOUT: read by the direct form
+    const float *dYn, *Wn;                                         // the layer above: its dY [R, Nn] and W [Nn, N] (the forming form)
+    int Nn, K, N, bn_mode;
+    float slope;
+    float *dY, *dW, *dbias, *dgamma, *dbeta;
+    Drop drop;
+};
+template <int RMAX>
+__device__ __forceinline__ float head_col_dout(const float* __restrict__ dYn, const float* __restrict__ Wn, int R, int Nn, int N, int n,
+                                               float (*sP)[RMAX]) {
+    constexpr int Q = RMAX / 16;
+    const int c = threadIdx.x & (HD_W - 1), r0 = threadIdx.x >> 4, lane = threadIdx.x & 63;
+    float acc[Q];
+    const float* row[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) { acc[q] = 0.f; row[q] = dYn + (size_t)min(r0 + 16 * q, R - 1) * Nn; }   // (rows past R: computed, never used)
+#pragma unroll 4
+    for (int m = c; m < Nn; m += HD_W) {
+        const float w = Wn[(size_t)m * N + n];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) acc[q] = fmaf(row[q][m], w, acc[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) sP[c][r0 + 16 * q] = acc[q];
+    __syncthreads();
+    float v = 0.f;
+    if (lane < RMAX) {
+        v = sP[0][lane];
+        for (int w = 1; w < HD_W; ++w) v += sP[w][lane];
+    }
+    return v;
+}
+template <int RMAX, bool FORM>
+__device__ __forceinline__ void head_col_job(const ColJob& j, int R, int n, float (*sP)[RMAX]) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float dout;
+    if (FORM) dout = head_col_dout<RMAX>(j.dYn, j.Wn, R, j.Nn, j.N, n, sP);
+    else dout = j.dOUT[(size_t)min(lane, R - 1) * j.N + n];
+    const float dy = head_col_dy(lane, n, dout, j.OUT, j.Ypre, j.gamma, j.mean, j.invstd, R, j.N, j.bn_mode, j.slope, j.dY, j.dbias, j.dgamma,
+                                 j.dbeta, j.drop, wave == 0);
+    head_col_dw<RMAX>(j.X, dy, R, j.K, n, wave, lane, j.dW);
+}
+// grid: na + b.N workgroups of 256.  Workgroups below na are the columns of job a (direct form: a layer whose dY is its dOUT, so that
+// job b may read a.dOUT as the dY above it in the same launch); the others are the columns of job b, which forms its dOUT.
+template <int RMAX>
+__global__ __launch_bounds__(256) void head_bwd_cols_kernel(const ColJob a, const ColJob b, int na, int R) {
+    __shared__ float sP[HD_W][RMAX];
+    if ((int)blockIdx.x < na) head_col_job<RMAX, false>(a, R, blockIdx.x, sP);
+    else head_col_job<RMAX, true>(b, R, (int)blockIdx.x - na, sP);
 }
 
 typedef float hd_f32x16 __attribute__((ext_vector_type(16)));
@@ -377,7 +428,9 @@ __global__ __launch_bounds__(256) void head_dy_kernel(const float* __restrict__ 
         for (int e = blockIdx.x * chunk + tid; e < min(((int)blockIdx.x + 1) * chunk, total); e += 256) dX_zero[e] = 0.f;
     }
     const int n = blockIdx.x * 4 + wave;
-    if (n < N) (void)head_col_dy(lane, n, dOUT, OUT, Ypre, gamma, mean, invstd, R, N, bn_mode & 3, slope, dY, dbias, dgamma, dbeta, drop);
+    if (n < N)
+        (void)head_col_dy(lane, n, dOUT[(size_t)min(lane, R - 1) * N + n], OUT, Ypre, gamma, mean, invstd, R, N, bn_mode & 3, slope, dY, dbias, dgamma,
+                          dbeta, drop, true);
 }
 __global__ __launch_bounds__(256) void head_dw_mfma_kernel(const float* __restrict__ dY, const float* __restrict__ X, int R, int K, int N,
                                                            int kb_per_wg, float* __restrict__ dW) {
@@ -496,7 +549,8 @@ extern "C" int pcl_head_layer_fwd_f32(const float* X, const float* W, const floa
 }
 extern "C" size_t pcl_head_layer_fwd_workspace_bytes(int R, int K, int N) { return (R < 1 || K < 1 || N < 1) ? 0 : head_fwd_ws_bytes(R, K, N); }
 
-static int head_layer_bwd_impl(const float* X, const float* W, const float* dOUT, const float* OUT, const float* Ypre,
+// the column part of a layer's backward (dX: cleared here where head_dx_mfma_kernel's atomics follow), then its dX
+static int head_layer_cols(const float* X, const float* W, const float* dOUT, const float* OUT, const float* Ypre,
                                       const float* gamma, const float* mean, const float* invstd, int R, int K, int N, int bn_mode,
                                       float slope, float* dY_ws, float* dW, float* dbias, float* dgamma, float* dbeta, float* dX,
                                       void* stream, const Drop drop) {
@@ -517,15 +571,24 @@ static int head_layer_bwd_impl(const float* X, const float* W, const float* dOUT
     else
         hipLaunchKernelGGL(head_bwd_col_kernel<64>, grid, block, 0, st, X, dOUT, OUT, Ypre, gamma, mean, invstd, R, K, N, bn_mode & 3, slope, dY_ws,
                            dW, dbias, dgamma, dbeta, nullptr, drop);
-    int rc = check_launch("pcl_head_layer_bwd_f32(col)");
-    if (rc || !dX) return rc;
-    const dim3 g2((K + 63) / 64, (R + HD_RB - 1) / HD_RB);
+    return check_launch("pcl_head_layer_bwd_f32(col)");
+}
+static int head_layer_dx(const float* dY, const float* W, int R, int K, int N, float* dX, hipStream_t st) {
     if (R <= 32 && K >= 2048) {
         const int NS = N >= 512 ? 2 : 1, nper = ((N + NS - 1) / NS + 127) / 128 * 128;
-        hipLaunchKernelGGL(head_dx_mfma_kernel, dim3((K + 127) / 128, NS), block, 0, st, dY_ws, W, R, K, N, nper, dX);
+        hipLaunchKernelGGL(head_dx_mfma_kernel, dim3((K + 127) / 128, NS), dim3(256), 0, st, dY, W, R, K, N, nper, dX);
     }
-    else hipLaunchKernelGGL(head_bwd_dx_kernel, g2, dim3(64 * HD_W), 0, st, dY_ws, W, R, K, N, dX);
+    else if (head_dx_rb(R, K) == 2) hipLaunchKernelGGL(head_bwd_dx_kernel<2>, dim3((K + 63) / 64, (R + 1) / 2), dim3(64 * HD_W), 0, st, dY, W, R, K, N, dX);
+    else hipLaunchKernelGGL(head_bwd_dx_kernel<HD_RB>, dim3((K + 63) / 64, (R + HD_RB - 1) / HD_RB), dim3(64 * HD_W), 0, st, dY, W, R, K, N, dX);
     return check_launch("pcl_head_layer_bwd_f32(dx)");
+}
+static int head_layer_bwd_impl(const float* X, const float* W, const float* dOUT, const float* OUT, const float* Ypre,
+                                      const float* gamma, const float* mean, const float* invstd, int R, int K, int N, int bn_mode,
+                                      float slope, float* dY_ws, float* dW, float* dbias, float* dgamma, float* dbeta, float* dX,
+                                      void* stream, const Drop drop) {
+    int rc = head_layer_cols(X, W, dOUT, OUT, Ypre, gamma, mean, invstd, R, K, N, bn_mode, slope, dY_ws, dW, dbias, dgamma, dbeta, dX, stream, drop);
+    if (rc || !dX) return rc;
+    return head_layer_dx(dY_ws, W, R, K, N, dX, as_stream(stream));
 }
 
 extern "C" int pcl_head_layer_bwd_f32(const float* X, const float* W, const float* dOUT, const float* OUT, const float* Ypre,
@@ -588,6 +651,12 @@ static inline Drop head_drop(const pcl_fc_head_t& d, int l) {
     const unsigned lo = (unsigned)(d.seed & 0xffffffffull) ^ (0x9E3779B9u * (unsigned)(l + 1)), hi = (unsigned)(d.seed >> 32) + 0x7F4A7C15u * (unsigned)(l + 1);
     return Drop{d.layer[l].drop_p, lo, hi};
 }
+// The seam between layer l and layer l - 1 needs no dX launch when both are the plain VALU column form (head_bwd_col_kernel +
+// head_bwd_dx_kernel: not the wide layers, not K >= 2048 on <= 32 rows with its MFMA dX, atomics and clearing) and the sum that a column
+// of l - 1 then forms is short: every one of its N workgroups reads all of dY_l, R x N_l floats.
+constexpr int HD_FORM_NMAX = 1024;
+static inline bool head_valu(const pcl_fc_head_t& d, int l) { return !(d.R <= 32 && d.layer[l].K >= 2048); }
+static inline bool head_seam(const pcl_fc_head_t& d, int l) { return head_valu(d, l) && head_valu(d, l - 1) && d.layer[l].N <= HD_FORM_NMAX; }
 }  // namespace pcl
 
 extern "C" int pcl_fc_head_sizes(const pcl_fc_head_t* d, size_t* save_bytes, size_t* bwd_tmp_bytes) {
@@ -626,16 +695,58 @@ extern "C" int pcl_fc_head_bwd_f32(const pcl_fc_head_t* dp) {
     float *dY, *dXa, *dXb;
     const size_t need = head_bwd_tmp(d, &dY, &dXa, &dXb, d.tmp);
     if (d.save_bytes < h.bytes || d.tmp_bytes < need) return fail(PCL_EWS, "pcl_fc_head_bwd_f32: save %zu < %zu or tmp %zu < %zu", d.save_bytes, h.bytes, d.tmp_bytes, need);
-    const float* g = d.gout;
-    for (int l = d.n_layers - 1; l >= 0; --l) {
+    // Top layer down.  A layer's dOUT is either in memory (`g`: gout, or a dX that was launched) or still to be formed by its own column
+    // workgroups from the dY and W of the layer above (`up`).  Every buffer written here is read by the next launch only, so dY and dX
+    // rotate through the three regions of the carve; the first, the last layer's dY [R, N_last], is the region sized for it.
+    float* const region[3] = {dY, dXa, dXb};
+    int turn = 0;
+    hipStream_t st = as_stream(d.stream);
+    auto job = [&](int l, const float* dOUT, float* dYl) {
+        const pcl_head_layer_t& y = d.layer[l];
+        return ColJob{l == 0 ? d.x : h.OUT[l - 1], dOUT, l == d.n_layers - 1 ? d.out : h.OUT[l], h.Ypre[l], y.gamma, h.mean[l], h.invstd[l],
+                      nullptr, nullptr, 0, y.K, y.N, y.bn_mode & 3, y.slope, dYl, y.dW, y.dbias, y.dgamma, y.dbeta, head_drop(d, l)};
+    };
+    auto launch = [&](const ColJob& a, const ColJob& b, int na) {
+        if (d.R <= 32) hipLaunchKernelGGL(head_bwd_cols_kernel<32>, dim3(na + b.N), dim3(256), 0, st, a, b, na, d.R);
+        else hipLaunchKernelGGL(head_bwd_cols_kernel<64>, dim3(na + b.N), dim3(256), 0, st, a, b, na, d.R);
+        return check_launch("pcl_fc_head_bwd_f32(cols)");
+    };
+    for (int l = 0; l < d.n_layers; ++l) {
         const pcl_head_layer_t& y = d.layer[l];
         PCL_REQUIRE(y.dW && (!y.bias || y.dbias) && (!(y.bn_mode & 3) || !y.gamma || (y.dgamma && y.dbeta)), "pcl_fc_head_bwd_f32: layer %d: null gradient output", l);
-        const float* X = l == 0 ? d.x : h.OUT[l - 1];
-        const float* OUT = l == d.n_layers - 1 ? d.out : h.OUT[l];
-        float* dX = l == 0 ? d.dx : ((d.n_layers - 1 - l) & 1 ? dXb : dXa);
-        rc = head_layer_bwd_impl(X, y.W, g, OUT, h.Ypre[l], y.gamma, h.mean[l], h.invstd[l], d.R, y.K, y.N, y.bn_mode, y.slope, dY, y.dW, y.dbias,
-                                 y.dgamma, y.dbeta, dX, d.stream, head_drop(d, l));
-        if (rc) return rc;
+    }
+    const float* g = d.gout;
+    const float* up = nullptr;                    // dY of layer l + 1 while layer l forms its dOUT
+    for (int l = d.n_layers - 1; l >= 0; --l) {
+        const pcl_head_layer_t& y = d.layer[l];
+        float* dYl;
+        if (up) {                                 // forms its dOUT from (up, W of l + 1)
+            dYl = region[turn++ % 3];
+            ColJob b = job(l, nullptr, dYl);
+            b.dYn = up; b.Wn = d.layer[l + 1].W; b.Nn = d.layer[l + 1].N;
+            if ((rc = launch(b, b, 0))) return rc;
+        } else if (l > 0 && head_seam(d, l) && (y.bn_mode & 3) == 0 && y.slope == 1.f && y.drop_p == 0.f) {
+            // dY of this layer is its dOUT bit for bit: its columns and those of the layer below, which reads g as that dY, share a launch
+            dYl = region[turn++ % 3];
+            ColJob b = job(l - 1, nullptr, dYl);
+            b.dYn = g; b.Wn = y.W; b.Nn = y.N;
+            if ((rc = launch(job(l, g, nullptr), b, y.N))) return rc;
+            --l;
+        } else {
+            dYl = region[turn++ % 3];
+            const float* X = l == 0 ? d.x : h.OUT[l - 1];
+            float* clear = l == 0 ? d.dx : region[turn % 3];      // (the dX below, where head_dx_mfma_kernel will add into it)
+            rc = head_layer_cols(X, y.W, g, l == d.n_layers - 1 ? d.out : h.OUT[l], h.Ypre[l], y.gamma, h.mean[l], h.invstd[l], d.R, y.K, y.N,
+                                 y.bn_mode, y.slope, dYl, y.dW, y.dbias, y.dgamma, y.dbeta, clear, d.stream, head_drop(d, l));
+            if (rc) return rc;
+        }
+        // the seam below layer l (l: the layer whose column part has just been launched)
+        const pcl_head_layer_t& z = d.layer[l];
+        up = nullptr;
+        if (l > 0 && head_seam(d, l)) { up = dYl; continue; }
+        float* dX = l == 0 ? d.dx : region[turn++ % 3];
+        if (!dX) break;
+        if ((rc = head_layer_dx(dYl, z.W, d.R, z.K, z.N, dX, st))) return rc;
         g = dX;
     }
     return PCL_OK;
