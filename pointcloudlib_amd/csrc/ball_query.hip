@@ -150,10 +150,7 @@ static int bq_run(const char* who, const float* new_xyz, const float* xyz, const
     hipStream_t st = as_stream(stream);
     if (lds <= 150 * 1024) {
         auto kern = ball_query_kernel<true, RAGGED>;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return fail(PCL_EHIP, "ball_query: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
+        if (int rc = lds_opt_in(kern, lds, who)) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(BQ_THREADS), lds, st, new_xyz, xyz, n_valid, m, N, radius2, nsample, qpb, idx_out, cnt_out);
     } else {
         hipLaunchKernelGGL((ball_query_kernel<false, RAGGED>), grid, dim3(BQ_THREADS), 0, st, new_xyz, xyz, n_valid, m, N, radius2, nsample, qpb,
@@ -180,10 +177,7 @@ static int launch_bq_multi(const char* who, const float* new_xyz, const float* x
     const size_t lds = sizeof(float) * 3 * (size_t)N;
     if (lds <= 150 * 1024) {
         auto kern = ball_query_multi_kernel<true, NR, RAGGED>;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return fail(PCL_EHIP, "ball_query_multi: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
+        if (int rc = lds_opt_in(kern, lds, who)) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(BQ_THREADS), lds, st, new_xyz, xyz, n_valid, m, N, qpb, a);
     } else {
         hipLaunchKernelGGL((ball_query_multi_kernel<false, NR, RAGGED>), grid, dim3(BQ_THREADS), 0, st, new_xyz, xyz, n_valid, m, N, qpb, a);

@@ -2,6 +2,7 @@
 #include "common.h"
 #include <math.h>
 #include <string.h>
+#include <atomic>
 
 namespace pcl {
 static thread_local char g_err[512] = "";
@@ -24,6 +25,17 @@ bool time_hook_matches(const TimeHook& h) { return h.want[0] == 0 || strcmp(h.wa
 PathSwitches& path_switches() {
     static PathSwitches s = {1, 1, 1};
     return s;
+}
+int cu_count() {
+    static std::atomic<int> known[16];                 // by device id, 0 = not asked yet; an id beyond the table is asked every time
+    int dev = -1, cu = 0;
+    const bool have = hipGetDevice(&dev) == hipSuccess;
+    std::atomic<int>* slot = have && dev >= 0 && dev < 16 ? &known[dev] : nullptr;
+    if (slot && (cu = slot->load(std::memory_order_relaxed)) > 0) return cu;
+    if (!have || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu < 1) cu = 256;
+    (void)hipGetLastError();
+    if (slot) slot->store(cu, std::memory_order_relaxed);
+    return cu;
 }
 
 }  // namespace pcl

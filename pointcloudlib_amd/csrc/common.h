@@ -53,15 +53,35 @@ struct PathSwitches { int fwd_resident, narrow_stacks, fused_backward; };
 PathSwitches& path_switches();
 void set_launch_tag(const char* tag);
 bool time_hook_matches(const TimeHook& h);
-#define PCL_LAUNCH_TIMED(kernel, grid, blk, st, ...)                                                                   \
+#define PCL_LAUNCH_TIMED_LDS(kernel, grid, blk, lds, st, ...)                                                          \
     do {                                                                                                                \
         ::pcl::TimeHook& h_ = ::pcl::time_hook();                                                                       \
         h_.last_kernel = #kernel;    /* pcl_last_launch_kernel(): which kernel an entry point chose (profiling tools) */ \
         if (h_.start && ::pcl::time_hook_matches(h_)) {                                                                 \
-            hipExtLaunchKernelGGL(kernel, grid, blk, 0, st, h_.start, h_.stop, 0, __VA_ARGS__);                         \
+            hipExtLaunchKernelGGL(kernel, grid, blk, lds, st, h_.start, h_.stop, 0, __VA_ARGS__);                       \
             h_.start = h_.stop = nullptr;                                                                               \
-        } else hipLaunchKernelGGL(kernel, grid, blk, 0, st, __VA_ARGS__);                                               \
+        } else hipLaunchKernelGGL(kernel, grid, blk, lds, st, __VA_ARGS__);                                             \
     } while (0)
+#define PCL_LAUNCH_TIMED(kernel, grid, blk, st, ...) PCL_LAUNCH_TIMED_LDS(kernel, grid, blk, 0, st, __VA_ARGS__)
+
+// ---------------------------------------------------------------- host launch helpers
+// CU count of the CURRENT device, asked once per device id (capi.hip).  256 -- the MI355X's own count -- when there is no device or
+// the query fails; the sticky HIP error of the failed query is cleared (the size queries answer without a GPU).
+int cu_count();
+
+// Dynamic LDS beyond the 64 KB a kernel may use by default needs the kernel's limit raised first: call this before every such
+// launch (a no-op up to 64 KB; the attribute belongs to the current device, so nothing is remembered here).
+template <class K>
+inline int lds_opt_in(K* kernel, size_t bytes, const char* who) {
+    if (bytes <= 64 * 1024) return PCL_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return fail(PCL_EHIP, "%s: hipFuncSetAttribute(%zu): %s", who, bytes, hipGetErrorString(e));
+    return PCL_OK;
+}
+
+// May a kernel move 16-byte pieces of these operands?  True when every pointer given is 16-byte aligned; null counts as aligned.
+template <class... T>
+inline bool al16(const T*... p) { return ((uintptr_t(0) | ... | reinterpret_cast<uintptr_t>(p)) & 15) == 0; }
 
 // XCD-aware logical block id for a 1-D grid whose consecutive blocks walk the clouds one after another (`bpc` blocks per
 // cloud, nblk = clouds * bpc).  The hardware deals consecutive workgroup ids to the 8 XCDs round-robin, each with its own

@@ -734,7 +734,7 @@ extern "C" int pcl_group_compact_f32(const float* xyz, const float* new_xyz, con
 extern "C" int pcl_bn_act_max_rows_f32(const float* Y, const int32_t* group_off, const float* scale, const float* shift,
                                        float slope, int G, int C, float* out, int32_t* arg, float* ymax, void* stream) {
     PCL_REQUIRE(Y && group_off && scale && shift && out && arg && ymax && G >= 1 && C >= 1, "pcl_bn_act_max_rows_f32: bad arguments");
-    const bool vec = (C % 4 == 0) && ((reinterpret_cast<uintptr_t>(Y) & 15) == 0);
+    const bool vec = (C % 4 == 0) && al16(Y);
     const size_t total = (size_t)G * (vec ? C / 4 : C);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 16384) blocks = 16384;
@@ -808,8 +808,7 @@ int pcl::group_linear_fwd_impl(const float* xyz, const float* new_xyz, const flo
     const float4* rl = reinterpret_cast<const float4*>(row_loc);
     const float4* rf = reinterpret_cast<const float4*>(row_feat);
     const dim3 grid(GL_BLOCKS), block(256);
-    const bool al16 = ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(Uf)) & 15) == 0;
-    if (al16 && (C1 == 64 || C1 == 128 || C1 == 256)) {
+    if (al16(Y, Uf) && (C1 == 64 || C1 == 128 || C1 == 256)) {
         if (C1 == 64) hipLaunchKernelGGL(group_linear_v4_kernel<16>, grid, block, 0, st, Uf, Wx, Wf_small, CF, ldw, rl, rf, row_src, group_off + G, Y, stats_ws);
         else if (C1 == 128) hipLaunchKernelGGL(group_linear_v4_kernel<32>, grid, block, 0, st, Uf, Wx, Wf_small, CF, ldw, rl, rf, row_src, group_off + G, Y, stats_ws);
         else hipLaunchKernelGGL(group_linear_v4_kernel<64>, grid, block, 0, st, Uf, Wx, Wf_small, CF, ldw, rl, rf, row_src, group_off + G, Y, stats_ws);
@@ -854,8 +853,7 @@ int pcl::group_linear_bwd_impl(const float* row_loc, const float* row_feat, int 
     const dim3 grid(GL_BLOCKS), block(256);
     // with dUf the scatter is one atomic per element either way, and a lane owning 4 consecutive channels spreads every
     // atomic instruction over 4x the cache lines (measured 187 vs 77 us on SA2): the 16-byte layout only when there is none
-    const bool al16 = !dUf && ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(dU)) & 15) == 0;
-    if (al16 && (C1 == 64 || C1 == 128 || C1 == 256)) {
+    if (!dUf && al16(Y, dU) && (C1 == 64 || C1 == 128 || C1 == 256)) {
         if (C1 == 64) hipLaunchKernelGGL(group_linear_bwd_v4_kernel<16>, grid, block, 0, st, rl, rf, CF, dU, Y, a, k1, k2, mu, row_src, n_rows_dev, dUf, dWx_part, dWf_part);
         else if (C1 == 128) hipLaunchKernelGGL(group_linear_bwd_v4_kernel<32>, grid, block, 0, st, rl, rf, CF, dU, Y, a, k1, k2, mu, row_src, n_rows_dev, dUf, dWx_part, dWf_part);
         else hipLaunchKernelGGL(group_linear_bwd_v4_kernel<64>, grid, block, 0, st, rl, rf, CF, dU, Y, a, k1, k2, mu, row_src, n_rows_dev, dUf, dWx_part, dWf_part);
@@ -879,10 +877,7 @@ extern "C" int pcl_group_rows_transpose_i32(const int32_t* row_src, const int32_
     PCL_REQUIRE(pcl_group_rows_transpose_supported(N, m, ns), "pcl_group_rows_transpose_i32: N=%d m=%d ns=%d beyond the LDS-resident form", N, m, ns);
     const size_t lds = ((size_t)(RT_W + 1) * N + 1 + (size_t)m * ns) * 4;
     auto kern = rows_transpose_kernel;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PCL_EHIP, "pcl_group_rows_transpose_i32: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-    }
+    if (int rc = lds_opt_in(kern, lds, "pcl_group_rows_transpose_i32")) return rc;
     hipLaunchKernelGGL(kern, dim3(B), dim3(RT_T), lds, as_stream(stream), row_src, group_off, m, N, B, in_off, in_rows);
     return check_launch("pcl_group_rows_transpose_i32");
 }
@@ -896,7 +891,7 @@ extern "C" int pcl_group_linear_bwd_gather_f32(const float* row_loc, const float
                                                int C1, float* dUf, float* dWx_part, float* dW0, int ldw, void* stream) {
     PCL_REQUIRE(row_loc && dU && Y && a && k1 && k2 && mu && in_off && in_rows && dUf, "pcl_group_linear_bwd_gather_f32: null pointer");
     PCL_REQUIRE(B >= 1 && N >= 1 && pcl_group_linear_bwd_gather_supported(C1), "pcl_group_linear_bwd_gather_f32: bad sizes (C1 = %d: 64, 128 or 256)", C1);
-    PCL_REQUIRE(((reinterpret_cast<uintptr_t>(dU) | reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(dUf)) & 15) == 0, "pcl_group_linear_bwd_gather_f32: 16-byte aligned rows");
+    PCL_REQUIRE(al16(dU, Y, dUf), "pcl_group_linear_bwd_gather_f32: 16-byte aligned rows");
     PCL_REQUIRE(!dW0 || (dWx_part && ldw >= 3), "pcl_group_linear_bwd_gather_f32: dW0 needs dWx_part and ldw >= 3");
     hipStream_t st = as_stream(stream);
     const float4* rl = reinterpret_cast<const float4*>(row_loc);

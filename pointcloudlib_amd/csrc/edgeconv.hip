@@ -477,10 +477,7 @@ extern "C" int pcl_knn_transpose_i32(const int32_t* idx, int B, int N, int k, in
         while (nwv > 1 && (size_t)(nwv + 1) * N * sizeof(int) > 128 * 1024) nwv >>= 1;
         const size_t lds = (size_t)(nwv + 1) * N * sizeof(int);
         auto kern = knn_transpose_ordered_kernel;
-        if (lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return fail(PCL_EHIP, "pcl_knn_transpose_i32: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-        }
+        if (int rc = lds_opt_in(kern, lds, "pcl_knn_transpose_i32")) return rc;
         hipLaunchKernelGGL(kern, dim3(B), dim3(1024), lds, st, idx, N, k, B, nwv, in_off, in_src);
         return check_launch("pcl_knn_transpose_i32");
     }

@@ -327,10 +327,7 @@ static int launch_fps(const char* who, const float* xyz, const int32_t* n_valid,
                       int32_t* idx, float* nx, hipStream_t st) {
     const size_t lds = fps_lds_bytes(N, m, log2S, T * PPT > 1024 ? 3 : 4);           // slots + rank-indexed xyz + sampled ranks
     auto kern = fps_kernel<T, PPT, RAGGED>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PCL_EHIP, "fps: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-    }
+    if (int rc = lds_opt_in(kern, lds, who)) return rc;
     hipLaunchKernelGGL(kern, dim3(B), dim3(T), lds, st, xyz, n_valid, N, m, log2S, thr, start, idx, nx, g_fps_prio);
     return check_launch(who);
 }
@@ -370,10 +367,7 @@ static int fps_run(const char* who, const float* xyz, const int32_t* n_valid, in
     const size_t lds = sizeof(FpsSlot) * 2 * 16 + sizeof(float) * (size_t)N;
     if (lds > 160 * 1024) return fail(PCL_ENOSUP, "%s: N=%d exceeds the LDS-resident limit (%d points)", who, N, (160 * 1024 - 512) / 4);
     auto kern = fps_kernel_lds<1024, RAGGED>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PCL_EHIP, "fps: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-    }
+    if (int rc = lds_opt_in(kern, lds, who)) return rc;
     hipLaunchKernelGGL(kern, dim3(B), dim3(1024), lds, st, xyz, n_valid, N, m, log2S, skip_sqnorm_le, start_idx, idx_out, new_xyz_out);
     return check_launch(who);
 }

@@ -523,16 +523,6 @@ __global__ __launch_bounds__(1024) void frag_dw_kernel(const DwArgs2 p) {
     }
 }
 
-static int cu_count() {
-    static const int n = [] {
-        int dev = 0, cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu < 1) cu = 256;
-        (void)hipGetLastError();
-        return cu;
-    }();
-    return n;
-}
-
 // k groups per workgroup so that the launch puts >= 2 waves on every SIMD when the output alone does not (<= 4: 1024 threads), while a
 // wave keeps >= 8 k steps
 static int pick_ksw(int tiles, int steps) {
@@ -542,36 +532,21 @@ static int pick_ksw(int tiles, int steps) {
     return ksw;
 }
 
-#define FG_LAUNCH(kernel, grid, blk, lds, st, ...)                                                                      \
-    do {                                                                                                                \
-        ::pcl::TimeHook& h_ = ::pcl::time_hook();                                                                       \
-        h_.last_kernel = #kernel;                                                                                       \
-        if (h_.start && ::pcl::time_hook_matches(h_)) {                                                                 \
-            hipExtLaunchKernelGGL(kernel, grid, blk, lds, st, h_.start, h_.stop, 0, __VA_ARGS__);                       \
-            h_.start = h_.stop = nullptr;                                                                               \
-        } else hipLaunchKernelGGL(kernel, grid, blk, lds, st, __VA_ARGS__);                                             \
-    } while (0)
-
 template <int TN, int FLUSH, bool ACT, bool BKN, int EP>
-static void launch_gemm_t(const GemmArgs& g, int ksw, hipStream_t st) {
+static int launch_gemm_t(const char* who, const GemmArgs& g, int ksw, hipStream_t st) {
     const int S = g.K / 8 + ((g.K & 7) ? 1 : 0);
     const size_t cst = ACT ? (size_t)2 * (S + FG_D + 1) * 8 * 4 : 0;
     size_t red = (size_t)4 * TN * 16 * 64 * (FLUSH > 0 ? 8 : 4);                       // k-group reduction buffer (also the statistics exchange)
     const size_t lds = cst + red;
-    if (lds > 64 * 1024) {
-        // the folded input BatchNorm's constants (2 x 32 bytes per 8 k) beside the reduction buffer pass the 64 KB default from Cin ~ 4 000 on
-        // (the entry point admits Cin <= 8 192: 66 KB + 32 KB): raise the kernel's limit, once per instantiation
-        static size_t raised = 0;
-        if (lds > raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(frag_gemm_kernel<TN, FLUSH, ACT, BKN, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            raised = lds;
-        }
-    }
-    FG_LAUNCH((frag_gemm_kernel<TN, FLUSH, ACT, BKN, EP>), dim3(g.nrt * g.nct), dim3(256 * ksw), lds, st, g);
+    // the folded input BatchNorm's constants (2 x 32 bytes per 8 k) beside the reduction buffer pass the 64 KB default from Cin ~ 4 000 on
+    // (the entry point admits Cin <= 8 192: 66 KB + 32 KB)
+    if (int rc = lds_opt_in(frag_gemm_kernel<TN, FLUSH, ACT, BKN, EP>, lds, who)) return rc;
+    PCL_LAUNCH_TIMED_LDS((frag_gemm_kernel<TN, FLUSH, ACT, BKN, EP>), dim3(g.nrt * g.nct), dim3(256 * ksw), lds, st, g);
+    return check_launch(who);
 }
 
 template <int FLUSH, bool ACT, bool BKN, int EP>
-static void launch_gemm(GemmArgs g, hipStream_t st, int force_tn, int force_ksw) {
+static int launch_gemm(const char* who, GemmArgs g, hipStream_t st, int force_tn, int force_ksw) {
     const int width = g.N - g.n_begin;
     g.nrt = (g.M + 63) / 64;
     // 128-column wave pairs (two B fragments per A fragment) when the output still fills the chip twice over with them
@@ -583,8 +558,8 @@ static void launch_gemm(GemmArgs g, hipStream_t st, int force_tn, int force_ksw)
     if (FLUSH > 0) tn = 1;              // (fp64 accumulators: 32 more registers per tile -- two tiles do not fit 128 registers at 4 waves per SIMD)
     g.nct = (width + 64 * tn - 1) / (64 * tn);
     const int ksw = force_ksw ? force_ksw : pick_ksw(g.nrt * g.nct, g.K / 8);
-    if constexpr (FLUSH == 0) { if (tn == 2) { launch_gemm_t<2, FLUSH, ACT, BKN, EP>(g, ksw, st); return; } }
-    launch_gemm_t<1, FLUSH, ACT, BKN, EP>(g, ksw, st);
+    if constexpr (FLUSH == 0) { if (tn == 2) return launch_gemm_t<2, FLUSH, ACT, BKN, EP>(who, g, ksw, st); }
+    return launch_gemm_t<1, FLUSH, ACT, BKN, EP>(who, g, ksw, st);
 }
 
 static int g_force_tn = 0, g_force_ksw = 0, g_force_dw[4] = {0, 0, 0, 0};     // lab / test knobs (pcl_frag_set_tuning)
@@ -651,11 +626,12 @@ extern "C" int pcl_frag_linear_fwd_f32(const float* X, int ldx, const float* W, 
     g.A = X; g.lda = ldx; g.B = W; g.ldb = ldw; g.bias = bias; g.asc = in_scale; g.ash = in_shift; g.aslope = in_slope;
     g.C = Y; g.ldc = ldy; g.Clo = Y_lo; g.stats = stats_ws; g.M = P; g.N = Cout; g.K = Cin; g.n_begin = 0;
     const bool act = in_scale != nullptr;
-#define FWD(FL) do { if (stats_ws) { if (act) launch_gemm<FL, true, false, EP_STATS>(g, st, g_force_tn, g_force_ksw); else launch_gemm<FL, false, false, EP_STATS>(g, st, g_force_tn, g_force_ksw); } \
-                     else { if (act) launch_gemm<FL, true, false, EP_STORE>(g, st, g_force_tn, g_force_ksw); else launch_gemm<FL, false, false, EP_STORE>(g, st, g_force_tn, g_force_ksw); } } while (0)
-    if (flush_k == 0) FWD(0); else if (flush_k == 8) FWD(8); else FWD(32);
+    const char* who = "pcl_frag_linear_fwd_f32";
+#define FWD(FL) (stats_ws ? (act ? launch_gemm<FL, true, false, EP_STATS>(who, g, st, g_force_tn, g_force_ksw) : launch_gemm<FL, false, false, EP_STATS>(who, g, st, g_force_tn, g_force_ksw)) \
+                          : (act ? launch_gemm<FL, true, false, EP_STORE>(who, g, st, g_force_tn, g_force_ksw) : launch_gemm<FL, false, false, EP_STORE>(who, g, st, g_force_tn, g_force_ksw)))
+    const int rc = flush_k == 0 ? FWD(0) : flush_k == 8 ? FWD(8) : FWD(32);
 #undef FWD
-    return check_launch("pcl_frag_linear_fwd_f32");
+    return rc;
 }
 
 extern "C" int pcl_frag_dy_f32(const float* dU, const float* Y, const float* a, const float* k1, const float* k2, const float* mu,
@@ -663,8 +639,7 @@ extern "C" int pcl_frag_dy_f32(const float* dU, const float* Y, const float* a, 
     PCL_REQUIRE(Y && a && k1 && k2 && mu && dy && P >= 1 && C >= 4 && C % 4 == 0, "pcl_frag_dy_f32: bad arguments (C must be a multiple of 4)");
     PCL_REQUIRE((dU != nullptr) != (arg != nullptr && gz != nullptr), "pcl_frag_dy_f32: pass dU or (arg, gz)");
     PCL_REQUIRE(dU || ns >= 1, "pcl_frag_dy_f32: ns = %d", ns);
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    PCL_REQUIRE(al16(Y) && al16(a) && al16(k1) && al16(k2) && al16(mu) && al16(dy) && (!dU || al16(dU)) && (!gz || (al16(gz) && al16(arg))),
+    PCL_REQUIRE(al16(Y, a, k1, k2, mu, dy, dU) && (!gz || al16(gz, arg)),
                 "pcl_frag_dy_f32: operands must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     if (zero_words && n_zero > 0) {
@@ -691,9 +666,9 @@ extern "C" int pcl_frag_linear_bwd_dx_f32(const float* dy, const float* W, int l
     GemmArgs g = {};
     g.A = dy; g.lda = Cout; g.B = W; g.ldb = ldw; g.C = dUprev; g.ldc = ldu; g.stats = stats_ws; g.M = P; g.N = Cin; g.K = Cout; g.n_begin = first_col;
     g.Yp = Yprev; g.ldyp = ldyp; g.esc = prev_scale; g.esh = prev_shift; g.eslope = prev_slope;
-    if (Yprev) launch_gemm<0, false, true, EP_MASK_STATS>(g, st, g_force_tn, g_force_ksw);
-    else launch_gemm<0, false, true, EP_STORE>(g, st, g_force_tn, g_force_ksw);
-    return check_launch("pcl_frag_linear_bwd_dx_f32");
+    const char* who = "pcl_frag_linear_bwd_dx_f32";
+    if (Yprev) return launch_gemm<0, false, true, EP_MASK_STATS>(who, g, st, g_force_tn, g_force_ksw);
+    return launch_gemm<0, false, true, EP_STORE>(who, g, st, g_force_tn, g_force_ksw);
 }
 
 extern "C" size_t pcl_frag_dw_workspace_bytes(int P, int Cout, int Cin) {
@@ -733,9 +708,9 @@ extern "C" int pcl_frag_linear_bwd_dw_f32(const float* dy, const float* X, int l
     d.part = part; d.counters = counters; d.M = P; d.I = Cout; d.J = Cin; d.nti = s.nti; d.ntj = s.ntj; d.ksg = s.ksg;
     const dim3 grid((unsigned)(tiles * s.ksg)), blk(256 * s.ksw);
     const size_t lds = (size_t)4 * s.tm * s.tn * 16 * 64 * 4;
-    if (s.tm == 1 && s.tn == 1) FG_LAUNCH((frag_dw_kernel<1, 1>), grid, blk, lds, st, d);
-    else if (s.tm == 1 && s.tn == 2) FG_LAUNCH((frag_dw_kernel<1, 2>), grid, blk, lds, st, d);
-    else if (s.tm == 2 && s.tn == 1) FG_LAUNCH((frag_dw_kernel<2, 1>), grid, blk, lds, st, d);
-    else FG_LAUNCH((frag_dw_kernel<2, 2>), grid, blk, lds, st, d);
+    if (s.tm == 1 && s.tn == 1) PCL_LAUNCH_TIMED_LDS((frag_dw_kernel<1, 1>), grid, blk, lds, st, d);
+    else if (s.tm == 1 && s.tn == 2) PCL_LAUNCH_TIMED_LDS((frag_dw_kernel<1, 2>), grid, blk, lds, st, d);
+    else if (s.tm == 2 && s.tn == 1) PCL_LAUNCH_TIMED_LDS((frag_dw_kernel<2, 1>), grid, blk, lds, st, d);
+    else PCL_LAUNCH_TIMED_LDS((frag_dw_kernel<2, 2>), grid, blk, lds, st, d);
     return check_launch("pcl_frag_linear_bwd_dw_f32");
 }

@@ -501,7 +501,7 @@ __global__ __launch_bounds__(256) void head_dx_mfma_kernel(const float* __restri
 
 // the 8-columns-per-workgroup kernels: few rows, a long reduction, 16-byte rows
 static bool head_wide(int R, int K, const float* X, const float* W) {
-    return R <= 32 && K >= 2048 && K % 4 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W)) & 15) == 0;
+    return R <= 32 && K >= 2048 && K % 4 == 0 && al16(X, W);
 }
 
 }  // namespace pcl
@@ -525,7 +525,7 @@ static int head_layer_fwd_impl(const float* X, const float* W, const float* bias
     if (head_wide(R, K, X, W)) {
         const int KS = head_wide_ks(K), kper = ((K + KS - 1) / KS + HM_KC - 1) / HM_KC * HM_KC;
         const size_t need = (size_t)KS * 32 * N * sizeof(float);
-        if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        if (!workspace || workspace_bytes < need || !al16(workspace))
             return fail(PCL_EWS, "pcl_head_layer_fwd_f32: workspace %zu < %zu (pcl_head_layer_fwd_workspace_bytes; 16-byte aligned)", workspace ? workspace_bytes : (size_t)0, need);
         float* part = static_cast<float*>(workspace);
         hipLaunchKernelGGL(head_fwd_part_kernel, dim3((N + 31) / 32, KS), block, 0, st, X, W, R, K, N, kper, part);

@@ -235,10 +235,7 @@ int launch_infer(const char* fn, InferArgs a, hipStream_t st) {
     a.GT = GT;
     const size_t lds = S::lds_bytes(GT);
     auto kern = sa_level_infer_kernel<C1, C2, C3, BF16>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PCL_EHIP, "%s: hipFuncSetAttribute(%zu): %s", fn, lds, hipGetErrorString(e));
-    }
+    if (int rc = lds_opt_in(kern, lds, fn)) return rc;
     const int blocks = (a.G + GT - 1) / GT;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(IF_T), lds, st, a);
     return check_launch(fn);
@@ -290,9 +287,9 @@ int sa_level_infer(const char* fn, const float* xyz, const float* new_xyz, const
     for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", fn, l);
     const int CL = widths[L - 1];
     PCL_REQUIRE(col0 >= 0 && ldo >= col0 + CL, "%s: ldo=%d col0=%d for %d channels", fn, ldo, col0, CL);
-    bool al16 = (reinterpret_cast<uintptr_t>(Uf) & 15) == 0;
-    for (int l = 1; l < L; ++l) al16 = al16 && (reinterpret_cast<uintptr_t>(W[l]) & 15) == 0;
-    PCL_REQUIRE(al16, "%s: Uf and the weights must be 16-byte aligned", fn);
+    bool aligned = al16(Uf);
+    for (int l = 1; l < L; ++l) aligned = aligned && al16(W[l]);
+    PCL_REQUIRE(aligned, "%s: Uf and the weights must be 16-byte aligned", fn);
     InferArgs a = {};
     a.xyz = xyz; a.new_xyz = new_xyz; a.Uf = Uf; a.Wx = Wx; a.fs = feat_small; a.Wfs = Wf_small; a.CF = CF; a.ldw = ldw;
     a.idx = idx; a.cnt = cnt; a.G = B * m; a.N = N; a.m = m; a.ns = ns;

@@ -191,10 +191,7 @@ int launch_fp(const char* who, const FpArgs& a, hipStream_t st) {
     constexpr size_t lds = S::lds_bytes;
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
     auto kern = fp_level_infer_kernel<L, C1, C2, C3, C4, C5, RAGGED>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PCL_EHIP, "%s: hipFuncSetAttribute(%zu): %s", who, lds, hipGetErrorString(e));
-    }
+    if (int rc = lds_opt_in(kern, lds, who)) return rc;
     const int blocks = (a.R + FP_RT - 1) / FP_RT;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(FP_T), lds, st, a);
     return check_launch(who);
@@ -244,9 +241,9 @@ static int fp_run(const char* who, const float* Us, const float* skip_small, con
     PCL_REQUIRE(ldo >= CL, "%s: ldo=%d for %d channels", who, ldo, CL);
     PCL_REQUIRE(!tap || (tap_layer >= 1 && tap_layer <= L - 2 && ldt >= w[tap_layer]),
                 "%s: tap_layer=%d (an intermediate MFMA layer, 1..L-2) ldt=%d", who, tap_layer, ldt);
-    bool al16 = ((reinterpret_cast<uintptr_t>(Us) | reinterpret_cast<uintptr_t>(Uc) | reinterpret_cast<uintptr_t>(cloud_bias)) & 15) == 0;
-    for (int l = 1; l < L; ++l) al16 = al16 && (reinterpret_cast<uintptr_t>(W[l]) & 15) == 0;
-    PCL_REQUIRE(al16, "%s: Us, Uc, cloud_bias and the weights must be 16-byte aligned", who);
+    bool aligned = al16(Us, Uc, cloud_bias);
+    for (int l = 1; l < L; ++l) aligned = aligned && al16(W[l]);
+    PCL_REQUIRE(aligned, "%s: Us, Uc, cloud_bias and the weights must be 16-byte aligned", who);
     FpArgs a = {};
     a.Us = Us; a.fs = skip_small; a.Wfs = Ws_small; a.CS = CS; a.ldw = ldw;
     a.Uc = Uc; a.idx3 = idx3; a.w3 = w3; a.S = S; a.cb = cloud_bias;

@@ -586,7 +586,7 @@ extern "C" int pcl_knn_point_matmul_f32(const float* xyz, const float* new_xyz, 
     PCL_REQUIRE(xyz && new_xyz && idx_out, "pcl_knn_point_matmul_f32: null pointer");
     PCL_REQUIRE(B >= 0 && N >= 1 && S >= 1 && k >= 1 && k <= N, "pcl_knn_point_matmul_f32: bad sizes B=%d N=%d S=%d k=%d", B, N, S, k);
     PCL_REQUIRE(B <= 65535 && N <= KNN_FUSED_MAX_NR, "pcl_knn_point_matmul_f32: B=%d (<= 65535), N=%d (<= %d: the references of a cloud live in one wave's registers)", B, N, KNN_FUSED_MAX_NR);
-    PCL_REQUIRE((reinterpret_cast<uintptr_t>(xyz) & 15) == 0 && ((size_t)N * 12) % 16 == 0, "pcl_knn_point_matmul_f32: xyz must be 16-byte aligned and N a multiple of 4");
+    PCL_REQUIRE(al16(xyz) && ((size_t)N * 12) % 16 == 0, "pcl_knn_point_matmul_f32: xyz must be 16-byte aligned and N a multiple of 4");
     if (B == 0) return PCL_OK;
     hipStream_t st = as_stream(stream);
     const int ppt4 = (N + 255) / 256 * 4;

@@ -1745,10 +1745,8 @@ static bool fwd_res_eligible(const LinArgs& a) {
     if (!path_switches().fwd_resident || (a.a_mode != A_BNACT && a.a_mode != A_PLAIN) || a.e_mode != E_STORE_STATS || a.gmax || a.n_begin != 0 || a.ldc != a.N) return false;
     if (!((a.K == 64 && (a.N == 64 || a.N == 128)) || (a.K == 128 && (a.N == 128 || a.N == 256)))) return false;
     if (a.M < 32768 || (size_t)a.M * (size_t)(a.N > a.K ? a.N : a.K) * 4 >= 0xffffffffull) return false;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (!al16(a.bias)) return false;
-    if (a.a_mode == A_PLAIN) return al16(a.A) && al16(a.B);
-    return al16(a.A) && al16(a.B) && al16(a.sc) && al16(a.sh) && a.slope >= 0.f && a.slope <= 1.f;
+    if (!al16(a.bias, a.A, a.B)) return false;
+    return a.a_mode == A_PLAIN || (al16(a.sc, a.sh) && a.slope >= 0.f && a.slope <= 1.f);
 }
 template <int CI, int NS>
 static int launch_fwd_res_t(const FrArgs& f, bool rag, hipStream_t st) {
@@ -1774,7 +1772,8 @@ static int launch_fwd_split_t(const FrArgs& f, bool rag, hipStream_t st) {
 static int g_split_mfma = 0;               // bit 0: the resident-operand forward, bit 1: the staged GEMMs with K >= g_split_min_k
 static int g_split_min_k = 128;
 static bool fwd_split_on() { return (g_split_mfma & 1) != 0; }
-static int fr_cu_count();
+// the CU count the persistent kernels size their grids by (the partial-tile workspace and the 256-row statistics are sized for <= 256)
+static int fb_cu_count() { const int n = cu_count(); return n > 256 ? 256 : n; }
 static int launch_fwd_res(const LinArgs& a, int stat_rows, hipStream_t st) {
     FrArgs f = {};
     f.X = a.A; f.W = a.B; f.bias = a.bias; f.sc = a.a_mode == A_PLAIN ? nullptr : a.sc; f.sh = a.a_mode == A_PLAIN ? nullptr : a.sh; f.slope = a.slope; f.Y = a.C; f.stats = a.stats;
@@ -1783,7 +1782,7 @@ static int launch_fwd_res(const LinArgs& a, int stat_rows, hipStream_t st) {
     const bool split = fwd_split_on() || ((g_split_mfma & 4) && a.K == 128 && a.N == 256);
     f.nt = split ? 1 : a.N / NS;
     const int tiles = (a.M + R - 1) / R;
-    int gx = fr_cu_count() / f.nt;                       // one workgroup per CU in all
+    int gx = fb_cu_count() / f.nt;                       // one workgroup per CU in all
     if (gx > tiles) gx = tiles;
     if (gx > stat_rows) gx = stat_rows;
     if (gx < 1) gx = 1;
@@ -2535,16 +2534,6 @@ __global__ __launch_bounds__(FB_T) void linear_bwd_fused_kernel(const FbArgs p_i
 // setting made BETWEEN calls: it sizes the statistics rows, the workspace and the finish reduction of every later call.
 static int g_fb_cap = 0;
 static int g_fb_two = 1;                 // the 128 x 64 shape on two tile images (pcl_set_fb_two_images)
-static int fb_cu_count() {
-    static const int n = [] {
-        int dev = 0, cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu < 1) cu = 256;
-        (void)hipGetLastError();
-        return cu > 256 ? 256 : cu;          // (the partial-tile workspace and the 256-row statistics are sized for <= 256)
-    }();
-    return n;
-}
-static int fr_cu_count() { return fb_cu_count(); }
 static int fb_grid(int P, int Cin) {
     const int R = fb_rows(Cin), tiles = (P + R - 1) / R;
     const int cus = fb_cu_count();
@@ -3062,8 +3051,7 @@ static void linear_grid(int M, int N, bool bwd, bool rag, int& gx, int& n_tiles,
 template <int AM, int EM, int GM = 0, bool RAG = false>
 static int launch_linear_t(const LinArgs& a_in, hipStream_t st) {
     LinArgs a = a_in;
-    const bool vec = (a.K % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.A) & 15) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(a.B) & 15) == 0) && (!a.A2 || (reinterpret_cast<uintptr_t>(a.A2) & 15) == 0) &&
+    const bool vec = (a.K % 4 == 0) && al16(a.A, a.B, a.A2) &&
                      (AM < A_DY || a.ldb % 4 == 0);
     int gx, n_tiles; bool narrow, low;
     linear_grid(a.M, a.N - a.n_begin, AM >= A_DY, RAG, gx, n_tiles, narrow, low);
@@ -3226,9 +3214,6 @@ __global__ __launch_bounds__(256) void group_minmax_finalize_t_kernel(const floa
     }
 }
 
-extern "C" int pcl_group_minmax_finalize2_f32(const float* gmax, const float* gmin, const int32_t* gamax, const int32_t* gamin,
-                                              const float* scale, const float* shift, float slope, int G, int C, float* out,
-                                              int32_t* arg, float* ymax, float* out2, int out2_ld, void* stream);
 extern "C" int pcl_group_minmax_finalize_t_f32(const float* gmax, const float* gmin, const int32_t* gamax, const int32_t* gamin,
                                                const float* scale, const float* shift, float slope, int B, int N, int C, float* out,
                                                int32_t* arg, float* ymax, float* out2, int out2_ld, float* out_t, void* stream) {
@@ -3258,12 +3243,6 @@ extern "C" int pcl_group_minmax_finalize2_f32(const float* gmax, const float* gm
                        shift, slope, C, total, out, arg, ymax, out2, out2_ld);
     return check_launch("pcl_group_minmax_finalize_f32");
 }
-
-extern "C" int pcl_linear_bwd_dx_rows_f32(const float* dU, const float* Y, const float* a_, const float* k1, const float* k2, const float* mu,
-                                          const int32_t* arg, const float* gz, int ns, const float* W, int P, int Cout,
-                                          int Cin, const float* Yprev, const float* prev_scale, const float* prev_shift,
-                                          float prev_slope, float* dUprev, double* stats_ws, const int32_t* row_meta,
-                                          const int32_t* n_rows_dev, int first_col, int cin_stride, void* stream);
 
 extern "C" int pcl_linear_bwd_dx_f32(const float* dU, const float* Y, const float* a_, const float* k1, const float* k2, const float* mu,
                                      const int32_t* arg, const float* gz, int ns, const float* W, int P, int Cout,
@@ -3300,12 +3279,6 @@ extern "C" size_t pcl_linear_bwd_dw_workspace_bytes(int P, int Cout, int Cin) {
     return sizeof(float) * (size_t)gx * Cout * Cin;
 }
 
-extern "C" int pcl_linear_bwd_dw_rows_f32(const float* dU, const float* Y, const float* a_, const float* k1, const float* k2, const float* mu,
-                                          const int32_t* arg, const float* gz, int ns, const float* Xprev,
-                                          const float* prev_scale, const float* prev_shift, float prev_slope, int P, int Cout,
-                                          int Cin, float* dW, void* workspace, size_t workspace_bytes, const int32_t* row_meta,
-                                          const int32_t* n_rows_dev, int dw_ld, void* stream);
-
 extern "C" int pcl_linear_bwd_dw_f32(const float* dU, const float* Y, const float* a_, const float* k1, const float* k2, const float* mu,
                                      const int32_t* arg, const float* gz, int ns, const float* Xprev,
                                      const float* prev_scale, const float* prev_shift, float prev_slope, int P, int Cout,
@@ -3335,8 +3308,7 @@ extern "C" int pcl_linear_bwd_dw_rows_f32(const float* dU, const float* Y, const
     d.part = static_cast<float*>(workspace); d.P = P; d.I = Cout; d.J = Cin;
     d.rmeta = reinterpret_cast<const int2*>(row_meta); d.p_dev = n_rows_dev;
     d.a_mode = dU ? A_DY : A_DY_SPARSE; d.b_mode = prev_scale ? A_BNACT : A_PLAIN;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool vec = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(Y) && al16(Xprev) && (!dU || al16(dU)) && (!gz || (al16(gz) && al16(arg)));
+    const bool vec = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(Y, Xprev, dU) && (!gz || al16(gz, arg));
     d.gx = gx; d.ti = ti; d.tj = tj; d.ldo = Cin;
     // one row-chunk workgroup per output tile (few rows, a large weight: the per-point Linear of PointConv's GroupAll
     // level is 32 x 16384 -> 1024): nothing to reduce, the tiles go straight into dW instead of through the workspace
@@ -3397,10 +3369,9 @@ extern "C" int pcl_linear_bwd_pair_f32(const float* dU, const float* Y, const fl
     int gxl, n_tiles; bool narrow, low;
     linear_grid(P, Cin - first_col, true, false, gxl, n_tiles, narrow, low);
     a.gx = gxl; a.nt = n_tiles;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     // the two bodies' vector paths have different preconditions; the pair runs both on the same path (scalar when either needs it)
-    const bool vec_dw = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(Y) && al16(Xprev) && (!dU || al16(dU)) && (!gz || (al16(gz) && al16(arg)));
-    const bool vec_nt = (a.K % 4 == 0) && al16(a.A) && al16(a.B) && al16(a.A2) && a.ldb % 4 == 0;
+    const bool vec_dw = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(Y, Xprev, dU) && (!gz || al16(gz, arg));
+    const bool vec_nt = (a.K % 4 == 0) && al16(a.A, a.B, a.A2) && a.ldb % 4 == 0;
     const int n_dw = gx * ti * tj;
     if (vec_dw != vec_nt) {
         // (an operand aligned for one body's vector path only: the two plain launches, each on its own path -- the finish launch still sums the tiles)
@@ -3479,8 +3450,7 @@ extern "C" int pcl_bn_bwd_dy_f32(const double* stats_ws, int stat_rows, const fl
     PCL_REQUIRE(stat_rows >= 1 && P_bn >= 1 && pcl_bn_bwd_dy_supported(P, C), "pcl_bn_bwd_dy_f32: bad sizes P=%d C=%d (C must be a multiple of 32) stat_rows=%d", P, C, stat_rows);
     PCL_REQUIRE((dU != nullptr) != (arg != nullptr && gz != nullptr), "pcl_bn_bwd_dy_f32: pass dU or (arg, gz)");
     PCL_REQUIRE(dU || ns >= 1, "pcl_bn_bwd_dy_f32: ns = %d", ns);
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    PCL_REQUIRE(al16(Y) && al16(dy) && (!dU || al16(dU)) && (!gz || (al16(gz) && al16(arg))), "pcl_bn_bwd_dy_f32: operands must be 16-byte aligned");
+    PCL_REQUIRE(al16(Y, dy, dU) && (!gz || al16(gz, arg)), "pcl_bn_bwd_dy_f32: operands must be 16-byte aligned");
     BnDyArgs a = {};
     a.q = BnConstsArgs{stats_ws, stat_rows, gamma, mean, invstd, P_bn, C, dgamma, dbeta, a_out, k1, k2, dbias_zero};
     a.dU = dU; a.Y = Y; a.arg = arg; a.gz = gz; a.ns = ns; a.dy = dy; a.M = P;
@@ -3521,8 +3491,7 @@ extern "C" int pcl_linear_bwd_dw_plain_f32(const float* dy, const float* Xprev, 
     d.A = dy; d.Bsrc = Xprev; d.bsc = prev_scale; d.bsh = prev_shift; d.bslope = prev_slope;
     d.part = static_cast<float*>(workspace); d.P = P; d.I = Cout; d.J = Cin;
     d.a_mode = A_PLAIN; d.b_mode = prev_scale ? A_BNACT : A_PLAIN;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool vec = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(dy) && al16(Xprev);
+    const bool vec = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(dy, Xprev);
     d.gx = gx; d.ti = ti; d.tj = tj; d.ldo = Cin;
     const bool direct = gx == 1;
     if (direct) { d.part = dW; d.ldo = dw_ld ? dw_ld : Cin; }
@@ -3592,8 +3561,7 @@ extern "C" int pcl_linear_bwd_fused_rows_f32(const float* dU, const float* Y, co
     PCL_REQUIRE((row_meta == nullptr) == (n_rows_dev == nullptr), "pcl_linear_bwd_fused_rows_f32: row_meta and n_rows_dev come together");
     PCL_REQUIRE(prev_slope >= 0.f && prev_slope <= 1.f, "pcl_linear_bwd_fused_rows_f32: slope %f outside [0,1]", prev_slope);
     PCL_REQUIRE((size_t)P * (size_t)(Cout > Cin ? Cout : Cin) * 4 < 0xffffffffull, "pcl_linear_bwd_fused_rows_f32: tensors beyond 4 GiB need the two-kernel path");
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    PCL_REQUIRE(al16(Y) && al16(W) && al16(Yprev) && al16(a_) && al16(k1) && al16(k2) && al16(mu) && (!dU || al16(dU)) && (!gz || (al16(gz) && al16(arg))),
+    PCL_REQUIRE(al16(Y, W, Yprev, a_, k1, k2, mu, dU) && (!gz || al16(gz, arg)),
                 "pcl_linear_bwd_fused_rows_f32: operands must be 16-byte aligned");
     const size_t need = pcl_linear_bwd_fused_workspace_bytes(P, Cout, Cin);
     if (!workspace || workspace_bytes < need) return fail(PCL_EWS, "pcl_linear_bwd_fused_rows_f32: workspace %zu < %zu", workspace_bytes, need);
@@ -3715,7 +3683,7 @@ int pcl::maxgrad_prep_impl(const float* gout, const float* out, const float* yma
                            int* stat_rows_out, void* stream, float* zero, size_t n_zero, float* ones, int n_one, int n_one0, int ldg) {
     PCL_REQUIRE(gout && out && ymax && gz && stats_ws && stat_rows_out, "pcl_maxgrad_prep_f32: null pointer");
     PCL_REQUIRE(ldg >= C, "pcl_maxgrad_prep_f32: gout row stride %d below the width %d", ldg, C);
-    PCL_REQUIRE(!zero || ((reinterpret_cast<uintptr_t>(zero) & 15) == 0 && n_zero % 4 == 0), "pcl_maxgrad_prep_f32: the zero-fill region must be 16-byte aligned and a multiple of 4 floats");
+    PCL_REQUIRE(!zero || (al16(zero) && n_zero % 4 == 0), "pcl_maxgrad_prep_f32: the zero-fill region must be 16-byte aligned and a multiple of 4 floats");
     const PrepAux aux = {reinterpret_cast<float4*>(zero), n_zero / 4, ones, n_one, n_one0};
     PCL_REQUIRE(G >= 1 && C >= 1, "pcl_maxgrad_prep_f32: bad sizes");
     int CW = 256;

@@ -550,20 +550,14 @@ using namespace pcl;
 // groups per wave and 16-row blocks per pass of the weight-gradient kernel
 static int bwd_w_gpw(int ns) { return ns <= 32 ? 2 : 1; }
 static int bwd_w_max_wgs(int slices) {
-    static const int cus = [] {
-        int dev = 0, cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu < 1) cu = 256;
-        (void)hipGetLastError();
-        return cu;
-    }();
-    const int n = 2 * cus / (slices < 1 ? 1 : slices);
+    const int n = 2 * cu_count() / (slices < 1 ? 1 : slices);
     return n < 1 ? 1 : n;
 }
 static int g_bwd_w_rows = 1;             // lab switch (pcl_set_pointconv_paths)
 extern "C" void pcl_set_pointconv_paths(int bwd_w_rows) { if (bwd_w_rows >= 0) g_bwd_w_rows = bwd_w_rows != 0; }
 static void launch_bwd_w(int slices, hipStream_t st, const float* feat, const float* dout, const float* dens, const float* w, int G, int ns, int C,
                          float* dw, float* ddens, const FeatBN bn) {
-    if (g_bwd_w_rows && C % 4 == 0 && ns <= 64 && (size_t)ns * C * 4 < 0x7fffffffull && ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(dout)) & 15) == 0) {
+    if (g_bwd_w_rows && C % 4 == 0 && ns <= 64 && (size_t)ns * C * 4 < 0x7fffffffull && al16(feat, dout)) {
         // row-major LDS image, a wave per group (ns <= 64: the GroupAll level's 128-row groups keep the kernel above)
         int wgs = (G + 3) / 4;
         const int cap = 3 * bwd_w_max_wgs(slices) / 2;                   // persistent: three workgroups per CU (LDS: 26 / 45 KB each)
@@ -630,7 +624,7 @@ extern "C" int pcl_pointconv_contract_bn_bwd_f32(const float* dout, const float*
     PCL_REQUIRE(dout && Y && scale && shift && density && weights && du && dweights && ddensity && stats_ws, "pcl_pointconv_contract_bn_bwd_f32: null pointer");
     PCL_REQUIRE(G >= 1 && ns >= 1 && C >= 1 && M == PC_M && slope >= 0.f && slope <= 1.f, "pcl_pointconv_contract_bn_bwd_f32: bad sizes G=%d ns=%d C=%d M=%d", G, ns, C, M);
     PCL_REQUIRE((size_t)ns * C * 4 < 0x7fffffffull && (size_t)C * PC_M * 4 < 0x7fffffffull, "pcl_pointconv_contract_bn_bwd_f32: a group of ns=%d x C=%d floats is beyond the kernels' 32-bit group offsets", ns, C);
-    PCL_REQUIRE(C % 4 != 0 || ((reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15) == 0, "pcl_pointconv_contract_bn_bwd_f32: scale / shift must be 16-byte aligned");
+    PCL_REQUIRE(C % 4 != 0 || al16(scale, shift), "pcl_pointconv_contract_bn_bwd_f32: scale / shift must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     const FeatBN bn = {scale, shift, slope};
     const int rows = pcl_pointconv_contract_bn_stat_rows(G);

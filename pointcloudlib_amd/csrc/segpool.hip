@@ -189,7 +189,6 @@ __global__ __launch_bounds__(64 * SL) void seg_sum_kernel(const float* __restric
 }  // namespace pcl
 using namespace pcl;
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static int seg_sizes_ok(const char* who, int B, int C, int n_rows) {
     PCL_REQUIRE(B >= 1 && B <= 65535 && C >= 1, "%s: bad sizes B=%d C=%d (1 <= B <= 65535: grid.y)", who, B, C);
@@ -212,7 +211,7 @@ extern "C" int pcl_bn_act_seg_max_f32(const float* Y, const int32_t* row_off, co
     PCL_REQUIRE(Y && row_off && scale && shift && out && arg, "%s: null pointer", who);
     if (int rc = seg_sizes_ok(who, B, C, n_rows)) return rc;
     const dim3 grid((C + 63) / 64, B);
-    const bool vec = C % 4 == 0 && aligned16(Y) && aligned16(scale) && aligned16(shift);
+    const bool vec = C % 4 == 0 && al16(Y, scale, shift);
     const bool wide = n_rows / B >= 256;                               // the mean cloud: 16 waves per workgroup, else 4
     hipStream_t st = as_stream(stream);
 #define SP_MAX(SL, VEC) hipLaunchKernelGGL((bn_act_seg_max_kernel<SL, VEC>), grid, dim3(64 * SL), 0, st, Y, row_off, scale, shift, slope, C, n_rows, out, arg)
@@ -245,7 +244,7 @@ extern "C" int pcl_seg_broadcast_rows_f32(const float* src, const int32_t* row_c
     PCL_REQUIRE(src && row_cloud && dst, "%s: null pointer", who);
     if (int rc = seg_sizes_ok(who, B, C, n_rows)) return rc;
     if (n_rows == 0) return PCL_OK;
-    const bool vec = C % 4 == 0 && aligned16(src) && aligned16(dst);
+    const bool vec = C % 4 == 0 && al16(src, dst);
     const size_t total = (size_t)n_rows * (vec ? C / 4 : C);
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     if (vec) hipLaunchKernelGGL(seg_broadcast_kernel<true>, dim3(blocks), dim3(256), 0, as_stream(stream), src, row_cloud, B, C, total, dst);

@@ -69,6 +69,11 @@ FWD_CASES = [
     (640, 64, 200, True, False, (2, 4)),         # K split over four wave groups, 8 steps in all
     (130, 1024, 64, True, False, (1, 4)),
     (8192, 576, 256, False, False, (0, 0)),      # fp2 of the MSG decoder
+    # the folded BatchNorm's constants, 2 * (K / 8 + 4) * 32 B, beside the 16 KB (flushed: 32 KB) reduction buffer pass the 64 KB of dynamic LDS
+    # a kernel gets unasked; in this order the same kernels' limit is raised twice within one process
+    (130, 4608, 64, True, False, (1, 1)),        # 52.3 KB plain, 68.3 KB flushed: only flush 8 / 32 ask for more
+    (130, 6656, 64, True, False, (0, 0)),        # 68.3 KB / 84.3 KB: all three accumulation modes
+    (130, 8192, 64, True, False, (0, 0)),        # the entry point's largest Cin: 80.3 KB / 96.3 KB
 ]
 
 

@@ -103,7 +103,8 @@ def test_fps_properties_full_size(dev):
 # ------------------------------------------------------------------------------------ ball query
 @pytest.mark.parametrize("B,N,m,r,ns", [(2, 64, 10, 0.3, 8), (3, 1000, 77, 0.2, 64), (32, 1024, 512, 0.2, 64),
                                         (32, 512, 128, 0.4, 64), (2, 4096, 512, 0.1, 16), (2, 2048, 512, 0.4, 128),
-                                        (1, 14000, 33, 0.15, 32)])
+                                        (1, 14000, 33, 0.15, 32),
+                                        (1, 5504, 32, 0.15, 4)])     # (5504 points: 66 048 B of LDS, past the 64 KB a kernel gets unasked)
 def test_ball_query_matches_oracle(oracle, dev, B, N, m, r, ns):
     pts = synth.gauss_ball(B, N, 11 + N)
     q = oracle.fps(pts, m, block_size=1, return_xyz=True)[1]
@@ -365,7 +366,8 @@ def test_knn_point_matmul_form_matches_oracle(oracle, dev, B, N, S, k):
 
 @pytest.mark.parametrize("B,N,m,radii,ns", [(4, 2048, 512, [0.1, 0.2, 0.4], [16, 32, 128]), (3, 512, 128, [0.2, 0.4, 0.8], [32, 64, 128]),
                                             (2, 1000, 77, [0.05, 10.0], [8, 4]), (2, 300, 300, [0.3], [16]),
-                                            (1, 64, 5, [1e-6, 0.2, 0.25, 0.3], [4, 1, 70, 64])])
+                                            (1, 64, 5, [1e-6, 0.2, 0.25, 0.3], [4, 1, 70, 64]),
+                                            (1, 5504, 32, [0.1, 0.2], [4, 4])])     # (66 048 B of LDS: past the 64 KB a kernel gets unasked)
 def test_ball_query_multi_equals_one_query_per_radius(oracle, dev, B, N, m, radii, ns):
     """pcl_ball_query_multi_f32 (multi-scale grouping: every scale's list out of one scan of the cloud) against pcl_ball_query_f32 per
     radius and against the oracle: lists and counts identical, including radii with no hit at all, radii that fill their list in the
