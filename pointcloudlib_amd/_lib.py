@@ -133,6 +133,44 @@ def define(name):
     return _DEFINES[name]
 
 
+# ---------------------------------------------------------------- lab switches (csrc/common.h: LabSwitches; the table in DESIGN.md section 1)
+# The environment is read HERE (host side) and handed over as C calls -- the library itself reads none.  One row per variable:
+# (variable, setter, its arguments), an argument being a number (-1: "leave as is") or how the variable's text becomes one.
+def _on(text):
+    return int(text != "0")
+
+
+_ENV_SWITCHES = (("PCL_FWD_RES", "pcl_set_kernel_paths", (_on, -1, -1)),
+                 ("PCL_NARROW", "pcl_set_kernel_paths", (-1, _on, -1)),
+                 ("PCL_FUSED_BWD", "pcl_set_kernel_paths", (-1, -1, _on)),
+                 ("PCL_SIDE_DW", "pcl_set_stack_overlap", (_on, -1)),
+                 ("PCL_BWD_W_ROWS", "pcl_set_pointconv_paths", (_on,)),
+                 ("PCL_SCATTER", "pcl_set_scatter_form", (_on,)),
+                 ("PCL_BWD_PAIR", "pcl_set_bwd_pair", (_on,)),
+                 ("PCL_FB_TWO", "pcl_set_fb_two_images", (_on,)),
+                 ("PCL_FEWROW", "pcl_set_fewrow_backward", (_on,)),
+                 ("PCL_DW_GX", "pcl_set_dw_tuning", (int,)))
+# Several size queries answer by the switches, so whatever the host keeps of such an answer is dropped whenever a setter runs:
+# lib() puts a Python function over every setter of the header that calls it and then the registered invalidators.  Setters are
+# never called on a launch path.
+_SWITCH_SETTERS = [n for n in _SIGS if n.startswith("pcl_set_") or n == "pcl_frag_set_tuning"]
+_INVALIDATORS = []
+
+
+def on_switch_change(fn):
+    """Register ``fn()`` to run after every lab-switch setter (a cache whose contents depend on a switch registers its clear)."""
+    _INVALIDATORS.append(fn)
+    return fn
+
+
+def _invalidating(setter):
+    def set_and_invalidate(*args):
+        setter(*args)
+        for fn in _INVALIDATORS:
+            fn()
+    return set_and_invalidate
+
+
 def lib():
     """The loaded library; raises PclError when it has not been built."""
     global _lib
@@ -150,24 +188,11 @@ def lib():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
-        # lab switches of the kernel selection: read HERE (host side) and handed over as a C call -- the library itself reads no environment
-        sw = [-1 if os.environ.get(k) is None else int(os.environ[k] != "0") for k in ("PCL_FWD_RES", "PCL_NARROW", "PCL_FUSED_BWD")]
-        if any(v >= 0 for v in sw):
-            L.pcl_set_kernel_paths(*sw)
-        if os.environ.get("PCL_SIDE_DW") is not None:
-            L.pcl_set_stack_overlap(int(os.environ["PCL_SIDE_DW"] != "0"), -1)
-        if os.environ.get("PCL_BWD_W_ROWS") is not None:
-            L.pcl_set_pointconv_paths(int(os.environ["PCL_BWD_W_ROWS"] != "0"))
-        if os.environ.get("PCL_SCATTER") is not None:
-            L.pcl_set_scatter_form(int(os.environ["PCL_SCATTER"] != "0"))
-        if os.environ.get("PCL_BWD_PAIR") is not None:
-            L.pcl_set_bwd_pair(int(os.environ["PCL_BWD_PAIR"] != "0"))
-        if os.environ.get("PCL_FB_TWO") is not None:
-            L.pcl_set_fb_two_images(int(os.environ["PCL_FB_TWO"] != "0"))
-        if os.environ.get("PCL_FEWROW") is not None:
-            L.pcl_set_fewrow_backward(int(os.environ["PCL_FEWROW"] != "0"))
-        if os.environ.get("PCL_DW_GX") is not None:
-            L.pcl_set_dw_tuning(int(os.environ["PCL_DW_GX"]))
+        for name in _SWITCH_SETTERS:
+            setattr(L, name, _invalidating(getattr(L, name)))
+        for var, setter, args in _ENV_SWITCHES:
+            if os.environ.get(var) is not None:
+                getattr(L, setter)(*(a(os.environ[var]) if callable(a) else a for a in args))
         _lib = L
     return _lib
 
@@ -314,6 +339,9 @@ class KernelTimer:
 def size_query(name, *ints):
     """Pure size functions of the ABI (``pcl_mlp_stat_rows``, ``pcl_linear_bwd_dw_workspace_bytes``, ...): asked once per shape."""
     return getattr(lib(), name)(*ints)
+
+
+on_switch_change(size_query.cache_clear)
 
 
 _FN = {}            # entry point name -> bound ctypes function

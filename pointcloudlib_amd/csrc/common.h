@@ -47,10 +47,26 @@ static inline hipStream_t as_stream(void* s) {
 // matches (an empty wanted tag matches anything).
 struct TimeHook { hipEvent_t start, stop; char want[32]; char cur[32]; const char* last_kernel; };
 TimeHook& time_hook();
-// Lab switches of the kernel selection (pcl_set_kernel_paths: a C call -- the library reads no environment variables):
-// resident-weight forward, recompute-per-pass narrow stacks, fused dX + dW backward.  All on by default.
-struct PathSwitches { int fwd_resident, narrow_stacks, fused_backward; };
-PathSwitches& path_switches();
+// Lab switches: every process-wide value that selects a kernel path or tunes a launch shape (DESIGN.md section 1 has the table).
+// The contract, once: the values are process-wide, changed only through the setters in capi.hip (C calls -- the library reads no
+// environment variables) BETWEEN calls of the library, and read unsynchronised by every call; several size queries answer by
+// them, so a host-side cache of such an answer is dropped whenever a setter runs (pointcloudlib_amd/_lib.py).
+struct LabSwitches {
+    int fwd_resident = 1, narrow_stacks = 1, fused_backward = 1;   // pcl_set_kernel_paths: resident-weight forward, recompute-per-pass narrow stacks, fused dX + dW backward
+    int side_dw = 0, side_dw_max_rows = 8192;                      // pcl_set_stack_overlap: few-row stacks' dW launches on the library's second stream
+    int fewrow = 0;                                                // pcl_set_fewrow_backward: constants + dy in one launch, dX and dW on the formed dy
+    int split_mfma = 0, split_min_k = 128;                         // pcl_set_matrix_form: 0 = fp32 MFMA; bit 0 the resident-operand forward, bit 1 the staged GEMMs with K >= split_min_k as three bf16 planes
+    int fb_cap = 0;                                                // pcl_set_fb_max_blocks: cap on the fused backward's persistent grid (0 = one workgroup per CU)
+    int fb_two = 1;                                                // pcl_set_fb_two_images: the fused backward's 128 x 64 shape on two tile images
+    int bwd_pair = 1;                                              // pcl_set_bwd_pair: 0 = the two launches + reduce of rounds 1-5
+    int dw_force_gx = 0;                                           // pcl_set_dw_tuning: row-chunk workgroups per output tile of the plain-dy dW (0 = the library's choice)
+    int bwd_w_rows = 1;                                            // pcl_set_pointconv_paths: PointConv weight gradient with the row-major LDS image
+    int scatter_gather = 1;                                        // pcl_set_scatter_form: 0 = the fp32-atomic scatter everywhere
+    int fps_threads = 0, fps_prio = 3;                             // pcl_set_fps_tuning: threads per cloud (0 = by N), issue priority
+    int frag_max_rows = 8192;                                      // pcl_frag_set_tuning: largest P for which a plain stack takes the fragment kernels ...
+    int force_tn = 0, force_ksw = 0, force_dw[4] = {0, 0, 0, 0};   // ... and its lab / test knobs (0 = the library's choice): column tiles, row groups, dW tm / tn / ksw / ksg
+};
+extern LabSwitches g_lab;
 void set_launch_tag(const char* tag);
 bool time_hook_matches(const TimeHook& h);
 #define PCL_LAUNCH_TIMED_LDS(kernel, grid, blk, lds, st, ...)                                                          \

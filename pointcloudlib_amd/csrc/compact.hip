@@ -883,9 +883,7 @@ extern "C" int pcl_group_rows_transpose_i32(const int32_t* row_src, const int32_
 }
 /* pcl_group_linear_bwd_f32 with the scatter as a gather over the points' row lists: dUf [B*N][C1] is WRITTEN (no zero-fill, no atomics),
  * dWx_part as there; C1 in {64, 128, 256}, 16-byte aligned rows */
-static int g_scatter_gather = 1;        // lab switch (pcl_set_scatter_form): 0 = the fp32-atomic scatter everywhere
-extern "C" void pcl_set_scatter_form(int gather) { if (gather >= 0) g_scatter_gather = gather != 0; }
-extern "C" int pcl_group_linear_bwd_gather_supported(int C1) { return g_scatter_gather && (C1 == 64 || C1 == 128 || C1 == 256); }
+extern "C" int pcl_group_linear_bwd_gather_supported(int C1) { return g_lab.scatter_gather && (C1 == 64 || C1 == 128 || C1 == 256); }
 extern "C" int pcl_group_linear_bwd_gather_f32(const float* row_loc, const float* dU, const float* Y, const float* a, const float* k1,
                                                const float* k2, const float* mu, const int32_t* in_off, const int32_t* in_rows, int B, int N,
                                                int C1, float* dUf, float* dWx_part, float* dW0, int ldw, void* stream) {

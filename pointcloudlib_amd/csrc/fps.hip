@@ -312,8 +312,6 @@ __global__ __launch_bounds__(T) void fps_kernel_lds(const float* __restrict__ xy
     }
 }
 
-static int g_fps_threads = 0, g_fps_prio = 3;       // pcl_set_fps_tuning (process-wide, set between calls)
-
 // LDS of the register kernel: 256 B of slots + (RT + 1) entries of 16 | 12 bytes (RT = the power of two the tie ranks live under, N <= RT < 2 N) + m ranks
 static size_t fps_lds_bytes(int N, int m, int log2S, int entry_floats) {
     int sh = 0;
@@ -328,7 +326,7 @@ static int launch_fps(const char* who, const float* xyz, const int32_t* n_valid,
     const size_t lds = fps_lds_bytes(N, m, log2S, T * PPT > 1024 ? 3 : 4);           // slots + rank-indexed xyz + sampled ranks
     auto kern = fps_kernel<T, PPT, RAGGED>;
     if (int rc = lds_opt_in(kern, lds, who)) return rc;
-    hipLaunchKernelGGL(kern, dim3(B), dim3(T), lds, st, xyz, n_valid, N, m, log2S, thr, start, idx, nx, g_fps_prio);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(T), lds, st, xyz, n_valid, N, m, log2S, thr, start, idx, nx, g_lab.fps_prio);
     return check_launch(who);
 }
 
@@ -349,7 +347,7 @@ static int fps_run(const char* who, const float* xyz, const int32_t* n_valid, in
     //  N = 512: 336 / 355 / 374 / - / -;  N = 1024: 479 / 410 / 381 / 416 / 736;  N = 2048: - / 550 / 450 / 475 / 766;  N = 4096: - / - / 589 / 611 / 869.
     //  One wave per cloud -- no barrier, no LDS exchange, DPP only -- wins up to 512 points; beyond, four waves: the cross-wave
     //  exchange costs less than the eight more distance evaluations per lane)
-    int T = g_fps_threads > 0 ? g_fps_threads : (N <= 512 ? 64 : N <= 4096 ? 256 : N <= 8192 ? 512 : 1024);
+    int T = g_lab.fps_threads > 0 ? g_lab.fps_threads : (N <= 512 ? 64 : N <= 4096 ? 256 : N <= 8192 ? 512 : 1024);
     const int ppt = (N + T - 1) / T;
 #define PCL_FPS_CASE(TT, PP) \
     if (T == TT && ppt <= PP) return launch_fps<TT, PP, RAGGED>(who, xyz, n_valid, B, N, m, log2S, skip_sqnorm_le, start_idx, idx_out, new_xyz_out, st);
@@ -383,11 +381,6 @@ extern "C" int pcl_lab_fps_read(long long* dst) {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_fps_ph), sizeof(g_fps_ph), 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 #endif
-
-extern "C" void pcl_set_fps_tuning(int threads_per_cloud, int issue_priority) {
-    g_fps_threads = threads_per_cloud > 0 ? threads_per_cloud : 0;
-    g_fps_prio = issue_priority < 0 ? 3 : issue_priority > 3 ? 3 : issue_priority;
-}
 
 extern "C" int pcl_fps_f32(const float* xyz, int B, int N, int m, int tie_stride, double skip_sqnorm_le,
                            const int32_t* start_idx, int32_t* idx_out, float* new_xyz_out, void* stream) {

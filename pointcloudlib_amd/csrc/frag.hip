@@ -562,14 +562,12 @@ static int launch_gemm(const char* who, GemmArgs g, hipStream_t st, int force_tn
     return launch_gemm_t<1, FLUSH, ACT, BKN, EP>(who, g, ksw, st);
 }
 
-static int g_force_tn = 0, g_force_ksw = 0, g_force_dw[4] = {0, 0, 0, 0};     // lab / test knobs (pcl_frag_set_tuning)
-
 // dW launch shape: tile (64 TM x 64 TN), KSW row groups per workgroup, KSG workgroups per tile
 struct DwShape { int tm, tn, ksw, ksg, nti, ntj; };
 static DwShape dw_shape(int M, int I, int J) {
     DwShape s;
     s.tm = 1; s.tn = 1;
-    if (g_force_dw[0]) { s.tm = g_force_dw[0]; s.tn = g_force_dw[1]; }
+    if (g_lab.force_dw[0]) { s.tm = g_lab.force_dw[0]; s.tn = g_lab.force_dw[1]; }
     s.nti = (I + 64 * s.tm - 1) / (64 * s.tm); s.ntj = (J + 64 * s.tn - 1) / (64 * s.tn);
     const int tiles = s.nti * s.ntj, steps = (M + 7) / 8;
     s.ksw = 4;
@@ -580,8 +578,8 @@ static DwShape dw_shape(int M, int I, int J) {
     if (ksg > 16) ksg = 16;
     if (ksg < 1) ksg = 1;
     s.ksg = ksg;
-    if (g_force_dw[2]) s.ksw = g_force_dw[2];
-    if (g_force_dw[3]) s.ksg = g_force_dw[3];
+    if (g_lab.force_dw[2]) s.ksw = g_lab.force_dw[2];
+    if (g_lab.force_dw[3]) s.ksg = g_lab.force_dw[3];
     return s;
 }
 static size_t dw_tile_floats(const DwShape& s) { return (size_t)s.tm * s.tn * 16 * 256; }
@@ -590,20 +588,13 @@ static size_t dw_tile_floats(const DwShape& s) { return (size_t)s.tm * s.tn * 16
 
 // What the staged kernels' callers (stack.hip) ask: may a plain stack of P rows take the fragment path, and how many statistics rows
 // does a forward / dX GEMM write then (one per 64-row tile)?
-static int g_frag_max_rows = 8192;
-bool frag_rows_eligible(int P) { return P >= 1 && P <= g_frag_max_rows; }
+bool frag_rows_eligible(int P) { return P >= 1 && P <= g_lab.frag_max_rows; }
 int frag_stat_rows(int P) { return (P + 63) / 64; }
 
 }  // namespace pcl
 using namespace pcl;
 using namespace pcl::fg;
 
-extern "C" void pcl_frag_set_tuning(int max_rows, int force_tn, int force_ksw, int dw_tm, int dw_tn, int dw_ksw, int dw_ksg) {
-    if (max_rows >= 0) g_frag_max_rows = max_rows;
-    g_force_tn = force_tn; g_force_ksw = force_ksw;
-    g_force_dw[0] = dw_tm; g_force_dw[1] = dw_tn; g_force_dw[2] = dw_ksw; g_force_dw[3] = dw_ksg;
-}
-extern "C" int pcl_frag_max_rows(void) { return g_frag_max_rows; }
 extern "C" int pcl_frag_stat_rows(int P) { return P < 1 ? 1 : frag_stat_rows(P); }
 
 static bool small_enough(const void* base, size_t bytes) { (void)base; return bytes < 0x7fffffffull; }
@@ -627,8 +618,8 @@ extern "C" int pcl_frag_linear_fwd_f32(const float* X, int ldx, const float* W, 
     g.C = Y; g.ldc = ldy; g.Clo = Y_lo; g.stats = stats_ws; g.M = P; g.N = Cout; g.K = Cin; g.n_begin = 0;
     const bool act = in_scale != nullptr;
     const char* who = "pcl_frag_linear_fwd_f32";
-#define FWD(FL) (stats_ws ? (act ? launch_gemm<FL, true, false, EP_STATS>(who, g, st, g_force_tn, g_force_ksw) : launch_gemm<FL, false, false, EP_STATS>(who, g, st, g_force_tn, g_force_ksw)) \
-                          : (act ? launch_gemm<FL, true, false, EP_STORE>(who, g, st, g_force_tn, g_force_ksw) : launch_gemm<FL, false, false, EP_STORE>(who, g, st, g_force_tn, g_force_ksw)))
+#define FWD(FL) (stats_ws ? (act ? launch_gemm<FL, true, false, EP_STATS>(who, g, st, g_lab.force_tn, g_lab.force_ksw) : launch_gemm<FL, false, false, EP_STATS>(who, g, st, g_lab.force_tn, g_lab.force_ksw)) \
+                          : (act ? launch_gemm<FL, true, false, EP_STORE>(who, g, st, g_lab.force_tn, g_lab.force_ksw) : launch_gemm<FL, false, false, EP_STORE>(who, g, st, g_lab.force_tn, g_lab.force_ksw)))
     const int rc = flush_k == 0 ? FWD(0) : flush_k == 8 ? FWD(8) : FWD(32);
 #undef FWD
     return rc;
@@ -667,8 +658,8 @@ extern "C" int pcl_frag_linear_bwd_dx_f32(const float* dy, const float* W, int l
     g.A = dy; g.lda = Cout; g.B = W; g.ldb = ldw; g.C = dUprev; g.ldc = ldu; g.stats = stats_ws; g.M = P; g.N = Cin; g.K = Cout; g.n_begin = first_col;
     g.Yp = Yprev; g.ldyp = ldyp; g.esc = prev_scale; g.esh = prev_shift; g.eslope = prev_slope;
     const char* who = "pcl_frag_linear_bwd_dx_f32";
-    if (Yprev) return launch_gemm<0, false, true, EP_MASK_STATS>(who, g, st, g_force_tn, g_force_ksw);
-    return launch_gemm<0, false, true, EP_STORE>(who, g, st, g_force_tn, g_force_ksw);
+    if (Yprev) return launch_gemm<0, false, true, EP_MASK_STATS>(who, g, st, g_lab.force_tn, g_lab.force_ksw);
+    return launch_gemm<0, false, true, EP_STORE>(who, g, st, g_lab.force_tn, g_lab.force_ksw);
 }
 
 extern "C" size_t pcl_frag_dw_workspace_bytes(int P, int Cout, int Cin) {

@@ -1742,7 +1742,7 @@ __global__ __launch_bounds__(FR_T) void linear_fwd_split_kernel(const FrArgs p_i
 // which forward launches take the resident-weight kernel: a hidden layer (folded BatchNorm + activation on the input) of a
 // set-abstraction shape with enough rows to keep one workgroup per CU busy for several tiles
 static bool fwd_res_eligible(const LinArgs& a) {
-    if (!path_switches().fwd_resident || (a.a_mode != A_BNACT && a.a_mode != A_PLAIN) || a.e_mode != E_STORE_STATS || a.gmax || a.n_begin != 0 || a.ldc != a.N) return false;
+    if (!g_lab.fwd_resident || (a.a_mode != A_BNACT && a.a_mode != A_PLAIN) || a.e_mode != E_STORE_STATS || a.gmax || a.n_begin != 0 || a.ldc != a.N) return false;
     if (!((a.K == 64 && (a.N == 64 || a.N == 128)) || (a.K == 128 && (a.N == 128 || a.N == 256)))) return false;
     if (a.M < 32768 || (size_t)a.M * (size_t)(a.N > a.K ? a.N : a.K) * 4 >= 0xffffffffull) return false;
     if (!al16(a.bias, a.A, a.B)) return false;
@@ -1768,10 +1768,8 @@ static int launch_fwd_split_t(const FrArgs& f, bool rag, hipStream_t st) {
     else PCL_LAUNCH_TIMED((linear_fwd_split_kernel<CI, CBK, false, false>), grid, blk, st, f);
     return check_launch("pcl_linear_fwd(split bf16 planes)");
 }
-// the matrix-pipe form of the GEMM family: 0 (DEFAULT) = fp32 MFMA, bit 0 / 1 = fp32 operands as three bf16 planes on the bf16 MFMA (opt-in)
-static int g_split_mfma = 0;               // bit 0: the resident-operand forward, bit 1: the staged GEMMs with K >= g_split_min_k
-static int g_split_min_k = 128;
-static bool fwd_split_on() { return (g_split_mfma & 1) != 0; }
+// the matrix-pipe form of the GEMM family (g_lab.split_mfma): 0 (DEFAULT) = fp32 MFMA, bit 0 / 1 = fp32 operands as three bf16 planes on the bf16 MFMA (opt-in)
+static bool fwd_split_on() { return (g_lab.split_mfma & 1) != 0; }
 // the CU count the persistent kernels size their grids by (the partial-tile workspace and the 256-row statistics are sized for <= 256)
 static int fb_cu_count() { const int n = cu_count(); return n > 256 ? 256 : n; }
 static int launch_fwd_res(const LinArgs& a, int stat_rows, hipStream_t st) {
@@ -1779,7 +1777,7 @@ static int launch_fwd_res(const LinArgs& a, int stat_rows, hipStream_t st) {
     f.X = a.A; f.W = a.B; f.bias = a.bias; f.sc = a.a_mode == A_PLAIN ? nullptr : a.sc; f.sh = a.a_mode == A_PLAIN ? nullptr : a.sh; f.slope = a.slope; f.Y = a.C; f.stats = a.stats;
     f.rmeta = a.rmeta; f.m_dev = a.m_dev; f.M = a.M; f.N = a.N; f.stat_rows = stat_rows;
     const int NS = a.N == 64 ? 64 : 128, R = a.K == 64 ? 128 : 64;
-    const bool split = fwd_split_on() || ((g_split_mfma & 4) && a.K == 128 && a.N == 256);
+    const bool split = fwd_split_on() || ((g_lab.split_mfma & 4) && a.K == 128 && a.N == 256);
     f.nt = split ? 1 : a.N / NS;
     const int tiles = (a.M + R - 1) / R;
     int gx = fb_cu_count() / f.nt;                       // one workgroup per CU in all
@@ -2532,12 +2530,10 @@ __global__ __launch_bounds__(FB_T) void linear_bwd_fused_kernel(const FbArgs p_i
 // one persistent workgroup per CU (the device's CU count, asked once); pcl_set_fb_max_blocks caps it (tests: several row tiles
 // per workgroup at sizes small enough for an fp64 comparison free of ReLU-mask flips; tuning).  The cap is a process-wide
 // setting made BETWEEN calls: it sizes the statistics rows, the workspace and the finish reduction of every later call.
-static int g_fb_cap = 0;
-static int g_fb_two = 1;                 // the 128 x 64 shape on two tile images (pcl_set_fb_two_images)
 static int fb_grid(int P, int Cin) {
     const int R = fb_rows(Cin), tiles = (P + R - 1) / R;
     const int cus = fb_cu_count();
-    int gx = g_fb_cap >= 1 && g_fb_cap < cus ? g_fb_cap : cus;
+    int gx = g_lab.fb_cap >= 1 && g_lab.fb_cap < cus ? g_lab.fb_cap : cus;
     if (gx > tiles) gx = tiles;
     if (gx < 1) gx = 1;
     return gx;
@@ -3058,7 +3054,7 @@ static int launch_linear_t(const LinArgs& a_in, hipStream_t st) {
     a.gx = gx; a.nt = n_tiles;
     dim3 grid(gx * n_tiles);
     if constexpr (GM == 0) {                   // matrix-bound shapes: fp32 operands as three bf16 planes on the bf16 matrix pipe
-        if (vec && (g_split_mfma & 2) && a.K >= g_split_min_k) {
+        if (vec && (g_lab.split_mfma & 2) && a.K >= g_lab.split_min_k) {
             if (!RAG && low) PCL_LAUNCH_TIMED((linear_nt_kernel<AM, EM, true, 1, 0, false, 1, true>), grid, dim3(MLP_T), st, a);
             else if (narrow || AM >= A_DY) PCL_LAUNCH_TIMED((linear_nt_kernel<AM, EM, true, 1, 0, RAG, 2, true>), grid, dim3(MLP_T), st, a);
             else { if constexpr (AM < A_DY) PCL_LAUNCH_TIMED((linear_nt_kernel<AM, EM, true, 2, 0, RAG, 2, true>), grid, dim3(MLP_T), st, a); }
@@ -3326,12 +3322,8 @@ extern "C" int pcl_linear_bwd_dw_rows_f32(const float* dU, const float* Y, const
 }
 
 // ---- both backward GEMMs of a few-row layer in one launch, the partial-tile sum in the finish launch (round 6) --------------------------
-static int g_bwd_pair = 1;               // lab switch (pcl_set_bwd_pair): 0 = the two launches + reduce of rounds 1-5
-extern "C" void pcl_set_bwd_pair(int on) { g_bwd_pair = on != 0; }
-extern "C" int pcl_get_bwd_pair(void) { return g_bwd_pair; }
-
 extern "C" int pcl_linear_bwd_pair_supported(int P, int Cout, int Cin, int first_col) {
-    if (!g_bwd_pair || P < 1 || Cout <= 64 || Cin <= 64 || (g_split_mfma & 2)) return 0;
+    if (!g_lab.bwd_pair || P < 1 || Cout <= 64 || Cin <= 64 || (g_lab.split_mfma & 2)) return 0;
     int gx, ti, tj, tm, tn;
     dw_grid(P, Cout, Cin, gx, ti, tj, tm, tn);
     if (gx == 1 || tm != 2 || tn != 2) return 0;                 // (gx == 1: the direct form, nothing to reduce)
@@ -3438,9 +3430,6 @@ int pcl::pair_finish_impl(const void* workspace, size_t workspace_bytes, int P, 
 }
 
 // ---- few-row layers: constants + dy in one launch, weight gradient on the formed dy (round 5) ----------------------------------------
-static int g_dw_force_gx = 0;            // lab knob (pcl_set_dw_tuning): row-chunk workgroups per output tile of the plain-dy dW
-extern "C" void pcl_set_dw_tuning(int gx) { g_dw_force_gx = gx > 0 ? gx : 0; }
-
 extern "C" int pcl_bn_bwd_dy_supported(int P, int C) { return P >= 1 && C >= 32 && C % 32 == 0; }
 
 extern "C" int pcl_bn_bwd_dy_f32(const double* stats_ws, int stat_rows, const float* gamma, const float* mean, const float* invstd, int P_bn, int C,
@@ -3464,9 +3453,9 @@ extern "C" int pcl_bn_bwd_dy_f32(const double* stats_ws, int stat_rows, const fl
 
 static void dw_plain_grid(int P, int I, int J, int& gx, int& ti, int& tj, int& tm, int& tn) {
     dw_grid(P, I, J, gx, ti, tj, tm, tn);
-    if (g_dw_force_gx) {
+    if (g_lab.dw_force_gx) {
         const int chunks = (P + DW_BP - 1) / DW_BP;
-        gx = g_dw_force_gx < chunks ? g_dw_force_gx : chunks;
+        gx = g_lab.dw_force_gx < chunks ? g_lab.dw_force_gx : chunks;
     }
 }
 extern "C" size_t pcl_linear_bwd_dw_plain_workspace_bytes(int P, int Cout, int Cin) {
@@ -3505,15 +3494,6 @@ extern "C" int pcl_linear_bwd_dw_plain_f32(const float* dy, const float* Xprev, 
     return check_launch("pcl_linear_bwd_dw_plain_f32(reduce)");
 }
 
-extern "C" void pcl_set_fb_max_blocks(int n) { g_fb_cap = n; }
-// 1 (opt-in; the default is 0, the fp32 MFMA): the resident-operand GEMMs take fp32 operands as three bf16 planes on the bf16 matrix pipe (nine exact partial
-// products per fp32 product); 0: the fp32 MFMA form of rounds 2-3 (kept for A/B measurements and the error comparison test)
-extern "C" void pcl_set_matrix_form(int split) { g_split_mfma = split & 7; g_split_min_k = (split >> 8) > 0 ? (split >> 8) : 128; }
-extern "C" int pcl_get_matrix_form(void) { return g_split_mfma; }
-
-extern "C" void pcl_set_fb_two_images(int on) { g_fb_two = on != 0; }
-extern "C" int pcl_get_fb_two_images(void) { return g_fb_two; }
-
 extern "C" int pcl_linear_bwd_fused_supported(int Cout, int Cin) {
     return ((Cout == 64 || Cout == 128) && (Cin == 64 || Cin == 128)) || (Cout == 256 && Cin == 128);
 }
@@ -3540,7 +3520,7 @@ static int launch_fb(const FbArgs& a_in, int Cout, int Cin, hipStream_t st) {
     else if (Cout == 64 && Cin == 128) PCL_FB(1, 2);
     else if (Cout == 128 && Cin == 64) {
         // two tile images of 64 rows, waves in two roles (round 6); pcl_set_fb_two_images(0) keeps the one-image form for A/B runs
-        if (g_fb_two) PCL_LAUNCH_TIMED((linear_bwd_fused_kernel<SPARSE, RAG, 2, 1, true>), grid, blk, st, a);
+        if (g_lab.fb_two) PCL_LAUNCH_TIMED((linear_bwd_fused_kernel<SPARSE, RAG, 2, 1, true>), grid, blk, st, a);
         else PCL_FB(2, 1);
     }
     else if (Cout == 128 && Cin == 128) PCL_FB(2, 2);

@@ -553,11 +553,9 @@ static int bwd_w_max_wgs(int slices) {
     const int n = 2 * cu_count() / (slices < 1 ? 1 : slices);
     return n < 1 ? 1 : n;
 }
-static int g_bwd_w_rows = 1;             // lab switch (pcl_set_pointconv_paths)
-extern "C" void pcl_set_pointconv_paths(int bwd_w_rows) { if (bwd_w_rows >= 0) g_bwd_w_rows = bwd_w_rows != 0; }
 static void launch_bwd_w(int slices, hipStream_t st, const float* feat, const float* dout, const float* dens, const float* w, int G, int ns, int C,
                          float* dw, float* ddens, const FeatBN bn) {
-    if (g_bwd_w_rows && C % 4 == 0 && ns <= 64 && (size_t)ns * C * 4 < 0x7fffffffull && al16(feat, dout)) {
+    if (g_lab.bwd_w_rows && C % 4 == 0 && ns <= 64 && (size_t)ns * C * 4 < 0x7fffffffull && al16(feat, dout)) {
         // row-major LDS image, a wave per group (ns <= 64: the GroupAll level's 128-row groups keep the kernel above)
         int wgs = (G + 3) / 4;
         const int cap = 3 * bwd_w_max_wgs(slices) / 2;                   // persistent: three workgroups per CU (LDS: 26 / 45 KB each)

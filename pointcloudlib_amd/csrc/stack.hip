@@ -70,7 +70,7 @@ static SaveLayout save_layout(const pcl_mlp_stack_t& d, void* base) {
 static inline bool frag_fwd(const pcl_mlp_stack_t& d) { return !d.grouped && d.flush_k != 0; }
 static inline bool use_gmax(const pcl_mlp_stack_t& d) { return !d.grouped && !d.flush_k && (d.pool == 32 || d.pool == 64); }
 static inline bool fused_bwd_enabled() {
-    return path_switches().fused_backward != 0;
+    return g_lab.fused_backward != 0;
 }
 
 // ---- transient buffer of the forward -------------------------------------------------------------------------------
@@ -128,19 +128,19 @@ struct BwdTmp {
 // too short to fill the chip (fill / drain, a split-K tail and a reduce launch around 20-50 us of matrix work).  So the dW launches
 // (+ their reduces) go to a second stream of the library, forked after consts(l) and joined at the end of the call: they run in the
 // holes of the dX chain.  Results do not depend on the interleaving (same kernels, same grids, per-layer buffers).
-static int g_side_dw = 0, g_side_dw_max_rows = 8192;
+// Switch: g_lab.side_dw, up to g_lab.side_dw_max_rows rows.
 // Few-row layers (same stacks): BatchNorm-backward constants + dy in ONE launch, then dX on the fragment-direct kernel and dW on the staged
 // kernel, both reading the formed dy (csrc/mlp.hip: bn_bwd_dy_kernel).  Per layer: no fused dX + dW kernel for the shape, Cout % 32 == 0.
-static int g_fewrow = 0;
+// Switch: g_lab.fewrow.
 bool frag_rows_eligible(int P);
 int frag_stat_rows(int P);
 static inline bool fewrow_layer(const pcl_mlp_stack_t& d, int l) {
-    if (!g_fewrow || d.grouped || !frag_rows_eligible(d.P)) return false;
+    if (!g_lab.fewrow || d.grouped || !frag_rows_eligible(d.P)) return false;
     if (l > 0 && fused_bwd_enabled() && pcl_linear_bwd_fused_supported(d.c[l + 1], d.c[l])) return false;
     return pcl_bn_bwd_dy_supported(d.P, d.c[l + 1]) != 0;
 }
 static inline bool side_dw(const pcl_mlp_stack_t& d) {
-    if (!g_side_dw || d.grouped || d.P > g_side_dw_max_rows || d.n_layers < 2) return false;
+    if (!g_lab.side_dw || d.grouped || d.P > g_lab.side_dw_max_rows || d.n_layers < 2) return false;
     for (int l = 1; l < d.n_layers; ++l) if (fused_bwd_enabled() && pcl_linear_bwd_fused_supported(d.c[l + 1], d.c[l])) return false;
     return true;
 }
@@ -799,17 +799,10 @@ static int stack_bwd_impl(const pcl_mlp_stack_t* dp) {
     return PCL_OK;
 }
 
-extern "C" void pcl_set_stack_overlap(int side_dw_on, int max_rows) {
-    if (side_dw_on >= 0) g_side_dw = side_dw_on != 0;
-    if (max_rows > 0) g_side_dw_max_rows = max_rows;
-}
-extern "C" int pcl_get_stack_overlap(void) { return g_side_dw; }
-extern "C" void pcl_set_fewrow_backward(int on) { if (on >= 0) g_fewrow = on != 0; }
-extern "C" int pcl_get_fewrow_backward(void) { return g_fewrow; }
 /* does layer (Cout <- Cin) of a plain stack on P rows take the few-row backward (constants + dy in one launch, dX and dW on the formed dy)?
  * The per-kernel host path asks the same question so that both paths launch the same kernels. */
 extern "C" int pcl_mlp_fewrow_layer(int P, int Cout, int Cin, int first_layer) {
-    if (!g_fewrow || !frag_rows_eligible(P)) return 0;
+    if (!g_lab.fewrow || !frag_rows_eligible(P)) return 0;
     if (!first_layer && fused_bwd_enabled() && pcl_linear_bwd_fused_supported(Cout, Cin)) return 0;
     return pcl_bn_bwd_dy_supported(P, Cout);
 }

@@ -616,6 +616,7 @@ class _StackPlan:
 
 
 _PLANS = {}
+_lib.on_switch_change(_PLANS.clear)          # (pcl_mlp_stack_sizes answers by the lab switches)
 
 
 def _stack_plan(module, P, c0, pool, grouped, geom, need_dx, x_grad_from, defer=False):

@@ -72,14 +72,11 @@ def test_fused_backward_tiles_per_block(dev, monkeypatch, spec, lead, ns, bias, 
     the cyclic weight-chunk stage, the double-buffered row records), at a row count where an fp64 comparison is still free
     of ReLU-mask flips (a pre-activation within fp32 rounding of 0 turns up about once per 10^7 elements)."""
     from pointcloudlib_amd import _lib
-    from pointcloudlib_amd.misc import mlp_hip
-    _lib.lib().pcl_set_fb_max_blocks(blocks)
-    _lib.size_query.cache_clear(); mlp_hip._PLANS.clear()          # sizes depend on the cap
+    _lib.lib().pcl_set_fb_max_blocks(blocks)          # (sizes depend on the cap: the setter drops the cached ones)
     try:
         _check_against_fp64(dev, spec, lead, ns, bias, slope)
     finally:
         _lib.lib().pcl_set_fb_max_blocks(0)
-        _lib.size_query.cache_clear(); mlp_hip._PLANS.clear()
 
 
 @pytest.mark.parametrize("spec,lead,ns", [([16, 128, 64, 256], (8, 512, 32), 32), ([16, 64, 128, 64], (3, 44444), None),
@@ -929,7 +926,6 @@ def test_side_stream_weight_gradients_equal_the_serial_order(dev, spec, lead, ns
     """pcl_mlp_stack_bwd_f32 forks the dW launches of few-row plain stacks to a second stream and joins at the end of the call
     (csrc/stack.hip: side_dw): outputs and every gradient must be BIT-identical to the serial order, call after call."""
     from pointcloudlib_amd import _lib
-    from pointcloudlib_amd.misc import mlp_hip
     L = _lib.lib()
     torch.manual_seed(11)
     mlp = PointwiseMLP(spec, bias=bias, slope=0.0).to(dev).train()
@@ -938,9 +934,9 @@ def test_side_stream_weight_gradients_equal_the_serial_order(dev, spec, lead, ns
     gout = torch.randn(*gshape, device=dev)
     prev = L.pcl_get_stack_overlap()
     try:
-        L.pcl_set_stack_overlap(0, -1); mlp_hip._PLANS.clear()          # (buffer sizes depend on the mode)
+        L.pcl_set_stack_overlap(0, -1)          # (buffer sizes depend on the mode: the setter drops the cached plans)
         ref = run(copy.deepcopy(mlp), x, ns, gout, "auto")
-        L.pcl_set_stack_overlap(1, -1); mlp_hip._PLANS.clear()
+        L.pcl_set_stack_overlap(1, -1)
         for _ in range(4):
             got = run(copy.deepcopy(mlp), x, ns, gout, "auto")
             # consume the gradients right away on the caller's stream: the join must order them behind the side stream's writes
@@ -948,7 +944,7 @@ def test_side_stream_weight_gradients_equal_the_serial_order(dev, spec, lead, ns
             for n in ref[2]:
                 assert torch.equal(ref[2][n], got[2][n]), n
     finally:
-        L.pcl_set_stack_overlap(prev, -1); mlp_hip._PLANS.clear()
+        L.pcl_set_stack_overlap(prev, -1)
 
 
 @pytest.mark.parametrize("spec,lead,ns,bias", [([259, 256, 512, 1024], (32, 1, 128), 128, False),     # the GroupAll level at full size (sparse max gradient)
@@ -959,7 +955,6 @@ def test_few_row_backward_matches_the_staged_kernels(dev, spec, lead, ns, bias):
     the staged kernel reading the formed dy.  dgamma / dbeta come from the same sums in the same order (bit-identical); the GEMMs sum in
     another order: 1e-4 of the gradient's max-norm (this file's gradient tolerance).  The per-stack and the per-kernel host path must launch the same kernels (bit-identical)."""
     from pointcloudlib_amd import _lib
-    from pointcloudlib_amd.misc import mlp_hip
     L = _lib.lib()
     torch.manual_seed(5)
     mlp = PointwiseMLP(spec, bias=bias, slope=0.0).to(dev).train()
@@ -967,17 +962,15 @@ def test_few_row_backward_matches_the_staged_kernels(dev, spec, lead, ns, bias):
     gshape = (lead[:-1] if ns else lead) + (spec[-1],)
     gout = torch.randn(*gshape, device=dev)
     prev = L.pcl_get_fewrow_backward()
-    def fresh():
-        _lib.size_query.cache_clear(); mlp_hip._PLANS.clear()
     try:
-        L.pcl_set_fewrow_backward(0); fresh()
+        L.pcl_set_fewrow_backward(0)
         ref = run(copy.deepcopy(mlp), x, ns, gout, "auto")
-        L.pcl_set_fewrow_backward(1); fresh()
+        L.pcl_set_fewrow_backward(1)
         assert L.pcl_mlp_fewrow_layer(x.numel() // spec[0], spec[-1], spec[-2], 0) == 1
         got = _with_stack(True, lambda: run(copy.deepcopy(mlp), x, ns, gout, "auto"))
         per = _with_stack(False, lambda: run(copy.deepcopy(mlp), x, ns, gout, "auto"))
     finally:
-        L.pcl_set_fewrow_backward(prev); fresh()
+        L.pcl_set_fewrow_backward(prev)
     assert torch.equal(ref[0], got[0])
     L_ = len(spec) - 1
     for n in ref[2]:
@@ -1053,7 +1046,6 @@ def test_backward_pair_launch_equals_the_separate_launches(dev, spec, lead, ns, 
     below's constants (csrc/mlp.hip: linear_bwd_pair_kernel, pcl_linear_bwd_pair_finish_f32).  Same kernel bodies, same reduction order:
     outputs and every gradient must be BIT-identical to the four-launch form (pcl_set_bwd_pair(0))."""
     from pointcloudlib_amd import _lib
-    from pointcloudlib_amd.misc import mlp_hip
     L = _lib.lib()
     torch.manual_seed(12)
     mlp = PointwiseMLP(spec, bias=bias, slope=0.0).to(dev).train()
@@ -1062,15 +1054,15 @@ def test_backward_pair_launch_equals_the_separate_launches(dev, spec, lead, ns, 
     gout = torch.randn(*gshape, device=dev)
     prev = L.pcl_get_bwd_pair()
     try:
-        L.pcl_set_bwd_pair(0); mlp_hip._PLANS.clear()
+        L.pcl_set_bwd_pair(0)
         ref = run(copy.deepcopy(mlp), x, ns, gout, "auto")
-        L.pcl_set_bwd_pair(1); mlp_hip._PLANS.clear()
+        L.pcl_set_bwd_pair(1)
         got = run(copy.deepcopy(mlp), x, ns, gout, "auto")
         assert torch.equal(ref[0], got[0]) and torch.equal(ref[1], got[1])
         for n in ref[2]:
             assert torch.equal(ref[2][n], got[2][n]), n
     finally:
-        L.pcl_set_bwd_pair(prev); mlp_hip._PLANS.clear()
+        L.pcl_set_bwd_pair(prev)
 
 
 @pytest.mark.parametrize("spec,lead,ns", [([16, 64, 128, 64], (3, 44444), None),            # dense 128 x 64 at size (2-9 tiles per workgroup)
@@ -1080,7 +1072,6 @@ def test_two_image_fused_backward_equals_the_one_image_form(dev, spec, lead, ns)
     """Round 6: the 128 x 64 fused backward walks 64-row tiles over two LDS images with the waves in two roles (pcl_set_fb_two_images).
     Same arithmetic per element; dW and the BatchNorm sums differ from the one-image form in summation order only."""
     from pointcloudlib_amd import _lib
-    from pointcloudlib_amd.misc import mlp_hip
     L = _lib.lib()
     torch.manual_seed(13)
     mlp = PointwiseMLP(spec, bias=False, slope=0.0).to(dev).train()
@@ -1089,16 +1080,16 @@ def test_two_image_fused_backward_equals_the_one_image_form(dev, spec, lead, ns)
     gout = torch.randn(*gshape, device=dev)
     prev = L.pcl_get_fb_two_images()
     try:
-        L.pcl_set_fb_two_images(0); mlp_hip._PLANS.clear()
+        L.pcl_set_fb_two_images(0)
         ref = run(copy.deepcopy(mlp), x, ns, gout, "auto")
-        L.pcl_set_fb_two_images(1); mlp_hip._PLANS.clear()
+        L.pcl_set_fb_two_images(1)
         got = run(copy.deepcopy(mlp), x, ns, gout, "auto")
         assert torch.equal(ref[0], got[0])
         for name, a, b in [("x", ref[1], got[1])] + [(n, ref[2][n], got[2][n]) for n in ref[2]]:
             scale = a.abs().max().item()
             assert (a - b).abs().max().item() <= 2e-5 * max(scale, 1e-6) + 1e-7, (name, (a - b).abs().max().item(), scale)
     finally:
-        L.pcl_set_fb_two_images(prev); mlp_hip._PLANS.clear()
+        L.pcl_set_fb_two_images(prev)
 
 
 @pytest.mark.parametrize("P,Cout,Cin,sparse,masked,w_shift", [(4096, 512, 256, False, True, 0),      # a GroupAll-level layer, dense gradient
