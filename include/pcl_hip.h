@@ -237,6 +237,23 @@ void pcl_set_scatter_form(int gather);        /* lab switch: 1 (default) the gat
 int pcl_group_linear_bwd_gather_f32(const float* row_loc, const float* dU, const float* Y, const float* a, const float* k1,
                                     const float* k2, const float* mu, const int32_t* in_off, const int32_t* in_rows, int B, int N,
                                     int C1, float* dUf, float* dWx_part, float* dW0, int ldw, void* stream);
+/* The same two backward forms WITHOUT the Y read (round 8): y is a 3-to-7-term fmaf chain over the 16-byte row records these kernels load
+ * anyway, so they form it again -- by the one device function the forward forms it with, hence the same float and bit-identical outputs --
+ * instead of streaming the stored pre-BatchNorm output back in: half the bytes per row.  The caller passes what the forward call was given:
+ * Wx [C1,3] or NULL and Wf_small [C1,CF] (row stride ldw) with the row_feat records it wrote, or (gather form) its Uf [B*N, C1] and Wx.
+ * They must hold the values the forward read.  pcl_group_linear_bwd_regen_f32 is pcl_group_linear_bwd_f32 without dUf (inline features
+ * or coordinates only); pcl_group_linear_bwd_gather_regen_f32 is pcl_group_linear_bwd_gather_f32.  dW0 (leading dimension ld0) as there.
+ * C1 in {64, 128, 256} and CF <= 4 (pcl_group_linear_bwd_regen_supported; the gather form: pcl_group_linear_bwd_gather_supported), dU, Uf,
+ * dUf, the row records and a / k1 / k2 / mu 16-byte aligned. */
+int pcl_group_linear_bwd_regen_supported(int C1, int CF);
+/* reference: gradient of the grouping + first conv (misc/ops.py:383-407 + networks/cls/pointnet2.py:25-26), as pcl_group_linear_bwd_f32 */
+int pcl_group_linear_bwd_regen_f32(const float* row_loc, const float* row_feat, const float* Wx, const float* Wf_small, int CF, int ldw,
+                                   const float* dU, const float* a, const float* k1, const float* k2, const float* mu,
+                                   const int32_t* n_rows_dev /* &group_off[B*m] */, int C1, float* dWx_part, float* dWf_part, float* dW0,
+                                   int ld0, int off, void* stream);
+int pcl_group_linear_bwd_gather_regen_f32(const float* row_loc, const float* dU, const float* Uf, const float* Wx, int ldw, const float* a,
+                                          const float* k1, const float* k2, const float* mu, const int32_t* in_off, const int32_t* in_rows,
+                                          int B, int N, int C1, float* dUf, float* dWx_part, float* dW0, int ld0, void* stream);
 
 /* The classification head on R <= 64 rows (one row per cloud): Linear (+bias) -> BatchNorm1d -> (Leaky)ReLU as ONE kernel
  * per layer (networks/cls/pointnet2.py:138-147, dgcnn.py:87-93, pointnet.py:22-38).  X [R,K], W [N,K] (nn.Linear layout).

@@ -192,6 +192,15 @@ constexpr int GL_MAXH = 4;       // channels per lane: C1 <= 256
 constexpr int GL_RPI = 4;        // rows in flight per wave
 constexpr int GL_CF = 4;         // features folded inline (e.g. the 3 normals of the first level), wider ones come as Uf
 
+// The folded layer's value of one row and channel: y = u + Wx . L.xyz + Wf_small . F.xyzw, ONE explicit fmaf chain in one order.
+// The forward kernels store it (Y0) and the regenerating backward kernels form it again from the same records and weights instead of
+// reading it back: the same chain on the same inputs is the same float, so whoever forms y must do it here and nowhere else.
+// (Absent inputs take part as zeros -- wx = 0 without coordinates, wf[f] = 0 and F = 0 beyond CF -- in the forward and in the backward alike.)
+__device__ __forceinline__ float glin_row_value(float u, const float4& L, const float4& F, const float (&wx)[3], const float (&wf)[GL_CF]) {
+    const float t = fmaf(wx[2], L.z, fmaf(wx[1], L.y, fmaf(wx[0], L.x, u)));
+    return fmaf(wf[3], F.w, fmaf(wf[2], F.z, fmaf(wf[1], F.y, fmaf(wf[0], F.x, t))));
+}
+
 // side job of the metadata kernel: the feature columns of the folded layer's weight as a dense matrix for the point GEMM
 struct DenseJob { const float* src; float* dst; int rows, cols, ldw, first, blocks; };
 
@@ -289,8 +298,7 @@ __global__ __launch_bounds__(256) void group_linear_kernel(const float* __restri
 #pragma unroll
             for (int j = 0; j < GL_RPI; ++j) {
                 if (r0 + j < R && lane + 64 * h < C1) {
-                    float y = fmaf(wx[h][2], L[j].z, fmaf(wx[h][1], L[j].y, fmaf(wx[h][0], L[j].x, u[j])));
-                    y = fmaf(wf[h][3], F[j].w, fmaf(wf[h][2], F[j].z, fmaf(wf[h][1], F[j].y, fmaf(wf[h][0], F[j].x, y))));
+                    const float y = glin_row_value(u[j], L[j], F[j], wx[h], wf[h]);
                     Y[(size_t)(r0 + j) * C1 + ch] = y;
                     const double w = (double)L[j].w;
                     ss[h] += w * (double)y; qq[h] += w * (double)y * (double)y;
@@ -392,6 +400,17 @@ __global__ __launch_bounds__(256) void group_linear_bwd_kernel(const float4* __r
 // ---- 16-byte-channel variants of the two kernels above (C1 = 64 / 128 / 256) -----------------------------------------
 // A lane owns 4 consecutive channels, LPR = C1/4 lanes cover a row, so one wave instruction moves 64/LPR consecutive
 // rows = 1 KiB of contiguous Y (or dU) instead of 256 B: a quarter of the memory instructions for the same bytes.
+// the folded layer's weights of a lane's 4 channels (row stride ldw), zeros where an input is absent
+__device__ __forceinline__ void glin_load_weights(const float* __restrict__ Wx, const float* __restrict__ Wfs, int CF, int ldw, int c4,
+                                                  float (&wx)[4][3], float (&wf)[4][GL_CF]) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) wx[v][d] = Wx ? Wx[(size_t)(c4 + v) * ldw + d] : 0.f;
+#pragma unroll
+        for (int f = 0; f < GL_CF; ++f) wf[v][f] = f < CF ? Wfs[(size_t)(c4 + v) * ldw + f] : 0.f;
+    }
+}
 template <int LPR>     // lanes per row: 16, 32 or 64
 __global__ __launch_bounds__(256) void group_linear_v4_kernel(const float* __restrict__ Uf, const float* __restrict__ Wx,
                                                               const float* __restrict__ Wfs, int CF, int ldw,
@@ -404,14 +423,14 @@ __global__ __launch_bounds__(256) void group_linear_v4_kernel(const float* __res
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int cl = lane % LPR, rsub = lane / LPR, c4 = 4 * cl;
     const int R = *n_rows;
-    float wx[3][4], wf[GL_CF][4];
+    float wx[4][3], wf[4][GL_CF];
     double ss[4], qq[4];
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
 #pragma unroll
-        for (int d = 0; d < 3; ++d) wx[d][v] = Wx ? Wx[(size_t)(c4 + v) * ldw + d] : 0.f;
+        for (int d = 0; d < 3; ++d) wx[v][d] = Wx ? Wx[(size_t)(c4 + v) * ldw + d] : 0.f;
 #pragma unroll
-        for (int f = 0; f < GL_CF; ++f) wf[f][v] = f < CF ? Wfs[(size_t)(c4 + v) * ldw + f] : 0.f;
+        for (int f = 0; f < GL_CF; ++f) wf[v][f] = f < CF ? Wfs[(size_t)(c4 + v) * ldw + f] : 0.f;
         ss[v] = 0.0; qq[v] = 0.0;
     }
     const int stride = gridDim.x * 4 * RPW * U;
@@ -432,8 +451,7 @@ __global__ __launch_bounds__(256) void group_linear_v4_kernel(const float* __res
                 const double w = (double)L[j].w;
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
-                    float t = fmaf(wx[2][v], L[j].z, fmaf(wx[1][v], L[j].y, fmaf(wx[0][v], L[j].x, y[v])));
-                    t = fmaf(wf[3][v], F[j].w, fmaf(wf[2][v], F[j].z, fmaf(wf[1][v], F[j].y, fmaf(wf[0][v], F[j].x, t))));
+                    const float t = glin_row_value(y[v], L[j], F[j], wx[v], wf[v]);
                     y[v] = t;
                     ss[v] += w * (double)t; qq[v] += w * (double)t * (double)t;
                 }
@@ -529,6 +547,86 @@ __global__ __launch_bounds__(256) void group_linear_bwd_v4_kernel(const float4* 
     }
 }
 
+// The same kernel without the Y read (no dUf: narrow inline features, the first level).  y is formed again from the row records the kernel
+// loads anyway and the 7 weights per channel the forward used (glin_row_value, started from 0 as the forward does without Uf): half the
+// bytes per row, 7 more FMAs per element.  dy and the sums are those of group_linear_bwd_v4_kernel, bit for bit.
+template <int LPR>
+__global__ __launch_bounds__(256) void group_linear_bwd_regen_kernel(const float4* __restrict__ rloc, const float4* __restrict__ rfeat,
+                                                                     const float* __restrict__ Wx, const float* __restrict__ Wfs, int CF,
+                                                                     int ldw, const float* __restrict__ dU, const float* __restrict__ a_,
+                                                                     const float* __restrict__ k1_, const float* __restrict__ k2_,
+                                                                     const float* __restrict__ mu_, const int32_t* __restrict__ n_rows,
+                                                                     float* __restrict__ dWx_part, float* __restrict__ dWf_part) {
+    // A wave owns the same rows as in group_linear_bwd_v4_kernel -- chunks of CH = 4 row groups, a workgroup round apart -- and a lane adds
+    // them up in the same order, so the partial sums are that kernel's bit for bit; but it walks them as ONE sequence t = 0, 1, 2, ... (chunk
+    // t / CH, row group t % CH) with U = 3 in flight instead of a whole chunk: 126 VGPRs, so the 1024 workgroups are all resident (4 waves
+    // per SIMD).  With 4 in flight the kernel needs 140 (3 waves per SIMD: a second, thin round of workgroups) and took 47 us on the first
+    // level of PointNet++ against 37 with 3; 2 and 8 (192 VGPRs, two even rounds) 38; the same kernel with y = 0 instead of the chain 35
+    // (profiles/r08_glin_bwd_regen_ab.txt)
+    constexpr int C1 = 4 * LPR, RPW = 64 / LPR, CH = 4, U = 3;
+    __shared__ float red[3 + GL_CF][4][C1];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int cl = lane % LPR, rsub = lane / LPR, c4 = 4 * cl;
+    const int R = *n_rows;
+    float wx[4][3], wf[4][GL_CF];
+    float a[4], k1[4], k2[4], mu[4], gw[3 + GL_CF][4];
+    glin_load_weights(Wx, Wfs, CF, ldw, c4, wx, wf);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        a[v] = a_[c4 + v]; k1[v] = k1_[c4 + v]; k2[v] = k2_[c4 + v]; mu[v] = mu_[c4 + v];
+#pragma unroll
+        for (int d = 0; d < 3 + GL_CF; ++d) gw[d][v] = 0.f;
+    }
+    const int stride = gridDim.x * 4 * RPW * CH, base = (blockIdx.x * 4 + wave) * RPW * CH;
+    for (int t0 = 0; base + (t0 / CH) * stride < R; t0 += U) {          // (rows ascend with t: what lies past R is masked below)
+        float4 L[U], F[U], du[U];
+        int row[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int t = t0 + j;
+            row[j] = base + (t / CH) * stride + (t % CH) * RPW + rsub;
+            const int r = min(row[j], R - 1);
+            L[j] = rloc[r];
+            F[j] = CF ? rfeat[r] : make_float4(0.f, 0.f, 0.f, 0.f);
+            du[j] = *reinterpret_cast<const float4*>(dU + (size_t)r * C1 + c4);
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            if (row[j] < R) {
+                const float dd[4] = {du[j].x, du[j].y, du[j].z, du[j].w};
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const float y = glin_row_value(0.f, L[j], F[j], wx[v], wf[v]);
+                    const float dy = fmaf(a[v], dd[v], -L[j].w * fmaf(k2[v], y - mu[v], k1[v]));
+                    gw[0][v] = fmaf(dy, L[j].x, gw[0][v]); gw[1][v] = fmaf(dy, L[j].y, gw[1][v]); gw[2][v] = fmaf(dy, L[j].z, gw[2][v]);
+                    gw[3][v] = fmaf(dy, F[j].x, gw[3][v]); gw[4][v] = fmaf(dy, F[j].y, gw[4][v]);
+                    gw[5][v] = fmaf(dy, F[j].z, gw[5][v]); gw[6][v] = fmaf(dy, F[j].w, gw[6][v]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 3 + GL_CF; ++d)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            float t = gw[d][v];
+#pragma unroll
+            for (int off = LPR; off < 64; off <<= 1) t += __shfl_xor(t, off);
+            if (rsub == 0) red[d][wave][c4 + v] = t;
+        }
+    __syncthreads();
+    if (dWx_part)
+        for (int e = threadIdx.x; e < C1 * 3; e += 256) {
+            const int ch = e / 3, d = e - ch * 3;
+            dWx_part[(size_t)blockIdx.x * C1 * 3 + e] = (red[d][0][ch] + red[d][1][ch]) + (red[d][2][ch] + red[d][3][ch]);
+        }
+    if (dWf_part)
+        for (int e = threadIdx.x; e < C1 * CF; e += 256) {
+            const int ch = e / CF, d = 3 + (e - ch * CF);
+            dWf_part[(size_t)blockIdx.x * C1 * CF + e] = (red[d][0][ch] + red[d][1][ch]) + (red[d][2][ch] + red[d][3][ch]);
+        }
+}
+
 // ---- the scatter to the points as a gather over the points' row lists (round 5) ---------------------------------------------------------
 // With wide point features every row's dy [C1] went to dUf[source point] by one fp32 atomic per element: 22.5 M of them at the second
 // level of PointNet++, 52 of the kernel's 82 us (tools/dbg/glinbwd_atomics.py; the reads alone run at 6 TB/s), in an order the hardware
@@ -585,6 +683,95 @@ __global__ __launch_bounds__(256) void group_linear_bwd_gather_kernel(const floa
                     const float w = L[j].w;
                     const float d0 = fmaf(a.x, du[j].x, -w * fmaf(k2.x, yv[j].x - mu.x, k1.x)), d1 = fmaf(a.y, du[j].y, -w * fmaf(k2.y, yv[j].y - mu.y, k1.y));
                     const float d2 = fmaf(a.z, du[j].z, -w * fmaf(k2.z, yv[j].z - mu.z, k1.z)), d3 = fmaf(a.w, du[j].w, -w * fmaf(k2.w, yv[j].w - mu.w, k1.w));
+                    acc.x += d0; acc.y += d1; acc.z += d2; acc.w += d3;
+                    gw[0][0] = fmaf(d0, L[j].x, gw[0][0]); gw[0][1] = fmaf(d1, L[j].x, gw[0][1]); gw[0][2] = fmaf(d2, L[j].x, gw[0][2]); gw[0][3] = fmaf(d3, L[j].x, gw[0][3]);
+                    gw[1][0] = fmaf(d0, L[j].y, gw[1][0]); gw[1][1] = fmaf(d1, L[j].y, gw[1][1]); gw[1][2] = fmaf(d2, L[j].y, gw[1][2]); gw[1][3] = fmaf(d3, L[j].y, gw[1][3]);
+                    gw[2][0] = fmaf(d0, L[j].z, gw[2][0]); gw[2][1] = fmaf(d1, L[j].z, gw[2][1]); gw[2][2] = fmaf(d2, L[j].z, gw[2][2]); gw[2][3] = fmaf(d3, L[j].z, gw[2][3]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j) r[j] = rn[j];
+        }
+#pragma unroll
+        for (int off = LPR; off < 64; off <<= 1) {
+            acc.x += __shfl_xor(acc.x, off); acc.y += __shfl_xor(acc.y, off); acc.z += __shfl_xor(acc.z, off); acc.w += __shfl_xor(acc.w, off);
+        }
+        if (psub == 0) *reinterpret_cast<float4*>(dUf + (size_t)p * C1 + c4) = acc;
+    }
+    if (dWx_part) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                float t = gw[d][v];
+#pragma unroll
+                for (int off = LPR; off < 64; off <<= 1) t += __shfl_xor(t, off);
+                if (psub == 0) red[d][wave][c4 + v] = t;
+            }
+        __syncthreads();
+        for (int e = threadIdx.x; e < C1 * 3; e += 256) {
+            const int ch = e / 3, d = e - ch * 3;
+            dWx_part[(size_t)blockIdx.x * C1 * 3 + e] = (red[d][0][ch] + red[d][1][ch]) + (red[d][2][ch] + red[d][3][ch]);
+        }
+    }
+}
+
+// The gather without the Y read: every row of point p is y = glin_row_value(Uf[p], L, ...), so a wave reads Uf[p] once per point (its lanes'
+// 4 channels, the same for all row-lanes) and forms y per row from the 16-byte record it loads anyway.  Sums and their order as above.
+template <int LPR>
+__global__ __launch_bounds__(256) void group_linear_bwd_gather_regen_kernel(const float4* __restrict__ rloc, const float* __restrict__ dU,
+                                                                      const float* __restrict__ Uf, const float* __restrict__ Wx, int ldw,
+                                                                      const float* __restrict__ a_,
+                                                                      const float* __restrict__ k1_, const float* __restrict__ k2_,
+                                                                      const float* __restrict__ mu_, const int32_t* __restrict__ in_off,
+                                                                      const int32_t* __restrict__ in_rows, int P, float* __restrict__ dUf,
+                                                                      float* __restrict__ dWx_part) {
+    constexpr int C1 = 4 * LPR, PPW = 64 / LPR, U = 4;
+    __shared__ float red[3][4][C1];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int cl = lane % LPR, psub = lane / LPR, c4 = 4 * cl;
+    const float4 a = *reinterpret_cast<const float4*>(a_ + c4), k1 = *reinterpret_cast<const float4*>(k1_ + c4);
+    const float4 k2 = *reinterpret_cast<const float4*>(k2_ + c4), mu = *reinterpret_cast<const float4*>(mu_ + c4);
+    float gw[3][4], wx[4][3], wf[4][GL_CF];
+    glin_load_weights(Wx, nullptr, 0, ldw, c4, wx, wf);
+    const float4 F0 = make_float4(0.f, 0.f, 0.f, 0.f);          // no inline features next to Uf: they take part as zeros, as in the forward
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) gw[d][v] = 0.f;
+    // a wave takes ONE point at a time and its 64 / LPR row-lanes alternate over the point's list in chunks of U rows: the lists of popular
+    // points (the centre of a cloud is in every group: 100+ rows) are the kernel's tail, and this halves / quarters their dependent chain;
+    // the row-lanes' sums meet by shuffles in a fixed order.  The next chunk's row indices are requested before this chunk's rows are used.
+    const int stride = gridDim.x * 4;
+    // (a point in no group has o0 == o1, and for the trailing points of the last cloud that is in_off[P] = the number of rows: the
+    // prefetch index is clamped to the last row so that the -- unused -- value is never read past a full `in_rows`)
+    const int last = max(in_off[P] - 1, 0);
+    for (int p = blockIdx.x * 4 + wave; p < P; p += stride) {
+        const int o0 = in_off[p], o1 = in_off[p + 1];
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 u = *reinterpret_cast<const float4*>(Uf + (size_t)p * C1 + c4);       // the start value of every row of this point
+        int o = o0 + psub * U;
+        int r[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) r[j] = in_rows[min(max(o0, min(o + j, o1 - 1)), last)];
+        for (; o < o1; o += PPW * U) {
+            float4 L[U], du[U];
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                L[j] = rloc[r[j]];
+                du[j] = *reinterpret_cast<const float4*>(dU + (size_t)r[j] * C1 + c4);
+            }
+            int rn[U];
+#pragma unroll
+            for (int j = 0; j < U; ++j) rn[j] = in_rows[min(max(o0, min(o + PPW * U + j, o1 - 1)), last)];
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                if (o + j < o1) {
+                    const float w = L[j].w;
+                    const float4 yv = make_float4(glin_row_value(u.x, L[j], F0, wx[0], wf[0]), glin_row_value(u.y, L[j], F0, wx[1], wf[1]),
+                                                  glin_row_value(u.z, L[j], F0, wx[2], wf[2]), glin_row_value(u.w, L[j], F0, wx[3], wf[3]));
+                    const float d0 = fmaf(a.x, du[j].x, -w * fmaf(k2.x, yv.x - mu.x, k1.x)), d1 = fmaf(a.y, du[j].y, -w * fmaf(k2.y, yv.y - mu.y, k1.y));
+                    const float d2 = fmaf(a.z, du[j].z, -w * fmaf(k2.z, yv.z - mu.z, k1.z)), d3 = fmaf(a.w, du[j].w, -w * fmaf(k2.w, yv.w - mu.w, k1.w));
                     acc.x += d0; acc.y += d1; acc.z += d2; acc.w += d3;
                     gw[0][0] = fmaf(d0, L[j].x, gw[0][0]); gw[0][1] = fmaf(d1, L[j].x, gw[0][1]); gw[0][2] = fmaf(d2, L[j].x, gw[0][2]); gw[0][3] = fmaf(d3, L[j].x, gw[0][3]);
                     gw[1][0] = fmaf(d0, L[j].y, gw[1][0]); gw[1][1] = fmaf(d1, L[j].y, gw[1][1]); gw[1][2] = fmaf(d2, L[j].y, gw[1][2]); gw[1][3] = fmaf(d3, L[j].y, gw[1][3]);
@@ -902,4 +1089,59 @@ extern "C" int pcl_group_linear_bwd_gather_f32(const float* row_loc, const float
     if (rc || !dW0) return rc;
     hipLaunchKernelGGL(group_linear_dw_kernel, dim3((C1 * 3 + 3) / 4), block, 0, st, dWx_part, (const float*)nullptr, GL_BLOCKS, C1, 0, 0, ldw, dW0);
     return check_launch("pcl_group_linear_bwd_gather_f32(dW)");
+}
+
+/* The two 16-byte-channel backward forms above WITHOUT the Y read: y is formed again per element from what the forward formed it from
+ * (glin_row_value: the same fmaf chain, hence the same float and bit-identical outputs), given the forward's weights and, with wide
+ * features, its Uf.  C1 in {64, 128, 256}, 16-byte aligned rows, CF <= 4. */
+extern "C" int pcl_group_linear_bwd_regen_supported(int C1, int CF) {
+    return (C1 == 64 || C1 == 128 || C1 == 256) && CF >= 0 && CF <= GL_CF;
+}
+extern "C" int pcl_group_linear_bwd_regen_f32(const float* row_loc, const float* row_feat, const float* Wx, const float* Wf_small, int CF,
+                                              int ldw, const float* dU, const float* a, const float* k1, const float* k2, const float* mu,
+                                              const int32_t* n_rows_dev, int C1, float* dWx_part, float* dWf_part, float* dW0, int ld0, int off,
+                                              void* stream) {
+    PCL_REQUIRE(row_loc && dU && a && k1 && k2 && mu && n_rows_dev, "pcl_group_linear_bwd_regen_f32: null pointer");
+    PCL_REQUIRE(pcl_group_linear_bwd_regen_supported(C1, CF), "pcl_group_linear_bwd_regen_f32: C1 = %d (64, 128 or 256), CF = %d (<= %d)", C1, CF, GL_CF);
+    PCL_REQUIRE(Wx || CF > 0, "pcl_group_linear_bwd_regen_f32: need the forward's weights (Wx and/or Wf_small)");
+    PCL_REQUIRE(CF == 0 || (row_feat && Wf_small), "pcl_group_linear_bwd_regen_f32: CF=%d inline features need row_feat and Wf_small", CF);
+    PCL_REQUIRE(ldw >= (Wx ? 3 : 0) && ldw >= CF, "pcl_group_linear_bwd_regen_f32: ldw=%d", ldw);
+    PCL_REQUIRE(dWx_part || dWf_part, "pcl_group_linear_bwd_regen_f32: nothing to compute");
+    PCL_REQUIRE(!dWf_part || CF >= 1, "pcl_group_linear_bwd_regen_f32: dWf_part needs CF >= 1");
+    PCL_REQUIRE(al16(dU, row_loc, row_feat), "pcl_group_linear_bwd_regen_f32: 16-byte aligned rows");
+    PCL_REQUIRE(!dW0 || (ld0 >= (dWx_part ? 3 : 0) && off >= 0 && ld0 >= off + (dWf_part ? CF : 0)),
+                "pcl_group_linear_bwd_regen_f32: dW0 needs ld0=%d >= off=%d + CF", ld0, off);
+    hipStream_t st = as_stream(stream);
+    const float4* rl = reinterpret_cast<const float4*>(row_loc);
+    const float4* rf = reinterpret_cast<const float4*>(row_feat);
+    const dim3 grid(GL_BLOCKS), block(256);
+    if (C1 == 64) hipLaunchKernelGGL(group_linear_bwd_regen_kernel<16>, grid, block, 0, st, rl, rf, Wx, Wf_small, CF, ldw, dU, a, k1, k2, mu, n_rows_dev, dWx_part, dWf_part);
+    else if (C1 == 128) hipLaunchKernelGGL(group_linear_bwd_regen_kernel<32>, grid, block, 0, st, rl, rf, Wx, Wf_small, CF, ldw, dU, a, k1, k2, mu, n_rows_dev, dWx_part, dWf_part);
+    else hipLaunchKernelGGL(group_linear_bwd_regen_kernel<64>, grid, block, 0, st, rl, rf, Wx, Wf_small, CF, ldw, dU, a, k1, k2, mu, n_rows_dev, dWx_part, dWf_part);
+    int rc = check_launch("pcl_group_linear_bwd_regen_f32");
+    if (rc || !dW0) return rc;
+    const int n = (dWx_part ? C1 * 3 : 0) + (dWf_part ? C1 * CF : 0);
+    hipLaunchKernelGGL(group_linear_dw_kernel, dim3((n + 3) / 4), block, 0, st, dWx_part, dWf_part, GL_BLOCKS, C1, CF, off, ld0, dW0);
+    return check_launch("pcl_group_linear_bwd_regen_f32(dW)");
+}
+extern "C" int pcl_group_linear_bwd_gather_regen_f32(const float* row_loc, const float* dU, const float* Uf, const float* Wx, int ldw,
+                                                     const float* a, const float* k1, const float* k2, const float* mu, const int32_t* in_off,
+                                                     const int32_t* in_rows, int B, int N, int C1, float* dUf, float* dWx_part, float* dW0,
+                                                     int ld0, void* stream) {
+    PCL_REQUIRE(row_loc && dU && Uf && a && k1 && k2 && mu && in_off && in_rows && dUf, "pcl_group_linear_bwd_gather_regen_f32: null pointer");
+    PCL_REQUIRE(B >= 1 && N >= 1 && pcl_group_linear_bwd_gather_supported(C1), "pcl_group_linear_bwd_gather_regen_f32: bad sizes (C1 = %d: 64, 128 or 256)", C1);
+    PCL_REQUIRE(al16(dU, Uf, dUf, row_loc) && al16(a, k1, k2, mu), "pcl_group_linear_bwd_gather_regen_f32: 16-byte aligned rows");
+    PCL_REQUIRE(!Wx || ldw >= 3, "pcl_group_linear_bwd_gather_regen_f32: ldw=%d", ldw);
+    PCL_REQUIRE(!dW0 || (dWx_part && ld0 >= 3), "pcl_group_linear_bwd_gather_regen_f32: dW0 needs dWx_part and ld0 >= 3");
+    hipStream_t st = as_stream(stream);
+    const float4* rl = reinterpret_cast<const float4*>(row_loc);
+    const dim3 grid(GL_BLOCKS), block(256);
+    const int P = B * N;
+    if (C1 == 64) hipLaunchKernelGGL(group_linear_bwd_gather_regen_kernel<16>, grid, block, 0, st, rl, dU, Uf, Wx, ldw, a, k1, k2, mu, in_off, in_rows, P, dUf, dWx_part);
+    else if (C1 == 128) hipLaunchKernelGGL(group_linear_bwd_gather_regen_kernel<32>, grid, block, 0, st, rl, dU, Uf, Wx, ldw, a, k1, k2, mu, in_off, in_rows, P, dUf, dWx_part);
+    else hipLaunchKernelGGL(group_linear_bwd_gather_regen_kernel<64>, grid, block, 0, st, rl, dU, Uf, Wx, ldw, a, k1, k2, mu, in_off, in_rows, P, dUf, dWx_part);
+    int rc = check_launch("pcl_group_linear_bwd_gather_regen_f32");
+    if (rc || !dW0) return rc;
+    hipLaunchKernelGGL(group_linear_dw_kernel, dim3((C1 * 3 + 3) / 4), block, 0, st, dWx_part, (const float*)nullptr, GL_BLOCKS, C1, 0, 0, ld0, dW0);
+    return check_launch("pcl_group_linear_bwd_gather_regen_f32(dW)");
 }

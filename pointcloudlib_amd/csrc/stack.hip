@@ -34,6 +34,7 @@ struct SaveLayout {
     int32_t* arg; float* ymax;             // pooled stacks: [G, cL]
     int32_t* row_meta; int32_t* row_src; float* row_loc; float* row_feat;     // grouped stacks
     int32_t* in_off; int32_t* in_rows;     // grouped, wide features: every source point's rows (the backward's scatter as a gather)
+    float* Uf;                             // ... and the per-point product feat Wf^T [B*N, c1]: that backward forms y from it instead of reading Y[0]
     size_t bytes;
 };
 
@@ -60,7 +61,10 @@ static SaveLayout save_layout(const pcl_mlp_stack_t& d, void* base) {
         s.row_src = c.take<int32_t>((size_t)d.P);
         s.row_loc = c.take<float>((size_t)d.P * 4);
         if (grouped_inline(d)) s.row_feat = c.take<float>((size_t)d.P * 4);
-        if (gather_scatter(d)) { s.in_off = c.take<int32_t>((size_t)d.B * d.N + 1); s.in_rows = c.take<int32_t>((size_t)d.P); }
+        if (gather_scatter(d)) {
+            s.in_off = c.take<int32_t>((size_t)d.B * d.N + 1); s.in_rows = c.take<int32_t>((size_t)d.P);
+            s.Uf = c.take<float>((size_t)d.B * d.N * d.c[1]);
+        }
     }
     s.bytes = c.off;
     return s;
@@ -76,7 +80,7 @@ static inline bool fused_bwd_enabled() {
 // ---- transient buffer of the forward -------------------------------------------------------------------------------
 struct FwdTmp {
     double* stats;                  // one region, reused layer after layer (stream order: finalize reads it before the next GEMM writes)
-    float* Uf; double* pt_stats;    // grouped, wide features: the per-point product feat Wf^T and its (unused) sums
+    float* Uf; double* pt_stats;    // grouped, wide features: the per-point product feat Wf^T (here unless the backward wants it: SaveLayout) and its (unused) sums
     float *gmax, *gmin; int32_t *gamax, *gamin;
     size_t bytes;
 };
@@ -94,7 +98,7 @@ static FwdTmp fwd_tmp(const pcl_mlp_stack_t& d, void* base) {
     }
     t.stats = c.take<double>(rows_max);
     if (grouped_wide(d)) {
-        t.Uf = c.take<float>((size_t)d.B * d.N * d.c[1]);
+        if (!gather_scatter(d)) t.Uf = c.take<float>((size_t)d.B * d.N * d.c[1]);
         if (!d.flush_k) t.pt_stats = c.take<double>((size_t)pcl_mlp_stat_rows(d.B * d.N, d.c[1], 0) * 2 * d.c[1]);     // (the flushed product writes no sums)
     }
     if (use_gmax(d)) {
@@ -524,6 +528,7 @@ static int stack_fwd_impl(const pcl_mlp_stack_t* dp) {
         if (l == 0 && d.grouped) {
             const int off = d.use_xyz ? 3 : 0, ldw = d.c[0];
             const bool inl = grouped_inline(d), wide = grouped_wide(d);
+            float* const Uf = s.Uf ? s.Uf : t.Uf;
             if (wide) {
                 // row metadata first: its kernel also copies the feature columns of W (row stride c0, rows not 16-byte aligned)
                 // into the dense matrix the point GEMM reads -- no separate copy launch per step
@@ -532,15 +537,15 @@ static int stack_fwd_impl(const pcl_mlp_stack_t* dp) {
                                               st, 1, ly.W + off, d.Wf_dense, d.Cf));
                 tagf("pt%dx%d", d.Cf, cout);
                 // (a conv bias of the folded layer is added here, once per point: every row gathers exactly one Uf row)
-                if (d.flush_k) PCL_TRY(pcl_frag_linear_fwd_f32(d.feature, d.Cf, d.Wf_dense, d.Cf, ly.bias, nullptr, nullptr, 0.f, d.B * d.N, d.Cf, cout, t.Uf, cout,
+                if (d.flush_k) PCL_TRY(pcl_frag_linear_fwd_f32(d.feature, d.Cf, d.Wf_dense, d.Cf, ly.bias, nullptr, nullptr, 0.f, d.B * d.N, d.Cf, cout, Uf, cout,
                                                                nullptr, nullptr, d.flush_k, st));
-                else PCL_TRY(pcl_linear_fwd_rows_f32(d.feature, d.Wf_dense, ly.bias, nullptr, nullptr, 0.f, d.B * d.N, d.Cf, cout, t.Uf,
+                else PCL_TRY(pcl_linear_fwd_rows_f32(d.feature, d.Wf_dense, ly.bias, nullptr, nullptr, 0.f, d.B * d.N, d.Cf, cout, Uf,
                                                      t.pt_stats, nullptr, nullptr, st));
             }
             if (gather_scatter(d))         // the rows by source point, for the backward (row_src is complete after the metadata launch)
                 PCL_TRY(pcl_group_rows_transpose_i32(s.row_src, d.group_off, d.B, d.N, d.m, d.pool, s.in_off, s.in_rows, st));
             tagf("glin%d", cout, 0);
-            PCL_TRY(group_linear_fwd_impl(d.xyz, d.new_xyz, wide ? t.Uf : nullptr, d.use_xyz ? ly.W : nullptr, inl ? d.feature : nullptr,
+            PCL_TRY(group_linear_fwd_impl(d.xyz, d.new_xyz, wide ? Uf : nullptr, d.use_xyz ? ly.W : nullptr, inl ? d.feature : nullptr,
                                           inl ? ly.W + off : nullptr, inl ? d.Cf : 0, ldw, d.idx, d.cnt, d.group_off, d.B, d.N, d.m,
                                           d.pool, cout, Y, s.row_meta, s.row_src, s.row_loc, s.row_feat, t.stats, st, wide ? 2 : 3, nullptr,
                                           nullptr, 0));
@@ -674,9 +679,15 @@ static int stack_bwd_impl(const pcl_mlp_stack_t* dp) {
             const bool pt_pair = wide && d.need_dx && pcl_linear_bwd_pair_supported(d.B * d.N, C1, d.Cf, 0);
             const bool x_in_finish = pt_pair && gather_scatter(d) && t.dWxp;
             tagf("glinbwd%d", C1, 0);
+            // y is formed again from the row records (and Uf) with the forward's weights where the 16-byte forms exist: Y[0] is not read here
+            // (nothing updates the weights between a step's forward and its backward; a padded stack's live in `save`)
             if (gather_scatter(d))
-                PCL_TRY(pcl_group_linear_bwd_gather_f32(s.row_loc, dU, s.Y[0], a, k1, k2, mean, s.in_off, s.in_rows, d.B, d.N, C1, t.dUf, t.dWxp,
-                                                        (t.dWxp && !x_in_finish) ? ly.dW : nullptr, fan_in, st));
+                PCL_TRY(pcl_group_linear_bwd_gather_regen_f32(s.row_loc, dU, s.Uf, d.use_xyz ? ly.W : nullptr, fan_in, a, k1, k2, mean, s.in_off,
+                                                              s.in_rows, d.B, d.N, C1, t.dUf, t.dWxp,
+                                                              (t.dWxp && !x_in_finish) ? ly.dW : nullptr, fan_in, st));
+            else if (!t.dUf && (t.dWxp || t.dWfp) && pcl_group_linear_bwd_regen_supported(C1, inl ? d.Cf : 0) && al16(dU))
+                PCL_TRY(pcl_group_linear_bwd_regen_f32(s.row_loc, s.row_feat, d.use_xyz ? ly.W : nullptr, inl ? ly.W + off : nullptr, inl ? d.Cf : 0,
+                                                       fan_in, dU, a, k1, k2, mean, nrows, C1, t.dWxp, t.dWfp, ly.dW, fan_in, off, st));
             else
             PCL_TRY(group_linear_bwd_impl(s.row_loc, s.row_feat, inl ? d.Cf : 0, dU, s.Y[0], a, k1, k2, mean, s.row_src, nrows, d.B, d.N, C1,
                                           t.dUf, t.dWxp, t.dWfp, (t.dWxp || t.dWfp) ? ly.dW : nullptr, fan_in, off, st, /*duf_is_zero=*/true));

@@ -506,13 +506,14 @@ class _GroupLinear(torch.autograd.Function):
         ctx.dims = (B, N, m, ns, C1, C, off, inline, rows)
         ctx.mark_non_differentiable(row_meta, row_src)
         ctx.set_materialize_grads(False)          # no zero tensors for the (integer) metadata outputs
-        ctx.save_for_backward(group_off, Y, row_src, row_loc, row_feat, feat2, None if inline else Wf, in_off, in_rows)
+        # the backward forms y again from the row records (and Uf) with these weights where the 16-byte forms exist: W0 and Uf are saved for it
+        ctx.save_for_backward(group_off, Y, row_src, row_loc, row_feat, feat2, None if inline else Wf, in_off, in_rows, W0, Uf)
         return Y, row_meta, row_src
 
     @staticmethod
     def backward(ctx, du, *_):
         B, N, m, ns, C1, C, off, inline, rows = ctx.dims
-        group_off, Y, row_src, row_loc, row_feat, feat2, Wf, in_off, in_rows = ctx.saved_tensors
+        group_off, Y, row_src, row_loc, row_feat, feat2, Wf, in_off, in_rows, W0, Uf = ctx.saved_tensors
         a, k1, k2, mu = ctx.link.consts
         ctx.link.consts = None
         dev = Y.device
@@ -527,10 +528,17 @@ class _GroupLinear(torch.autograd.Function):
         dWxp = _empty((rows, C1, 3), dev) if (off and need_w) else None
         dWfp = _empty((rows, C1, C), dev) if (inline and need_w) else None
         dW0 = _empty((C1, fan_in), dev) if need_w else None
+        Wx = W0[:, :3] if off else None                        # views of the forward's weight, row stride fan_in
         if dUf is not None and in_off is not None:
-            _lib.call("pcl_group_linear_bwd_gather_f32", _P(row_loc), _P(du.contiguous()), _P(Y), _P(a), _P(k1), _P(k2), _P(mu), _P(in_off), _P(in_rows),
-                      B, N, C1, _P(dUf), _P(dWxp), _P(dW0) if (dW0 is not None and dWxp is not None) else None, fan_in, st,
-                      algo_bytes=_rows_cost(group_off[B * m:], B * m * ns, 4 * C1 * 2 + 36, 4 * B * N * C1), tag=f"glinbwd{C1}")
+            # (what the per-stack entry point runs: y from Uf[p] and the row record, no Y read; per row du + the records, per point Uf and dUf)
+            _lib.call("pcl_group_linear_bwd_gather_regen_f32", _P(row_loc), _P(du.contiguous()), _P(Uf), _P(Wx), fan_in, _P(a), _P(k1), _P(k2), _P(mu),
+                      _P(in_off), _P(in_rows), B, N, C1, _P(dUf), _P(dWxp), _P(dW0) if (dW0 is not None and dWxp is not None) else None, fan_in, st,
+                      algo_bytes=_rows_cost(group_off[B * m:], B * m * ns, 4 * C1 + 36, 8 * B * N * C1), tag=f"glinbwd{C1}")
+        elif (dUf is None and (dWxp is not None or dWfp is not None)
+              and _lib.size_query("pcl_group_linear_bwd_regen_supported", C1, C if inline else 0)):
+            _lib.call("pcl_group_linear_bwd_regen_f32", _P(row_loc), _P(row_feat), _P(Wx), _P(W0[:, off:]) if inline else None, C if inline else 0,
+                      fan_in, _P(du.contiguous()), _P(a), _P(k1), _P(k2), _P(mu), _P(group_off[B * m:]), C1, _P(dWxp), _P(dWfp), _P(dW0),
+                      fan_in, off, st, algo_bytes=_rows_cost(group_off[B * m:], B * m * ns, 4 * C1 + 36, 0), tag=f"glinbwd{C1}")
         elif dUf is not None or dWxp is not None or dWfp is not None:
             fin = dW0 is not None and (dWxp is not None or dWfp is not None)       # partial sums -> dW0 columns, in the same call
             _lib.call("pcl_group_linear_bwd_f32", _P(row_loc), _P(row_feat), C if inline else 0, _P(du.contiguous()), _P(Y),
