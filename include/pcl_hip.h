@@ -347,6 +347,10 @@ int pcl_soft_ce_rows_f32(const float* logits, const int64_t* target, float eps, 
  *     With the transposed lists of pcl_knn_transpose_i32 and sumU the sums are formed without touching the edges:
  *     dV[i] = a gz[i] - k k1 - k2 (k (V[i]-mu) + SU[i]),  dU[n] = hits[n] - deg k1 - k2 (deg (U[n]-mu) + sum_{i->n} V[i]),
  *     hits by one atomic per (point, channel); with in_off = in_src = sumU = NULL: one atomic per (edge, channel).
+ *     With lists and N <= 8192 the hits are summed in fp64 LDS cells: exact, hence the same in any order and dUV run-to-run identical,
+ *     as long as the addends of one (point, channel) cell lie within a factor 2^(29 - log2 of their count) of each other; a cell whose
+ *     addends span more can still round differently from run to run.
+ *     Beyond, and without lists, they are fp32 global atomics and the last bits of the U half may differ from run to run.
  *   pcl_knn_transpose_i32: idx [B,N,k] -> in_off [B*N+1] (global offsets into in_src), in_src [B*N*k] (for every point the
  *     sources i, index within the cloud, of the edges i->n, ascending).  N <= 8192. */
 int pcl_edgeconv_stat_rows(int B, int N);

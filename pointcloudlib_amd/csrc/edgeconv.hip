@@ -328,19 +328,24 @@ __global__ __launch_bounds__(256) void edgeconv_hits_kernel(const float* __restr
     }
 }
 
-// The same through LDS: workgroup (cloud b, chunk of CH channels) owns hits[:, c0..c0+CH) of its cloud -- LDS float
+// The same through LDS: workgroup (cloud b, chunk of CH channels) owns hits[:, c0..c0+CH) of its cloud -- LDS
 // atomics instead of 64 scattered global ones per wave instruction (arg differs per channel, so a wave's 64 lanes end in
 // 64 different rows: 520 us per DGCNN step with global atomics), then plain coalesced stores: no memset either.
+// The cells are fp64: the order in which the waves' atomics arrive differs from launch to launch, and an fp32 cell with three or more
+// addends then rounds differently from call to call (dW and dx of a stage were not reproducible).  The fp64 sum of fp32 addends is exact
+// -- hence the same in any order -- while a cell's addends lie within 2^(29 - log2 of their count) of each other, and an inexact one
+// moves the fp32 result only when it lands within 2^-29 of a rounding boundary: within that span dU is the fp32 rounding of the exact
+// sum and reproducible; a cell whose addends span more (a hub with gradients of 1e-10 beside ones of 1) is not guaranteed to be.
 __global__ __launch_bounds__(1024) void edgeconv_hits_lds_kernel(const float* __restrict__ UV, const int32_t* __restrict__ idx,
                                                                 const float* __restrict__ gz, const int32_t* __restrict__ arg,
                                                                 const float* __restrict__ sumU, const float* __restrict__ a_,
                                                                 const float* __restrict__ k1_, const float* __restrict__ k2_,
                                                                 const float* __restrict__ mu_, int N, int k, int C, int CH,
                                                                 float* __restrict__ dUV) {
-    extern __shared__ float hits[];                  // [N][CH]
+    extern __shared__ double hits[];                 // [N][CH]
     const int b = blockIdx.x, c0 = blockIdx.y * CH, tid = threadIdx.x;
     const int n_el = N * CH;
-    for (int e = tid; e < n_el; e += 1024) hits[e] = 0.f;
+    for (int e = tid; e < n_el; e += 1024) hits[e] = 0.0;
     __syncthreads();
     constexpr int HU = 4;                             // (eight: 98 -> 103 us per stage)
     for (int e0 = tid; e0 < n_el; e0 += HU * 1024) {   // HU independent (point, channel) pairs in flight per lane
@@ -366,14 +371,14 @@ __global__ __launch_bounds__(1024) void edgeconv_hits_lds_kernel(const float* __
         for (int u = 0; u < HU; ++u) {
             if (!ok[u]) continue;
             const int c = c0 + cc[u];
-            if (g[u] != 0.f) atomicAdd(&hits[n[u] * CH + cc[u]], g[u]);
+            if (g[u] != 0.f) atomicAdd(&hits[n[u] * CH + cc[u]], (double)g[u]);
             dUV[o2[u]] = g[u] - (float)k * k1_[c] - k2_[c] * fmaf((float)k, v[u] - mu_[c], su[u]);
         }
     }
     __syncthreads();
     for (int e = tid; e < n_el; e += 1024) {
         const int n = e / CH, cc = e - n * CH;
-        if (c0 + cc < C) dUV[((size_t)b * N + n) * 2 * C + c0 + cc] = hits[e];
+        if (c0 + cc < C) dUV[((size_t)b * N + n) * 2 * C + c0 + cc] = (float)hits[e];
     }
 }
 
@@ -498,9 +503,9 @@ extern "C" int pcl_edgeconv_scatter_f32(const float* UV, const int32_t* idx, con
                 "pcl_edgeconv_scatter_f32: in_off, in_src and sumU go together");
     const size_t P = (size_t)B * N;
     hipStream_t st = as_stream(stream);
-    int CH = 16;                                      // channels per workgroup of the LDS path: N*CH floats <= 64 KiB
-    while (CH > 1 && (size_t)N * CH * sizeof(float) > 65536) CH >>= 1;
-    const bool lds = in_off && (size_t)N * CH * sizeof(float) <= 65536;
+    int CH = 16;                                      // channels per workgroup of the LDS path: N*CH doubles <= 64 KiB
+    while (CH > 1 && (size_t)N * CH * sizeof(double) > 65536) CH >>= 1;
+    const bool lds = in_off && (size_t)N * CH * sizeof(double) <= 65536;
     if (!lds) {
         hipError_t e = hipMemsetAsync(dUV, 0, sizeof(float) * P * 2 * C, st);
         if (e != hipSuccess) return fail(PCL_EHIP, "pcl_edgeconv_scatter_f32: memset: %s", hipGetErrorString(e));
@@ -511,7 +516,7 @@ extern "C" int pcl_edgeconv_scatter_f32(const float* UV, const int32_t* idx, con
         return check_launch("pcl_edgeconv_scatter_f32");
     }
     if (lds) {
-        hipLaunchKernelGGL(edgeconv_hits_lds_kernel, dim3(B, (C + CH - 1) / CH), dim3(1024), sizeof(float) * N * CH, st, UV, idx, gz, arg, sumU,
+        hipLaunchKernelGGL(edgeconv_hits_lds_kernel, dim3(B, (C + CH - 1) / CH), dim3(1024), sizeof(double) * N * CH, st, UV, idx, gz, arg, sumU,
                            a, k1, k2, mu, N, k, C, CH, dUV);
     } else {
         size_t blocks = (P * C + 255) / 256;

@@ -204,6 +204,8 @@ def test_round5_entry_points_validate_on_the_host():
     assert lib.pcl_group_linear_bwd_gather_f32(p, p, p, p, p, p, p, p, p, 1, 8, 96, p, None, None, 0, None) == -1      # C1 = 96
     assert b"C1" in lib.pcl_last_error()
     assert lib.pcl_frag_linear_fwd_f32(p, 8, p, 8, None, None, None, 0.0, 4, 8, 8, p, 8, None, None, 16, None) == -1  # flush_k not 0 / 8 / 32
+    assert lib.pcl_frag_linear_fwd_f32(p, 8, p, 8, None, None, None, 0.0, 4, 8, 8, p, 8, p, None, 0, None) == -1    # Y_lo without the fp64 sum
+    assert b"Y_lo" in lib.pcl_last_error()
 
 
 def test_stack_backward_refuses_a_gout_stride_it_cannot_honour():
