@@ -857,6 +857,37 @@ int pcl_fp_level_infer_ragged_f32(const float* Us, const float* skip_small, cons
                                   const float* const* shift, int act_mask, float slope, float* out, int ldo, float* tap,
                                   int tap_layer, int ldt, void* stream);
 
+/* ---- Frozen inference: the PointNet conv stack and its max over the points in evaluation mode (csrc/infer_pointnet.hip) -----
+ * networks/cls/pointnet.py:28-36 (conv/bn/relu x 5, max over the points) as evaluated by train_cls.py:92-124 (net.eval(): running
+ * statistics):
+ *     z_1 = act(scale_1 * (W0 x) + shift_1),  z_l = act(scale_l * (W_l z_{l-1}) + shift_l) (l >= 2),
+ *     out[b * ldo + c] = max over i < n_b of z_L[b, i, c]
+ * Point (b, i), channel c < C0 is read at x + b*stride_b + i*stride_n + c*stride_c (strides in floats, size_t: the
+ * ABI passes no other 64-bit integer by value): the network's own [B,3,N]
+ * input or a loader's [B,N,3] is read as it is.  n_b = n_valid[b] clamped to [1, N] (ragged convention above; NULL: every cloud
+ * N points); pad points may hold anything, NaN included, and reach no result.  W0 [C1, C0] with row stride ldw0; host arrays of L
+ * entries: widths C_l, W (device pointers, W[l] [C_l, C_{l-1}] dense, 16-byte aligned; W[0] ignored), scale, shift -- the eval
+ * constants scale = gamma / sqrt(running_var + eps), shift = beta - scale * running_mean.  act = leaky ReLU with `slope`.
+ * workspace: pcl_pointnet_stack_infer_workspace_bytes(B, N, C_L) bytes, 16-byte aligned, any contents (per-tile partial maxima;
+ * never cleared); too small returns PCL_EWS.  Two launches: the fused stack, one workgroup per 64-point tile of one cloud with
+ * its activations in LDS and the max over the tile's rows in registers, then the max over each cloud's tiles.  No atomics.
+ * Numerics: layer 1 fmaf(w2, z, fmaf(w1, y, w0 * x)); layers 2.. fp32 products accumulated in fp32 (v_mfma_f32_32x32x2_f32, the
+ * k order of csrc/infer_mfma.h).  A cloud's output depends only on its own valid points: bit for bit the same for any B, any
+ * position in the batch, any capacity N, any pad contents, any launch variant and any run.
+ * A kernel exists for C0 = 3, L = 5, widths 64/64/64/128/1024 (pcl_pointnet_stack_infer_supported); any other shape returns
+ * PCL_EINVAL ("no kernel"). */
+int pcl_pointnet_stack_infer_supported(int C0, int L, const int32_t* widths);
+size_t pcl_pointnet_stack_infer_workspace_bytes(int B, int N, int C_last);
+/* No reference counterpart: into how many column ranges (grid.y; 1, 2 or 4) the launch splits the last layer so that few tiles
+ * still fill the machine -- a pure function of the sizes, in the spirit of pcl_optimal_block; layers 1 .. L-1 are recomputed per
+ * split and the results are the same bits for every value. */
+int pcl_pointnet_stack_infer_splits(int B, int N);
+/* reference: networks/cls/pointnet.py:28-36 in eval mode (train_cls.py:92-124) */
+int pcl_pointnet_stack_infer_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid, int B,
+                                 int N, int C0, const float* W0, int ldw0, int L, const int32_t* widths, const float* const* W,
+                                 const float* const* scale, const float* const* shift, float slope, void* workspace,
+                                 size_t workspace_bytes, float* out, int ldo, void* stream);
+
 /* ---- packed rows of a ragged batch (csrc/pack.hip) ------------------------------------------------
  * No reference counterpart.  What runs once per raw point of a ragged batch (FP1, the head and the loss of PointNet++ part
  * segmentation) runs on R = sum_b n_b rows, cloud after cloud without a pad row: n_b = n_valid[b] clamped to [1, N] (ragged

@@ -18,7 +18,11 @@ output (the tap).  FP levels and heads of other widths run eval-mode copies of t
 
 ``frozen(net, precision="bf16")`` runs every fused set-abstraction launch as ``pcl_sa_level_infer_bf16_f32``: layers 2 and up
 take bf16 operands (activations rounded to nearest even, weights snapshot as bf16 once) and accumulate in fp32; the first layer,
-``Uf``, the epilogues, the max and every output stay fp32, and so do the GroupAll level, the FP levels and the heads."""
+``Uf``, the epilogues, the max and every output stay fp32, and so do the GroupAll level, the FP levels and the heads.
+
+``FrozenPointNet(net)`` is the same for ``networks.cls.pointnet.PointNet``: the five convs and the max over the points run as
+``pcl_pointnet_stack_infer_f32`` (csrc/infer_pointnet.hip: activations in LDS, nothing but per-tile maxima written), then the
+head.  It is constructed directly: ``frozen()`` keeps its PointNet++ dispatch."""
 import copy
 import ctypes
 
@@ -26,11 +30,13 @@ import torch
 
 from . import _lib
 from .misc.head import MAX_ROWS, fc_head
-from .misc.ops import _p, _stream, group_all, group_points, three_interpolate, three_nn
+from .misc.ops import (_lengths, _p, _stream, group_all, group_points, mlp_segment_max, pack_rows, packed_layout, three_interpolate,
+                       three_nn)
+from .networks.cls.pointnet import PointNet
 from .networks.cls.pointnet2 import PointNet2_cls
 from .networks.seg.pointnet2_partseg import PointNet2_partseg
 
-__all__ = ["frozen", "FrozenPointNet2", "FrozenPointNet2Partseg"]
+__all__ = ["frozen", "FrozenPointNet", "FrozenPointNet2", "FrozenPointNet2Partseg"]
 
 
 PRECISIONS = ("fp32", "bf16")
@@ -50,7 +56,7 @@ def frozen(net, precision="fp32"):
     if isinstance(net, PointNet2_partseg):
         return FrozenPointNet2Partseg(net, precision)
     raise TypeError(f"frozen() takes PointNet2_cls or PointNetMSG (PointNet++ classification) or PointNet2_partseg / its PointNetMSG "
-                    f"(PointNet++ part segmentation), got {type(net).__name__}")
+                    f"(PointNet++ part segmentation), got {type(net).__name__}; PointNet has FrozenPointNet(net)")
 
 
 def _eval_consts(mlp, l):
@@ -426,3 +432,87 @@ class FrozenPointNet2Partseg(_FrozenEncoder):
             if lengths is not None:                          # the head's bias / shift on FP1's zero pad rows
                 logits = self._zero_pads(logits, lengths)
         return [l1, l2, l3, f3, f2, f1], logits.permute(0, 2, 1)
+
+
+class FrozenPointNet:
+    """Frozen evaluator of ``networks.cls.pointnet.PointNet``: ``fnet(x, lengths=None) -> [B, n_classes]`` for ``x`` [B, 3, N] (the
+    network's input layout) of any strides -- a transposed view of a loader's [B, N, 3] is read as it is, no copy.  ``lengths``
+    (``misc.ops._lengths``): per-cloud point counts of a ragged batch of capacity N; pad points may hold anything and every cloud's
+    result is that of the cloud alone.  A device int32 tensor costs no host synchronisation and no packing.
+
+    ``plan`` is ``"fused"`` when ``net.convs`` has the kernel's shape (3 -> 64/64/64/128/1024, BatchNorm, activation after every
+    layer): dense weights, the eval constants of ``_eval_consts`` and the ctypes arrays are snapshot once, and a forward is
+    ``pcl_pointnet_stack_infer_f32`` + the eval-mode head kernels (at most ``MAX_ROWS`` rows per call).  A stack of other widths
+    gives ``"module"``: an eval-mode copy of ``net.convs`` runs, dense through ``group_max``, ragged through ``mlp_segment_max``.
+    ``refresh()`` re-reads weights and running statistics; ``net`` itself is never modified.
+
+    The class is constructed directly; ``frozen(net)`` still takes the PointNet++ networks only (its tests pin that), and taking
+    PointNet there is a later change."""
+
+    def __init__(self, net):
+        if not isinstance(net, PointNet):
+            raise TypeError(f"FrozenPointNet takes networks.cls.pointnet.PointNet, got {type(net).__name__}")
+        self.net = net
+        self._convs = self._head = None
+        self.refresh()
+
+    @staticmethod
+    def _refresh_copy(c, module):
+        if c is None:
+            return copy.deepcopy(module).eval()
+        c.load_state_dict(module.state_dict())            # same objects: the head kernels' plan cache keys on them
+        return c
+
+    @torch.no_grad()
+    def refresh(self):
+        net, mlp = self.net, self.net.convs
+        self._head = self._refresh_copy(self._head, torch.nn.Sequential(net.linear1, net.bn6, net.relu, net.dp1, net.linear2))
+        self.head = list(self._head)
+        widths = [w.shape[0] for w in mlp.weights]
+        L = len(widths)
+        c_widths = (ctypes.c_int32 * L)(*widths)
+        C0 = mlp.weights[0].shape[1]
+        fused = mlp.bn and mlp.last_act and bool(_lib.lib().pcl_pointnet_stack_infer_supported(C0, L, c_widths))
+        self.plan = "fused" if fused else "module"
+        if not fused:
+            self._convs = self._refresh_copy(self._convs, mlp)
+            return self
+        self.slope, self.width, self.c_widths = float(mlp.slope), widths[-1], c_widths
+        self.Ws = [w.detach().float().contiguous().clone() for w in mlp.weights]
+        consts = [_eval_consts(mlp, l) for l in range(L)]
+        self.scales, self.shifts = [c[0] for c in consts], [c[1] for c in consts]
+        self.c_W = (ctypes.c_void_p * L)(*[w.data_ptr() for w in self.Ws])
+        self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
+        self.c_shift = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.shifts])
+        return self
+
+    def __call__(self, x, lengths=None):
+        return self.run(x, lengths)[1]
+
+    def _stack(self, x, lengths):
+        B, C0, N = x.shape
+        if self.plan == "module":
+            if lengths is None:
+                return self._convs(x.transpose(1, 2).contiguous()[:, None], group_max=N).reshape(B, -1)
+            lengths, row_off, R, row_cloud = packed_layout(lengths, B, N, x.device)
+            return mlp_segment_max(self._convs, pack_rows(x.transpose(1, 2), lengths, row_off, R), row_off, row_cloud, B)
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise TypeError(f"FrozenPointNet: expected a float32 tensor on the GPU, got {x.dtype} on {x.device}")
+        lengths = _lengths(lengths, B, N, x.device)
+        ws_bytes = _lib.size_query("pcl_pointnet_stack_infer_workspace_bytes", B, N, self.width)
+        ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device)
+        out = torch.empty((B, self.width), dtype=torch.float32, device=x.device)
+        W0 = self.Ws[0]
+        _lib.call("pcl_pointnet_stack_infer_f32", _p(x), x.stride(0), x.stride(2), x.stride(1), _p(lengths), B, N, C0, _p(W0), W0.shape[1],
+                  len(self.Ws), self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(ws), ws_bytes, _p(out), out.shape[1],
+                  _stream())
+        return out
+
+    @torch.no_grad()
+    def run(self, x, lengths=None):
+        """-> (global feature [B, 1024], logits [B, n_classes])."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.net.convs.spec[0]:
+            raise ValueError(f"FrozenPointNet: x must be [B,{self.net.convs.spec[0]},N], got {tuple(getattr(x, 'shape', ()))}")
+        feature = self._stack(x, lengths)
+        logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, feature.shape[0], MAX_ROWS)]
+        return feature, logits[0] if len(logits) == 1 else torch.cat(logits)

@@ -14,6 +14,10 @@ compare three forms: ``eval`` (the network's default accumulation, fp64 flush ev
 interleaved windows, the same estimator), its ratio to the fp32 frozen form, the top-1 agreement of the two over the batch, and
 writes the JSON line to profiles/infer_bf16_bench_line.json as well.
 
+``--nets pointnet`` compares ``net.eval()`` under ``no_grad`` with ``FrozenPointNet(net)`` (B in {8, 32, 256}, N = 1024; both forms
+read the same dense [B,3,N] tensor) and writes the JSON line to profiles/infer_pointnet_bench_line.json; with ``--ragged`` the four
+forms below, the frozen form reading the [B,N,3] clouds through a transposed view (profiles/infer_pointnet_ragged_bench_line.json).
+
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
 (a) ``dense`` frozen at N, (b) ``ragged_full`` with every length = N, (c) ``ragged`` with the drawn lengths, (d) ``loop``: B calls
@@ -98,8 +102,8 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--batch", type=int, nargs="+", default=None, help="default: 32 256 (cls), 16 64 (part-seg)")
-    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg"])
+    ap.add_argument("--batch", type=int, nargs="+", default=None, help="default: 32 256 (cls), 16 64 (part-seg), 8 32 256 (pointnet)")
+    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg", "pointnet"])
     ap.add_argument("--points", type=int, default=None, help="default: 1024 (cls), 2048 (part-seg)")
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
     ap.add_argument("--precision", nargs="+", default=["fp32"], choices=["fp32", "bf16"],
@@ -112,7 +116,8 @@ def main():
     from pointcloudlib_amd.inference import frozen
     from pointcloudlib_amd.networks.cls.pointnet2 import PointNet2_cls, PointNetMSG
     dev = torch.device("cuda")
-    cls_only = all(k in ("ssg", "msg") for k in a.nets)
+    cls_only = all(k in ("ssg", "msg", "pointnet") for k in a.nets)
+    pointnet_only = all(k == "pointnet" for k in a.nets)
     res = {"N": (a.points or 1024) if cls_only else (a.points or 2048), "windows": a.windows, "iters": a.iters, "cases": []}
     if a.ragged:
         del res["N"]                 # every --ragged case carries its own N (classifiers and part-seg nets share one line)
@@ -125,11 +130,22 @@ def main():
             from pointcloudlib_amd.networks.seg.pointnet2_partseg import PointNet2_partseg, PointNetMSG as PartsegMSG
             net = (PointNet2_partseg if kind == "partseg_ssg" else PartsegMSG)().to(dev).eval()
             net0 = set_accumulation(copy.deepcopy(net), 0)
+        elif kind == "pointnet":
+            from pointcloudlib_amd.inference import FrozenPointNet
+            from pointcloudlib_amd.networks.cls.pointnet import PointNet
+            net = PointNet().to(dev).eval()
         else:
             net = (PointNet2_cls if kind == "ssg" else PointNetMSG)().to(dev).eval()
-        fnet = frozen(net)
-        fnet_bf16 = frozen(net, precision="bf16") if "bf16" in a.precision else None
-        for B in a.batch or ([16, 64] if seg else [32, 256]):
+        if kind == "pointnet":
+            fpn = FrozenPointNet(net)
+
+            def fnet(xyz, nrm, lengths=None):                 # the tool's call shape; [B,N,3] read through a transposed view
+                return fpn(xyz.transpose(1, 2), lengths)
+            fnet_bf16 = None
+        else:
+            fnet = frozen(net)
+            fnet_bf16 = frozen(net, precision="bf16") if "bf16" in a.precision else None
+        for B in a.batch or ([16, 64] if seg else [8, 32, 256] if kind == "pointnet" else [32, 256]):
             xyz = torch.from_numpy(synth.gauss_ball(B, N, 1)).to(dev)
             nrm = torch.from_numpy(synth.unit_normals(B, N, 2)).to(dev)
             extra = ()
@@ -144,6 +160,16 @@ def main():
 
             def frozen_fwd():
                 return fnet(xyz, nrm, *extra)
+
+            if kind == "pointnet":
+                x_cf = xyz.transpose(1, 2).contiguous()       # the network's input layout, made once: both forms read it
+
+                def eval_fwd(net=net):
+                    with torch.no_grad():
+                        return net(x_cf)
+
+                def frozen_fwd():
+                    return fpn(x_cf)
 
             if a.ragged:
                 res["cases"].append(_ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16))
@@ -189,7 +215,11 @@ def main():
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "infer_bf16_bench_line.json"), "w") as f:
             f.write(json.dumps(res) + "\n")
-    if a.ragged:
+    if pointnet_only and not a.frozen_only:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "infer_pointnet_ragged_bench_line.json" if a.ragged else "infer_pointnet_bench_line.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
+    elif a.ragged:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "infer_ragged_bench_line.json"), "w") as f:
             f.write(json.dumps(res) + "\n")

@@ -105,10 +105,10 @@ def main():
     ap.add_argument("--lr_decay", action="store_true")
     ap.add_argument("--synthetic_items", type=int, default=512)
     ap.add_argument("--seed", type=int, default=0, help="numpy (shuffles, augmentation: freeze_random_seed, train_cls.py:27-28) and torch (init)")
-    ap.add_argument("--fast_eval", action="store_true", help="--model pointnet2: validation through pointcloudlib_amd.inference.frozen(net)")
+    ap.add_argument("--fast_eval", action="store_true", help="--model pointnet2 | pointnet: validation through pointcloudlib_amd.inference (frozen(net) | FrozenPointNet(net))")
     a = ap.parse_args()
-    if a.fast_eval and a.model != "pointnet2":
-        raise SystemExit("--fast_eval: --model pointnet2 only")
+    if a.fast_eval and a.model not in ("pointnet2", "pointnet"):
+        raise SystemExit("--fast_eval: --model pointnet2 or pointnet only")
     if not torch.cuda.is_available():
         raise SystemExit("train_cls.py needs a GPU (the HIP path has no CPU fallback)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -130,8 +130,8 @@ def main():
     side = "own" if a.model == "pointnet2" else None     # sampling of batch t+1 beside batch t, on the network's private stream
     fnet = None
     if a.fast_eval:
-        from pointcloudlib_amd.inference import frozen
-        fnet = frozen(net)
+        from pointcloudlib_amd.inference import FrozenPointNet, frozen
+        fnet = FrozenPointNet(net) if a.model == "pointnet" else frozen(net)
     best = 0.0
     for epoch in range(a.epochs):
         if a.lr_decay and epoch and epoch % 20 == 0:
