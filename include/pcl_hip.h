@@ -888,6 +888,62 @@ int pcl_pointnet_stack_infer_f32(const float* x, size_t stride_b, size_t stride_
                                  const float* const* scale, const float* const* shift, float slope, void* workspace,
                                  size_t workspace_bytes, float* out, int ldo, void* stream);
 
+/* ---- Frozen inference: PointNet part segmentation in evaluation mode (csrc/infer_pointnet_seg.hip) -----
+ * networks/seg/pointnet_partseg.py:28-41 under net.eval() without the [B, N, 4944] concatenation and without out5: conv5 has no
+ * activation, so the head's first layer folds to K = 832 on a row buffer F [B*N, ldf] = out1 (64) | out2 (128) | out3 (128) |
+ * out4 (512) plus a per-cloud bias [B, 256]; the caller forms the folded weight.  Conventions of pcl_pointnet_stack_infer_f32:
+ * strides in floats, n_b = n_valid[b] clamped to [1, N] (NULL: N), pad points may hold NaN and reach no result, host arrays of L
+ * entries (widths, device pointers W / scale / shift with the eval constants), dense 16-byte aligned weights W[l] [C_l, C_{l-1}],
+ * never-cleared workspaces, no atomics, results bit for bit the same for any B, position, capacity, pad contents and run.
+ * Stacks with a kernel (pcl_pointnet_seg_infer_supported(stack, C0, L, widths); anything else returns PCL_EINVAL "no kernel"): */
+#define PCL_SEG_STN 0    /* 3 -> 64/128/1024 */
+#define PCL_SEG_TRUNK 1  /* 3 -> 64/128/128 */
+#define PCL_SEG_FSTN 2   /* 128 -> 64/128/1024 */
+#define PCL_SEG_GLOBAL 3 /* 128 -> 512/2048, the last layer without activation */
+#define PCL_SEG_HEAD 4   /* 832 -> 256/256/128/part_num, 1 <= part_num <= 128, the last layer linear + bias */
+int pcl_pointnet_seg_infer_supported(int stack, int C0, int L, const int32_t* widths);
+/* per-tile partial maxima of a C-wide max: 4 * B * ceil(N / 64) * C bytes */
+size_t pcl_pointnet_seg_part_workspace_bytes(int B, int N, int C);
+/* the row buffer F: 4 * B * N * ldf bytes, ldf >= 832 a multiple of 4 (0 for a smaller ldf) */
+size_t pcl_pointnet_seg_rows_workspace_bytes(int B, int N, int ldf);
+/* reference: STN3d's conv stack and max (misc/layers.py:22-39 in eval mode): out [B, ldo >= 1024]; W0 [64, 3] with row stride ldw0,
+ * W[0] ignored; workspace: pcl_pointnet_seg_part_workspace_bytes(B, N, 1024) */
+int pcl_pointnet_seg_stn_infer_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid, int B,
+                                   int N, int L, const int32_t* widths, const float* W0, int ldw0, const float* const* W,
+                                   const float* const* scale, const float* const* shift, float slope, void* workspace,
+                                   size_t workspace_bytes, float* out, int ldo, void* stream);
+/* reference: networks/seg/pointnet_partseg.py:43-50 and STNkd's conv stack and max: x' = x T3[b] (T3 [B, 3, 3], fmaf chains in
+ * ascending k), conv1-3 (W0 = conv1 [64, 3], W[0] ignored) stored into F[b*N + i, 0:320] for i < n_b, then the fstn stack (Ws,
+ * all three used) on out3 and its max: out [B, ldo >= 1024].  workspace as for the stn launch. */
+int pcl_pointnet_seg_trunk_infer_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid, int B,
+                                     int N, const float* T3, int L, const int32_t* widths, const float* W0, int ldw0,
+                                     const float* const* W, const float* const* scale, const float* const* shift, int Ls,
+                                     const int32_t* widths_s, const float* const* Ws, const float* const* scale_s,
+                                     const float* const* shift_s, float slope, float* F, int ldf, size_t f_bytes, void* workspace,
+                                     size_t workspace_bytes, float* out, int ldo, void* stream);
+/* reference: networks/seg/pointnet_partseg.py:51-57: out3 = F[., 192:320] times the cloud's own transform (TT [B, 128, 128],
+ * TT[b][j][k] = T128[b][k][j], 16-byte aligned), conv4 stored into F[., 320:832], conv5 (scale / shift, no activation) and its max:
+ * out [B, ldo >= 2048]; out5 is never stored.  workspace: pcl_pointnet_seg_part_workspace_bytes(B, N, 2048).  One workgroup per CU
+ * (a [64][516] fp32 tile of out4 in LDS). */
+int pcl_pointnet_seg_global_infer_f32(float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N, const float* TT, int L,
+                                      const int32_t* widths, const float* const* W, const float* const* scale,
+                                      const float* const* shift, float slope, void* workspace, size_t workspace_bytes, float* out,
+                                      int ldo, void* stream);
+/* reference: networks/seg/pointnet_partseg.py:60-66 with the folded first layer:
+ *   z1 = act(scale_1 * (W[0] F[row, 0:832] + cloud_bias[b]) + shift_1), z2, z3 as usual, logits = W[3] z3 + bias_out,
+ * W[0] [256, 832], W[3] [w_out_rows >= ceil(part_num / 32) * 32, 128] (rows >= part_num = widths[3]: any finite or non-finite
+ * contents, they reach no result), scale / shift of 3 layers.  out[b*stride_b + c*stride_c + i*stride_n], c < part_num, i < N:
+ * the network's [B, part_num, N] at its own strides; logits of pad points are exact zeros. */
+int pcl_pointnet_seg_head_infer_f32(const float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N,
+                                    const float* cloud_bias, int ldb, int L, const int32_t* widths, const float* const* W,
+                                    int w_out_rows, const float* const* scale, const float* const* shift, const float* bias_out,
+                                    float slope, float* out, size_t stride_b, size_t stride_c, size_t stride_n, void* stream);
+/* No reference counterpart: y[r, c] = act(scale[c] * (x[r] . W[c]) + shift[c]) for the B-row tails (the T-Nets' fully connected
+ * layers, the per-cloud bias): x [R, ldx], W [C, K] dense, K a multiple of 4 up to 2304, scale NULL = 1, slope 1 = no activation.
+ * One wave per column, the rows in turn, one fixed summation order: a row's result does not depend on R. */
+int pcl_pointnet_seg_rows_f32(const float* x, int ldx, int R, int K, const float* W, int C, const float* scale, const float* shift,
+                              float slope, float* y, int ldy, void* stream);
+
 /* ---- packed rows of a ragged batch (csrc/pack.hip) ------------------------------------------------
  * No reference counterpart.  What runs once per raw point of a ragged batch (FP1, the head and the loss of PointNet++ part
  * segmentation) runs on R = sum_b n_b rows, cloud after cloud without a pad row: n_b = n_valid[b] clamped to [1, N] (ragged

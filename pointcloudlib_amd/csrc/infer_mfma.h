@@ -73,6 +73,51 @@ __device__ __forceinline__ void mfma_layer(const float* __restrict__ X, const fl
     }
 }
 
+// The K-chunked form of mfma_layer: acc is NOT cleared, and W has row stride ldw -- the tile in LDS holds columns [k0, k0 + K)
+// of a wider input and W points at column k0 of a [*, ldw] matrix (16-byte aligned there).  Chunks accumulated in ascending
+// order give one fp32 chain per element in the k order of mfma_layer over the whole width.
+template <int K, int LDX, int NJ, int NCB>
+__device__ __forceinline__ void mfma_layer_acc(const float* __restrict__ X, const float* __restrict__ W, int ldw, int wave, int lane,
+                                               f32x16 (&acc)[2][NJ]) {
+    const int lr = lane & 31, lh = lane >> 5;
+    const float* xa0 = X + (size_t)lr * LDX + 4 * lh;
+    const float* xa1 = X + (size_t)(32 + lr) * LDX + 4 * lh;
+    const float* wb[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int cb = imax(0, wave + 4 * j < NCB ? wave + 4 * j : 0);
+        wb[j] = W + (size_t)(cb * 32 + lr) * ldw + 4 * lh;
+    }
+    float4 bn[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) bn[j] = *reinterpret_cast<const float4*>(wb[j]);
+#pragma unroll 2
+    for (int q = 0; q < K / 8; ++q) {
+        float4 b[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) b[j] = bn[j];
+        if (q + 1 < K / 8) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) bn[j] = *reinterpret_cast<const float4*>(wb[j] + 8 * (q + 1));
+        }
+        const float4 a0 = *reinterpret_cast<const float4*>(xa0 + 8 * q);
+        const float4 a1 = *reinterpret_cast<const float4*>(xa1 + 8 * q);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (wave + 4 * j < NCB) {
+                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b[j].x, acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b[j].x, acc[1][j], 0, 0, 0);
+                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b[j].y, acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b[j].y, acc[1][j], 0, 0, 0);
+                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b[j].z, acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b[j].z, acc[1][j], 0, 0, 0);
+                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b[j].w, acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b[j].w, acc[1][j], 0, 0, 0);
+            }
+        }
+    }
+}
+
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 

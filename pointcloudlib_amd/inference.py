@@ -22,7 +22,12 @@ take bf16 operands (activations rounded to nearest even, weights snapshot as bf1
 
 ``FrozenPointNet(net)`` is the same for ``networks.cls.pointnet.PointNet``: the five convs and the max over the points run as
 ``pcl_pointnet_stack_infer_f32`` (csrc/infer_pointnet.hip: activations in LDS, nothing but per-tile maxima written), then the
-head.  It is constructed directly: ``frozen()`` keeps its PointNet++ dispatch."""
+head.  It is constructed directly: ``frozen()`` keeps its PointNet++ dispatch.
+
+``FrozenPointNetPartseg(net)`` is the same for ``networks.seg.pointnet_partseg.PointNet_partseg`` (csrc/infer_pointnet_seg.hip,
+DESIGN.md section 20): ``conv5`` has no activation, so the head's 4944-wide first layer folds to 832 columns on a row buffer
+``out1 | out2 | out3 | out4`` plus a per-cloud bias (``fold_partseg_head``); neither the concatenation nor ``out5`` is ever
+stored."""
 import copy
 import ctypes
 
@@ -30,13 +35,15 @@ import torch
 
 from . import _lib
 from .misc.head import MAX_ROWS, fc_head
+from .misc.layers import PointwiseMLP
 from .misc.ops import (_lengths, _p, _stream, group_all, group_points, mlp_segment_max, pack_rows, packed_layout, three_interpolate,
-                       three_nn)
+                       three_nn, unpack_rows)
 from .networks.cls.pointnet import PointNet
 from .networks.cls.pointnet2 import PointNet2_cls
 from .networks.seg.pointnet2_partseg import PointNet2_partseg
+from .networks.seg.pointnet_partseg import PointNet_partseg
 
-__all__ = ["frozen", "FrozenPointNet", "FrozenPointNet2", "FrozenPointNet2Partseg"]
+__all__ = ["frozen", "FrozenPointNet", "FrozenPointNet2", "FrozenPointNet2Partseg", "FrozenPointNetPartseg"]
 
 
 PRECISIONS = ("fp32", "bf16")
@@ -516,3 +523,204 @@ class FrozenPointNet:
         feature = self._stack(x, lengths)
         logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, feature.shape[0], MAX_ROWS)]
         return feature, logits[0] if len(logits) == 1 else torch.cat(logits)
+
+
+# ---------------------------------------------------------------------------------------------- PointNet part segmentation
+PARTSEG_CONCAT = (2048, 16, 64, 128, 128, 512, 2048)     # the head's input blocks: g | label | out1 | out2 | out3 | out4 | out5
+
+
+def fold_partseg_head(Wh, W5, s5, t5, dtype=torch.float32):
+    """The head's first weight ``Wh`` [C, 4944] (column blocks ``PARTSEG_CONCAT``) with ``out5 = s5 * (W5 out4) + t5`` folded away:
+    -> (``Wrow`` [C, 832] on ``out1 | out2 | out3 | out4``, ``Wglob`` [C, 2064] on ``out_max | label``, ``c0`` [C]) with
+
+        Wh . concat = Wrow . [out1|out2|out3|out4] + Wglob . [out_max|label] + c0,
+        Wrow = [Wh_1 | Wh_2 | Wh_3 | Wh_4 + Wh_5 diag(s5) W5],  c0 = Wh_5 t5,  Wglob = [Wh_g | Wh_label].
+
+    Formed in fp64 and rounded once to ``dtype``; plain torch, any device."""
+    g, lab, o1, o2, o3, o4, o5 = Wh.detach().double().split(list(PARTSEG_CONCAT), dim=1)
+    W5, s5, t5 = W5.detach().double(), s5.detach().double(), t5.detach().double()
+    Wrow = torch.cat([o1, o2, o3, o4 + (o5 * s5) @ W5], dim=1)
+    return Wrow.to(dtype).contiguous(), torch.cat([g, lab], dim=1).to(dtype).contiguous(), (o5 @ t5).to(dtype).contiguous()
+
+
+def transposed_fc3(weight, bias, k):
+    """A T-Net's last layer with its rows permuted and the identity added to the bias: ``(g @ W.T + b).reshape(k, k)`` is the
+    TRANSPOSE of the module's ``(fc3(g) + I).reshape(k, k)`` -- the ``W[col][k]`` operand ``y = x @ T`` wants, with no transpose
+    per forward.  -> (W [k*k, C], b [k*k]); plain torch, any device."""
+    perm = torch.arange(k * k, device=weight.device).view(k, k).t().reshape(-1)
+    b = bias.detach() + torch.eye(k, device=weight.device, dtype=bias.dtype).reshape(-1)      # the identity is symmetric
+    return weight.detach()[perm].contiguous(), b[perm].contiguous()
+
+
+class _SegStack:
+    """Dense weights, eval constants and the ctypes arrays of consecutive layers ``[(mlp, l)]`` for the csrc/infer_pointnet_seg.hip
+    launchers."""
+
+    def __init__(self, layers, Ws=None):
+        self.Ws = [mlp.weights[l].detach().float().contiguous().clone() for mlp, l in layers] if Ws is None else Ws
+        consts = [_eval_consts(mlp, l) for mlp, l in layers]
+        self.scales, self.shifts = [c[0] for c in consts], [c[1] for c in consts]
+        self.L = len(self.Ws)
+        self.widths = (ctypes.c_int32 * self.L)(*[w.shape[0] for w in self.Ws])
+        self.c_W = (ctypes.c_void_p * self.L)(*[w.data_ptr() for w in self.Ws])
+        self.c_scale = (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in self.scales])
+        self.c_shift = (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in self.shifts])
+
+
+def _seg_rows(x, W, scale, shift, slope, out=None):
+    """``act(scale * (x W^T) + shift)`` on the B rows of x (pcl_pointnet_seg_rows_f32: a row's result does not depend on B)."""
+    R, K = x.shape
+    C = W.shape[0]
+    if out is None:
+        out = torch.empty((R, C), dtype=torch.float32, device=x.device)
+    _lib.call("pcl_pointnet_seg_rows_f32", _p(x), x.stride(0), R, K, _p(W), C, _p(scale), _p(shift), float(slope), _p(out), out.stride(0),
+              _stream())
+    return out
+
+
+class FrozenPointNetPartseg:
+    """Frozen evaluator of ``networks.seg.pointnet_partseg.PointNet_partseg``: ``fnet(point_cloud, label, lengths=None) ->
+    [B, part_num, N]`` for ``point_cloud`` [B, 3, N] of any strides and ``label`` [B, 16].  ``lengths`` (``misc.ops._lengths``):
+    per-cloud point counts of a ragged batch of capacity N; pad points may hold anything, every cloud's result is bit for bit
+    that of the cloud alone and the logits of pad points are exact zeros.  A device int32 tensor costs no host synchronisation.
+
+    ``plan`` is ``"fused"`` when every stack has its kernel's shape (``pcl_pointnet_seg_infer_supported``; BatchNorm and the
+    activation after every layer but ``conv5``'s, one slope): weights, eval constants, the folded head (``fold_partseg_head``)
+    and the transposed ``fstn.fc3`` (``transposed_fc3``) are snapshot once, and a forward is the four launches of
+    csrc/infer_pointnet_seg.hip with the B-row tails between them.  Anything else gives ``"module"``: an eval-mode copy of the
+    whole network runs (``forward``; ragged ``forward_packed`` scattered into zeros).  ``refresh()`` re-reads weights and running
+    statistics; ``net`` itself is never modified.  Constructed directly: ``frozen()`` keeps its PointNet++ dispatch."""
+
+    N_LABEL = 16
+    LDF = 832                      # row stride of the row buffer out1 | out2 | out3 | out4
+
+    def __init__(self, net):
+        if not isinstance(net, PointNet_partseg):
+            raise TypeError(f"FrozenPointNetPartseg takes networks.seg.pointnet_partseg.PointNet_partseg, got {type(net).__name__}")
+        self.net = net
+        self._module = None
+        self.refresh()
+
+    @staticmethod
+    def _fusable(net):
+        supported = _lib.lib().pcl_pointnet_seg_infer_supported
+        convs = [net.conv1, net.conv2, net.conv3, net.conv4, net.conv5]
+        mlps = [net.stn.convs, net.stn.fcs, net.fstn.convs, net.fstn.fcs, net.convs] + convs
+        if not all(isinstance(m, PointwiseMLP) and m.bn for m in mlps) or any(c.n_layers != 1 for c in convs):
+            return False
+        if not all(m.last_act for m in mlps if m is not net.conv5) or net.conv5.last_act or len({m.slope for m in mlps}) != 1:
+            return False
+        if not all(isinstance(f, torch.nn.Linear) and f.bias is not None for f in (net.stn.fc3, net.fstn.fc3, net.convs4)):
+            return False
+
+        def ok(stack, spec):
+            return bool(supported(_lib.define(stack), spec[0], len(spec) - 1, (ctypes.c_int32 * (len(spec) - 1))(*spec[1:])))
+
+        trunk = [net.conv1.spec[0], net.conv1.spec[1], net.conv2.spec[1], net.conv3.spec[1]]
+        chained = all(a.spec[-1] == b.spec[0] for a, b in zip(convs[:-1], convs[1:]))
+        tails = all(t.k * t.k == t.fc3.out_features and t.fcs.spec[0] == t.convs.spec[-1] and t.fcs.spec[-1] == t.fc3.in_features
+                    and all(c % 4 == 0 and c <= 2304 for c in t.fcs.spec) for t in (net.stn, net.fstn))
+        return (chained and tails and net.stn.k == 3 and net.fstn.k == 128 and net.convs.spec[0] == sum(PARTSEG_CONCAT)
+                and net.convs4.in_features == net.convs.spec[-1]
+                and ok("PCL_SEG_STN", net.stn.convs.spec) and ok("PCL_SEG_TRUNK", trunk) and ok("PCL_SEG_FSTN", net.fstn.convs.spec)
+                and ok("PCL_SEG_GLOBAL", [net.conv4.spec[0], net.conv4.spec[1], net.conv5.spec[1]])
+                and ok("PCL_SEG_HEAD", [FrozenPointNetPartseg.LDF] + net.convs.spec[1:] + [net.convs4.out_features]))
+
+    @staticmethod
+    def _tail(tnet, fc3):
+        """The B-row layers after a T-Net's max: [(W, scale | None, shift, slope)]"""
+        fcs = tnet.fcs
+        layers = []
+        for l in range(fcs.n_layers):
+            scale, shift = _eval_consts(fcs, l)
+            layers.append((fcs.weights[l].detach().float().contiguous().clone(), scale, shift, float(fcs.slope)))
+        return layers + [(fc3[0].float().contiguous().clone(), None, fc3[1].float().contiguous().clone(), 1.0)]
+
+    @torch.no_grad()
+    def refresh(self):
+        net = self.net
+        self.plan = "fused" if self._fusable(net) else "module"
+        if self.plan == "module":
+            self._module = FrozenPointNet._refresh_copy(self._module, net)
+            return self
+        self.slope, self.part_num = float(net.conv1.slope), net.convs4.out_features
+        self.stn = _SegStack([(net.stn.convs, l) for l in range(3)])
+        self.trunk = _SegStack([(net.conv1, 0), (net.conv2, 0), (net.conv3, 0)])
+        self.fstn = _SegStack([(net.fstn.convs, l) for l in range(3)])
+        self.glob = _SegStack([(net.conv4, 0), (net.conv5, 0)])
+        k3 = net.stn.k
+        eye3 = torch.eye(k3, device=net.stn.fc3.bias.device, dtype=net.stn.fc3.bias.dtype).reshape(-1)
+        self.stn_tail = self._tail(net.stn, (net.stn.fc3.weight.detach(), net.stn.fc3.bias.detach() + eye3))
+        self.fstn_tail = self._tail(net.fstn, transposed_fc3(net.fstn.fc3.weight, net.fstn.fc3.bias, net.fstn.k))
+        s5, t5 = self.glob.scales[1], self.glob.shifts[1]
+        Wrow, self.Wglob, self.c0 = fold_partseg_head(net.convs.weights[0], net.conv5.weights[0], s5, t5)
+        rows = -(-self.part_num // 32) * 32              # the last weight in whole 32-row blocks
+        Wout = torch.zeros((rows, net.convs4.in_features), dtype=torch.float32, device=Wrow.device)
+        Wout[:self.part_num] = net.convs4.weight.detach()
+        self.bias_out = net.convs4.bias.detach().float().contiguous().clone()
+        self.head = _SegStack([(net.convs, l) for l in range(3)],
+                              [Wrow] + [net.convs.weights[l].detach().float().contiguous().clone() for l in (1, 2)])
+        self.Wout = Wout
+        self.head_widths = (ctypes.c_int32 * 4)(*[w.shape[0] for w in self.head.Ws], self.part_num)
+        self.head_W = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in self.head.Ws], Wout.data_ptr())
+        return self
+
+    def __call__(self, point_cloud, label, lengths=None):
+        return self.run(point_cloud, label, lengths)[3]
+
+    @staticmethod
+    def _run_tail(layers, g):
+        for W, scale, shift, slope in layers:
+            g = _seg_rows(g, W, scale, shift, slope)
+        return g
+
+    @torch.no_grad()
+    def run(self, point_cloud, label, lengths=None):
+        """-> (T3 [B,3,3], T128 [B,128,128], out_max [B,2048], logits [B, part_num, N]); the ``"module"`` plan returns None for the
+        first three."""
+        x = point_cloud
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != 3:
+            raise ValueError(f"FrozenPointNetPartseg: point_cloud must be [B,3,N], got {tuple(getattr(x, 'shape', ()))}")
+        B, _, N = x.shape
+        if not isinstance(label, torch.Tensor) or tuple(label.shape) != (B, self.N_LABEL):
+            raise ValueError(f"FrozenPointNetPartseg: label must be [{B},{self.N_LABEL}], got {tuple(getattr(label, 'shape', ()))}")
+        if self.plan == "module":
+            if lengths is None:
+                return None, None, None, self._module(x, label)
+            rows, row_off = self._module.forward_packed(x, label, lengths)
+            lengths = _lengths(lengths, B, N, x.device)
+            return None, None, None, unpack_rows(rows, lengths, row_off, N).permute(0, 2, 1)
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise TypeError(f"FrozenPointNetPartseg: expected a float32 point cloud on the GPU, got {x.dtype} on {x.device}")
+        if label.device != x.device or label.dtype != torch.float32:
+            raise TypeError(f"FrozenPointNetPartseg: label must be float32 on {x.device}, got {label.dtype} on {label.device}")
+        dev, st = x.device, _stream()
+        lengths = _lengths(lengths, B, N, dev)
+        ws_bytes = _lib.size_query("pcl_pointnet_seg_part_workspace_bytes", B, N, 2048)
+        f_bytes = _lib.size_query("pcl_pointnet_seg_rows_workspace_bytes", B, N, self.LDF)
+        ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
+        F = torch.empty((f_bytes // 4,), dtype=torch.float32, device=dev)
+        strides = (x.stride(0), x.stride(2), x.stride(1))
+        s = self.stn
+        g = torch.empty((B, 1024), dtype=torch.float32, device=dev)
+        _lib.call("pcl_pointnet_seg_stn_infer_f32", _p(x), *strides, _p(lengths), B, N, s.L, s.widths, _p(s.Ws[0]), 3, s.c_W, s.c_scale,
+                  s.c_shift, self.slope, _p(ws), ws_bytes, _p(g), 1024, st)
+        T3 = self._run_tail(self.stn_tail, g)
+        c, s = self.trunk, self.fstn
+        g = torch.empty((B, 1024), dtype=torch.float32, device=dev)
+        _lib.call("pcl_pointnet_seg_trunk_infer_f32", _p(x), *strides, _p(lengths), B, N, _p(T3), c.L, c.widths, _p(c.Ws[0]), 3, c.c_W,
+                  c.c_scale, c.c_shift, s.L, s.widths, s.c_W, s.c_scale, s.c_shift, self.slope, _p(F), self.LDF, f_bytes, _p(ws), ws_bytes,
+                  _p(g), 1024, st)
+        TT = self._run_tail(self.fstn_tail, g)
+        c = self.glob
+        glob = torch.empty((B, 2048 + self.N_LABEL), dtype=torch.float32, device=dev)      # out_max | label
+        glob[:, 2048:] = label
+        _lib.call("pcl_pointnet_seg_global_infer_f32", _p(F), self.LDF, f_bytes, _p(lengths), B, N, _p(TT), c.L, c.widths, c.c_W, c.c_scale,
+                  c.c_shift, self.slope, _p(ws), ws_bytes, _p(glob), glob.stride(0), st)
+        bias = _seg_rows(glob, self.Wglob, None, self.c0, 1.0)
+        h = self.head
+        out = torch.empty((B, self.part_num, N), dtype=torch.float32, device=dev)
+        _lib.call("pcl_pointnet_seg_head_infer_f32", _p(F), self.LDF, f_bytes, _p(lengths), B, N, _p(bias), bias.stride(0), 4,
+                  self.head_widths, self.head_W, self.Wout.shape[0], h.c_scale, h.c_shift, _p(self.bias_out), self.slope, _p(out),
+                  out.stride(0), out.stride(1), out.stride(2), st)
+        return T3.view(B, 3, 3), TT.view(B, 128, 128).transpose(1, 2), glob[:, :2048], out

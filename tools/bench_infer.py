@@ -18,6 +18,11 @@ writes the JSON line to profiles/infer_bf16_bench_line.json as well.
 read the same dense [B,3,N] tensor) and writes the JSON line to profiles/infer_pointnet_bench_line.json; with ``--ragged`` the four
 forms below, the frozen form reading the [B,N,3] clouds through a transposed view (profiles/infer_pointnet_ragged_bench_line.json).
 
+``--nets pointnet_partseg`` compares ``net.eval()`` under ``no_grad`` with ``FrozenPointNetPartseg(net)`` (B in {16, 64}, N = 2048;
+both forms read the same dense [B,3,N] tensor and the same one-hot label) with the peak memory of both, and writes the JSON line
+to profiles/infer_pointnet_partseg_bench_line.json; with ``--ragged`` the four forms below
+(profiles/infer_pointnet_partseg_ragged_bench_line.json).
+
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
 (a) ``dense`` frozen at N, (b) ``ragged_full`` with every length = N, (c) ``ragged`` with the drawn lengths, (d) ``loop``: B calls
@@ -102,8 +107,8 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--batch", type=int, nargs="+", default=None, help="default: 32 256 (cls), 16 64 (part-seg), 8 32 256 (pointnet)")
-    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg", "pointnet"])
+    ap.add_argument("--batch", type=int, nargs="+", default=None, help="default: 32 256 (cls), 16 64 (part-seg, pointnet_partseg), 8 32 256 (pointnet)")
+    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg", "pointnet", "pointnet_partseg"])
     ap.add_argument("--points", type=int, default=None, help="default: 1024 (cls), 2048 (part-seg)")
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
     ap.add_argument("--precision", nargs="+", default=["fp32"], choices=["fp32", "bf16"],
@@ -118,12 +123,14 @@ def main():
     dev = torch.device("cuda")
     cls_only = all(k in ("ssg", "msg", "pointnet") for k in a.nets)
     pointnet_only = all(k == "pointnet" for k in a.nets)
+    pn_partseg_only = all(k == "pointnet_partseg" for k in a.nets)
     res = {"N": (a.points or 1024) if cls_only else (a.points or 2048), "windows": a.windows, "iters": a.iters, "cases": []}
     if a.ragged:
         del res["N"]                 # every --ragged case carries its own N (classifiers and part-seg nets share one line)
     for kind in a.nets:
         seg = kind.startswith("partseg")
-        N = a.points or (2048 if seg else 1024)
+        pn_seg = kind == "pointnet_partseg"
+        N = a.points or (2048 if seg or pn_seg else 1024)
         torch.manual_seed(0)
         if seg:
             from pointcloudlib_amd.misc.layers import set_accumulation
@@ -134,6 +141,10 @@ def main():
             from pointcloudlib_amd.inference import FrozenPointNet
             from pointcloudlib_amd.networks.cls.pointnet import PointNet
             net = PointNet().to(dev).eval()
+        elif pn_seg:
+            from pointcloudlib_amd.inference import FrozenPointNetPartseg
+            from pointcloudlib_amd.networks.seg.pointnet_partseg import PointNet_partseg
+            net = PointNet_partseg().to(dev).eval()
         else:
             net = (PointNet2_cls if kind == "ssg" else PointNetMSG)().to(dev).eval()
         if kind == "pointnet":
@@ -142,14 +153,20 @@ def main():
             def fnet(xyz, nrm, lengths=None):                 # the tool's call shape; [B,N,3] read through a transposed view
                 return fpn(xyz.transpose(1, 2), lengths)
             fnet_bf16 = None
+        elif pn_seg:
+            fps = FrozenPointNetPartseg(net)
+
+            def fnet(xyz, nrm, onehot, lengths=None):         # the tool's call shape; [B,N,3] read through a transposed view
+                return fps(xyz.transpose(1, 2), onehot, lengths)
+            fnet_bf16 = None
         else:
             fnet = frozen(net)
             fnet_bf16 = frozen(net, precision="bf16") if "bf16" in a.precision else None
-        for B in a.batch or ([16, 64] if seg else [8, 32, 256] if kind == "pointnet" else [32, 256]):
+        for B in a.batch or ([16, 64] if seg or pn_seg else [8, 32, 256] if kind == "pointnet" else [32, 256]):
             xyz = torch.from_numpy(synth.gauss_ball(B, N, 1)).to(dev)
             nrm = torch.from_numpy(synth.unit_normals(B, N, 2)).to(dev)
             extra = ()
-            if seg:
+            if seg or pn_seg:
                 onehot = torch.zeros(B, 16, device=dev)
                 onehot[torch.arange(B), torch.arange(B) % 16] = 1.0
                 extra = (onehot,)
@@ -171,6 +188,16 @@ def main():
                 def frozen_fwd():
                     return fpn(x_cf)
 
+            if pn_seg:
+                x_cf = xyz.transpose(1, 2).contiguous()       # the network's input layout, made once: both forms read it
+
+                def eval_fwd(net=net):
+                    with torch.no_grad():
+                        return net(x_cf, onehot)
+
+                def frozen_fwd():
+                    return fps(x_cf, onehot)
+
             if a.ragged:
                 res["cases"].append(_ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16))
                 continue
@@ -189,7 +216,7 @@ def main():
             for w in range(a.windows):
                 for name, fn in (forms if w % 2 == 0 else forms[::-1]):
                     times[name].append(_window(fn, a.iters))
-            case = {"net": kind, "B": B, "N": N} if seg else {"net": kind, "B": B}
+            case = {"net": kind, "B": B, "N": N} if seg or pn_seg else {"net": kind, "B": B}
             for name, fn in forms:
                 case[f"{name}_ms"] = round(statistics.median(times[name]), 4)
                 case[f"{name}_ms_min"] = round(min(times[name]), 4)
@@ -200,6 +227,7 @@ def main():
                 case["speedup"] = round(case["eval_ms"] / case["frozen_ms"], 3)
                 if seg:
                     case["speedup_vs_acc0"] = round(case["eval_acc0_ms"] / case["frozen_ms"], 3)
+                if seg or pn_seg:
                     case["mem_ratio"] = round(case["eval_peak_mib"] / max(case["frozen_peak_mib"], 0.1), 1)
                 with torch.no_grad():
                     case["max_abs_logit_diff"] = float((eval_fwd() - frozen_fwd()).abs().max())
@@ -218,6 +246,11 @@ def main():
     if pointnet_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "infer_pointnet_ragged_bench_line.json" if a.ragged else "infer_pointnet_bench_line.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
+    elif pn_partseg_only and not a.frozen_only:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        name = "infer_pointnet_partseg_ragged_bench_line.json" if a.ragged else "infer_pointnet_partseg_bench_line.json"
+        with open(os.path.join(ROOT, "profiles", name), "w") as f:
             f.write(json.dumps(res) + "\n")
     elif a.ragged:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
