@@ -254,6 +254,11 @@ int pcl_group_linear_bwd_regen_f32(const float* row_loc, const float* row_feat, 
 int pcl_group_linear_bwd_gather_regen_f32(const float* row_loc, const float* dU, const float* Uf, const float* Wx, int ldw, const float* a,
                                           const float* k1, const float* k2, const float* mu, const int32_t* in_off, const int32_t* in_rows,
                                           int B, int N, int C1, float* dUf, float* dWx_part, float* dW0, int ld0, void* stream);
+/* The reduce those calls end with, on its own: dW0[c][0..2] = sum_r dWx_part[r][c][0..2], dW0[c][off + f] = sum_r dWf_part[r][c][f] over
+ * `rows` partial rows (either part may be NULL; dW0 has leading dimension ld).  One wave per element: lane l adds the rows l, l + 64, ...
+ * in ascending order from 0, then the lanes fold by the xor tree 32 .. 1. */
+int pcl_group_linear_dw_sum_f32(const float* dWx_part, const float* dWf_part, int rows, int C1, int CF, int off, int ld, float* dW0,
+                                void* stream);
 
 /* The classification head on R <= 64 rows (one row per cloud): Linear (+bias) -> BatchNorm1d -> (Leaky)ReLU as ONE kernel
  * per layer (networks/cls/pointnet2.py:138-147, dgcnn.py:87-93, pointnet.py:22-38).  X [R,K], W [N,K] (nn.Linear layout).
@@ -476,6 +481,9 @@ int pcl_bn_rows_bwd_apply_f32(const float* g, const float* x, const float* a, co
 /* reference: gradient of the max over nsample, networks/cls/pointnet2.py:57 */
 int pcl_maxgrad_prep_f32(const float* gout, const float* out, const float* ymax, float slope, int G, int C,
                          float* gz, double* stats_ws, int* stat_rows_out, void* stream);
+/* the same with gout's rows ldg >= C floats apart (a column slice of a wider gradient: the consumer concatenated several stacks' outputs) */
+int pcl_maxgrad_prep_ld_f32(const float* gout, int ldg, const float* out, const float* ymax, float slope, int G, int C,
+                            float* gz, double* stats_ws, int* stat_rows_out, void* stream);
 /* BatchNorm backward constants from (sum du, sum du*y): dgamma, dbeta (nullable) and a, k1, k2 with
  * dy = a*du - k1 - k2*(y - mean)   (k1 = a*dbeta/P, k2 = a*dgamma*invstd/P; y is centred where it is used).
  * dbias_zero [C] (nullable) is cleared: the gradient of a conv bias that feeds training-mode BatchNorm is exactly 0. */
@@ -575,6 +583,14 @@ int pcl_linear_bwd_pair_finish_f32(const void* workspace, size_t workspace_bytes
                                    const double* stats_ws, int stat_rows, const float* gamma_prev, const float* mean_prev,
                                    const float* invstd_prev, int P_bn, float* dgamma_prev, float* dbeta_prev,
                                    float* a_prev, float* k1_prev, float* k2_prev, float* dbias_zero_prev, void* stream);
+/* pcl_linear_bwd_pair_finish_f32 that also carries the coordinate columns of a folded first layer's weight gradient, as the stack's backward
+ * launches it: extra workgroups form xdW0[c * xld + 0..2] = sum_r xpart[r][c][0..2] over xrows partial rows -- the sum of
+ * pcl_group_linear_dw_sum_f32 in the same order, bit for bit.  xpart = NULL: the plain finish. */
+int pcl_linear_bwd_pair_finish_xyz_f32(const void* workspace, size_t workspace_bytes, int P, int Cout, int Cin, float* dW, int dw_ld,
+                                       const double* stats_ws, int stat_rows, const float* gamma_prev, const float* mean_prev,
+                                       const float* invstd_prev, int P_bn, float* dgamma_prev, float* dbeta_prev,
+                                       float* a_prev, float* k1_prev, float* k2_prev, float* dbias_zero_prev,
+                                       const float* xpart, int xrows, int xC1, int xld, float* xdW0, void* stream);
 void pcl_set_bwd_pair(int on);
 int pcl_get_bwd_pair(void);
 /* Matrix-pipe form of the GEMM family (no reference counterpart: the reference calls cuDNN / cuBLAS fp32 through jittor's nn.Conv /

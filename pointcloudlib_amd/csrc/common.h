@@ -146,6 +146,27 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
     return min(min(a, b), min(c, d));
 }
 
+// A thread's walk over the rows r, r + step, ... < n with U rows requested before the first is used: use(q, load(q)) runs in ascending
+// q exactly as the one-load-per-trip loop would, so whatever it accumulates or compares comes out the same bits -- but a trip costs
+// one memory round trip per U rows instead of one per row.  (The plain loop compiles to load, wait for it, use, branch: the compiler
+// does not hoist the next trip's load across the loop-carried compare or add.)  Fewer than U rows left: batches of U/2, U/4, .. 1,
+// each at most once -- no padding, no row touched that the plain loop would not touch.
+template <int U, class L, class F>
+__device__ __forceinline__ void rows_in_flight(int r, int step, int n, L&& load, F&& use) {
+    for (; r + (U - 1) * step < n; r += U * step) {
+        decltype(load(r)) v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = load(r + u * step);
+#pragma unroll
+        for (int u = 0; u < U; ++u) use(r + u * step, v[u]);
+    }
+    if constexpr (U > 1) rows_in_flight<U / 2>(r, step, n, load, use);
+}
+// the same over one column x[q * ld]
+template <int U, class T, class F>
+__device__ __forceinline__ void rows_in_flight(const T* __restrict__ x, size_t ld, int r, int step, int n, F&& use) {
+    rows_in_flight<U>(r, step, n, [&](int q) { return x[(size_t)q * ld]; }, use);
+}
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // number of set bits of `mask` strictly below this lane

@@ -12,7 +12,7 @@
 
 namespace pcl {
 
-// goff[g] = sum_{h<g} max(cnt[h],1); goff[G] = P_eff.  One workgroup, 1024 lanes, sequential chunks + LDS scan.
+// goff[g] = sum_{h<g} max(cnt[h],1); goff[G] = P_eff.  One workgroup of 16 waves, a span of consecutive counts per wave.
 struct GoffMulti { const int32_t* cnt[4]; int32_t* goff[4]; };
 __device__ __forceinline__ void group_offsets_body(const int32_t* __restrict__ cnt, int G, int32_t* __restrict__ goff);
 __global__ __launch_bounds__(1024) void group_offsets_kernel(const int32_t* __restrict__ cnt, int G, int32_t* __restrict__ goff) {
@@ -23,23 +23,33 @@ __global__ __launch_bounds__(1024) void group_offsets_multi_kernel(const GoffMul
     group_offsets_body(a.cnt[blockIdx.x], G, a.goff[blockIdx.x]);
 }
 __device__ __forceinline__ void group_offsets_body(const int32_t* __restrict__ cnt, int G, int32_t* __restrict__ goff) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int per = (G + 1023) / 1024;
-    const int lo = min(t * per, G), hi = min(lo + per, G);
+    // wave w owns the consecutive counts [w * per, (w + 1) * per), per a multiple of 64, and walks them 64 at a time: a wave's load
+    // or store is one 256-byte piece, 8 pieces requested before the first is used.  (Integer sums: exact in any order -- goff is what
+    // the sequential scan gives.)  Pass 1 sums each wave's span, pass 2 reads it again (from L2) and scans it from the wave's base.
+    __shared__ int tot[16];
+    constexpr int U = 8;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int per = ((G + 15) / 16 + 63) / 64 * 64;
+    const int lo = min(w * per, G), hi = min(lo + per, G);
     int s = 0;
-    for (int g = lo; g < hi; ++g) s += max(cnt[g], 1);
-    part[t] = s;
+    rows_in_flight<U>(cnt, 1, lo + lane, 64, hi, [&](int, int v) { s += max(v, 1); });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) tot[w] = s;
     __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - s;                       // exclusive prefix of this thread's chunk
-    for (int g = lo; g < hi; ++g) { goff[g] = run; run += max(cnt[g], 1); }
-    if (t == 1023) goff[G] = part[1023];
+    int run = 0, all = 0;                        // exclusive prefix of this wave's span; the total
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { const int t = tot[j]; run += j < w ? t : 0; all += t; }
+    // (a piece's lanes past hi load the span's last count instead: lanes below them never see it, and nothing is stored for them)
+    rows_in_flight<U>(lo, 64, hi, [&](int g0) { return max(cnt[min(g0 + lane, hi - 1)], 1); },
+                      [&](int g0, int v) {
+                          int inc = v;           // inclusive scan over the wave's 64 lanes
+#pragma unroll
+                          for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+                          if (g0 + lane < hi) goff[g0 + lane] = run + inc - v;
+                          run += __shfl(inc, 63);
+                      });
+    if (threadIdx.x == 0) goff[G] = all;
 }
 
 // One workgroup per group, wave w takes the slots [w*chunk, (w+1)*chunk) of the group's c distinct ones.
@@ -873,7 +883,7 @@ __global__ __launch_bounds__(256) void group_linear_dw_kernel(const float* __res
     const float* src = isx ? px + e : pf + (e - nx);
     const int n = isx ? nx : nf;
     float s = 0.f;
-    for (int r = lane; r < rows; r += 64) s += src[(size_t)r * n];
+    rows_in_flight<8>(src, n, lane, 64, rows, [&](int, float v) { s += v; });      // (1024 partial rows: 16 per lane, 8 in flight)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) {
@@ -1052,6 +1062,16 @@ int pcl::group_linear_bwd_impl(const float* row_loc, const float* row_feat, int 
     const int n = (dWx_part ? C1 * 3 : 0) + (dWf_part ? C1 * CF : 0);
     hipLaunchKernelGGL(group_linear_dw_kernel, dim3((n + 3) / 4), block, 0, st, dWx_part, dWf_part, GL_BLOCKS, C1, CF, off, ldw, dW0);
     return check_launch("pcl_group_linear_bwd_f32(dW)");
+}
+
+extern "C" int pcl_group_linear_dw_sum_f32(const float* dWx_part, const float* dWf_part, int rows, int C1, int CF, int off, int ld, float* dW0,
+                                           void* stream) {
+    PCL_REQUIRE((dWx_part || dWf_part) && dW0 && rows >= 1 && C1 >= 1, "pcl_group_linear_dw_sum_f32: bad arguments");
+    PCL_REQUIRE(!dWf_part || CF >= 1, "pcl_group_linear_dw_sum_f32: dWf_part needs CF >= 1");
+    PCL_REQUIRE(ld >= (dWx_part ? 3 : 0) && off >= 0 && ld >= off + (dWf_part ? CF : 0), "pcl_group_linear_dw_sum_f32: ld=%d below off=%d + CF", ld, off);
+    const int n = (dWx_part ? C1 * 3 : 0) + (dWf_part ? C1 * CF : 0);
+    hipLaunchKernelGGL(group_linear_dw_kernel, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), dWx_part, dWf_part, rows, C1, CF, off, ld, dW0);
+    return check_launch("pcl_group_linear_dw_sum_f32");
 }
 
 /* in_off [B*N + 1], in_rows [group_off[B*m]]: every source point's rows (indices into the compacted row table), ascending */

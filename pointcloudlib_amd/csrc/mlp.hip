@@ -2773,11 +2773,10 @@ __global__ __launch_bounds__(256) void bn_act_max_kernel(const float* __restrict
         const float* y = Y + g * ns * C + c;
         float best = -INFINITY, by = 0.f;
         int bi = 0;
-        for (int s = 0; s < ns; ++s) {
-            const float yy = y[(size_t)s * C];
+        rows_in_flight<8>(y, C, 0, 1, ns, [&](int s, float yy) {
             const float z = lrelu(fmaf(a, yy, b), slope);
             if (z > best) { best = z; bi = s; by = yy; }
-        }
+        });
         out[e] = best;
         if (arg) arg[e] = bi;
         if (ymax) ymax[e] = by;
@@ -2801,11 +2800,10 @@ __global__ __launch_bounds__(64 * SL) void bn_act_max_sliced_kernel(const float*
     if (c < C) {
         const float a = scale[c], b = shift[c];
         const float* y = Y + (size_t)g * ns * C + c;
-        for (int s = sl; s < ns; s += SL) {
-            const float yy = y[(size_t)s * C];
+        rows_in_flight<8>(y, C, sl, SL, ns, [&](int s, float yy) {      // (ns = 128, SL = 4: 32 rows per thread, 8 in flight)
             const float z = lrelu(fmaf(a, yy, b), slope);
             if (z > best) { best = z; bi = s; by = yy; }
-        }
+        });
     }
     sz[sl][cl] = best; sy[sl][cl] = by; ss[sl][cl] = bi;
     __syncthreads();
@@ -2842,11 +2840,11 @@ __global__ __launch_bounds__(64 * SL) void bn_act_maxmean_sliced_kernel(const fl
     if (c < C) {
         const float a = scale[c], b = shift[c];
         const float* y = Y + (size_t)g * ns * C + c;
-        for (int s = sl; s < ns; s += SL) {
-            const float z = lrelu(fmaf(a, y[(size_t)s * C], b), slope);
+        rows_in_flight<8>(y, C, sl, SL, ns, [&](int s, float yy) {
+            const float z = lrelu(fmaf(a, yy, b), slope);
             if (z > best) { best = z; bi = s; }
             sum += (double)z;
-        }
+        });
     }
     sz[sl][cl] = best; ss[sl][cl] = bi; sm[sl][cl] = sum;
     __syncthreads();
@@ -2919,13 +2917,17 @@ __global__ __launch_bounds__(256) void maxgrad_prep_kernel(const float* __restri
     const int RS = 256 / CW, rsub = threadIdx.x / CW;
     const int c = blockIdx.x * CW + threadIdx.x % CW;
     double s1 = 0.0, s2 = 0.0;
-    if (c < C)
-        for (int g = blockIdx.y * RS + rsub; g < G; g += gridDim.y * RS) {
-            const size_t e = (size_t)g * C + c;
-            const float v = gout[(size_t)g * ldg + c] * (out[e] > 0.f ? 1.f : slope);
-            gz[e] = v;
-            s1 += v; s2 += (double)v * ymax[e];
-        }
+    if (c < C) {
+        // 8 rows' operands in flight (rows_in_flight, common.h): rows in ascending order, so gz and both fp64 sums are the plain loop's
+        struct Row { float g, o, y; };
+        rows_in_flight<8>(blockIdx.y * RS + rsub, gridDim.y * RS, G,
+                          [&](int g) { const size_t e = (size_t)g * C + c; return Row{gout[(size_t)g * ldg + c], out[e], ymax[e]}; },
+                          [&](int g, const Row& r) {
+                              const float v = r.g * (r.o > 0.f ? 1.f : slope);
+                              gz[(size_t)g * C + c] = v;
+                              s1 += v; s2 += (double)v * r.y;
+                          });
+    }
     fold_row_lanes(s1, s2, c, rsub, RS, CW, C, red, stats + (size_t)blockIdx.y * 2 * C);
 }
 
@@ -3400,6 +3402,15 @@ extern "C" int pcl_linear_bwd_pair_finish_f32(const void* workspace, size_t work
     return pair_finish_impl(workspace, workspace_bytes, P, Cout, Cin, dW, dw_ld, stats_ws, stat_rows, gamma_prev, mean_prev, invstd_prev, P_bn, dgamma_prev,
                             dbeta_prev, a_prev, k1_prev, k2_prev, dbias_zero_prev, stream, nullptr, 0, 0, 0, nullptr);
 }
+extern "C" int pcl_linear_bwd_pair_finish_xyz_f32(const void* workspace, size_t workspace_bytes, int P, int Cout, int Cin, float* dW, int dw_ld,
+                                                  const double* stats_ws, int stat_rows, const float* gamma_prev, const float* mean_prev,
+                                                  const float* invstd_prev, int P_bn, float* dgamma_prev, float* dbeta_prev,
+                                                  float* a_prev, float* k1_prev, float* k2_prev, float* dbias_zero_prev,
+                                                  const float* xpart, int xrows, int xC1, int xld, float* xdW0, void* stream) {
+    PCL_REQUIRE(!xpart || (xdW0 && xrows >= 1 && xC1 >= 1 && xld >= 3), "pcl_linear_bwd_pair_finish_xyz_f32: xpart needs xdW0, xrows, xC1 >= 1 and xld >= 3");
+    return pair_finish_impl(workspace, workspace_bytes, P, Cout, Cin, dW, dw_ld, stats_ws, stat_rows, gamma_prev, mean_prev, invstd_prev, P_bn, dgamma_prev,
+                            dbeta_prev, a_prev, k1_prev, k2_prev, dbias_zero_prev, stream, xpart, xrows, xC1, xld, xdW0);
+}
 // (xpart ..: the coordinate-weight partials of a folded first layer [xrows][xC1][3] summed into xdW0[c * xld + 0..2] by extra blocks of this launch)
 int pcl::pair_finish_impl(const void* workspace, size_t workspace_bytes, int P, int Cout, int Cin, float* dW, int dw_ld,
                           const double* stats_ws, int stat_rows, const float* gamma_prev, const float* mean_prev,
@@ -3658,6 +3669,10 @@ int maxgrad_prep_impl(const float* gout, const float* out, const float* ymax, fl
 extern "C" int pcl_maxgrad_prep_f32(const float* gout, const float* out, const float* ymax, float slope, int G, int C,
                                     float* gz, double* stats_ws, int* stat_rows_out, void* stream) {
     return maxgrad_prep_impl(gout, out, ymax, slope, G, C, gz, stats_ws, stat_rows_out, stream, nullptr, 0, nullptr, 0, 0, C);
+}
+extern "C" int pcl_maxgrad_prep_ld_f32(const float* gout, int ldg, const float* out, const float* ymax, float slope, int G, int C,
+                                       float* gz, double* stats_ws, int* stat_rows_out, void* stream) {
+    return maxgrad_prep_impl(gout, out, ymax, slope, G, C, gz, stats_ws, stat_rows_out, stream, nullptr, 0, nullptr, 0, 0, ldg);
 }
 int pcl::maxgrad_prep_impl(const float* gout, const float* out, const float* ymax, float slope, int G, int C, float* gz, double* stats_ws,
                            int* stat_rows_out, void* stream, float* zero, size_t n_zero, float* ones, int n_one, int n_one0, int ldg) {
