@@ -903,6 +903,20 @@ int pcl_pointnet_stack_infer_f32(const float* x, size_t stride_b, size_t stride_
                                  int N, int C0, const float* W0, int ldw0, int L, const int32_t* widths, const float* const* W,
                                  const float* const* scale, const float* const* shift, float slope, void* workspace,
                                  size_t workspace_bytes, float* out, int ldo, void* stream);
+/* No reference counterpart: the same stack with bf16 matrix operands (FrozenPointNet(net, precision="bf16")).  Arguments, checks,
+ * the "no kernel" error, workspace and contract of pcl_pointnet_stack_infer_f32, except that W[l], l >= 1, are bf16
+ * [C_l, C_{l-1}] dense, 16-byte aligned (W[0] ignored: layer 1 reads the fp32 W0), and that slope must lie in [0, 1] (the last
+ * epilogue runs on the extreme accumulators of a tile, which needs act monotone).  Every check runs before any HIP call.
+ * Numerics: layer 1 is the fp32 fmaf expression of pcl_pointnet_stack_infer_f32 with its epilogue in fp32, z_1 rounded to
+ * nearest even to bf16; y_l (l >= 2) = bf16 x bf16 products accumulated in fp32 (v_mfma_f32_32x32x16_bf16, k-blocks of 16
+ * ascending); every epilogue act(scale_l * y_l + shift_l) in fp32; z_2 .. z_{L-1} rounded to nearest even to bf16; z_L is never
+ * rounded, the max, the partials and out are fp32; W0, scale and shift stay fp32.  A cloud's output depends only on its own valid
+ * points: bit for bit the same for any B, position in the batch, capacity N, pad contents, split count, rows per workgroup and
+ * run; no atomics.  pcl_pointnet_stack_infer_supported, _workspace_bytes and _splits answer for both precisions. */
+int pcl_pointnet_stack_infer_bf16_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid, int B,
+                                      int N, int C0, const float* W0, int ldw0, int L, const int32_t* widths, const void* const* W,
+                                      const float* const* scale, const float* const* shift, float slope, void* workspace,
+                                      size_t workspace_bytes, float* out, int ldo, void* stream);
 
 /* ---- Frozen inference: PointNet part segmentation in evaluation mode (csrc/infer_pointnet_seg.hip) -----
  * networks/seg/pointnet_partseg.py:28-41 under net.eval() without the [B, N, 4944] concatenation and without out5: conv5 has no

@@ -1,4 +1,4 @@
-// infer_mfma.h -- the fp32-MFMA layer step shared by the frozen-inference kernels (infer.hip, infer_fp.hip).
+// infer_mfma.h -- the fp32-MFMA layer step shared by the frozen-inference kernels (infer.hip, infer_fp.hip, infer_pointnet.hip).
 //
 // A workgroup of 4 waves holds a 64-row tile of activations in LDS (row stride LDX).  Wave w owns the 32-column blocks
 // w, w+4, ... of both 32-row blocks and accumulates them on v_mfma_f32_32x32x2_f32: A from LDS (ds_read_b128), B straight
@@ -122,20 +122,22 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 // acc[rb][j] += X[rb*32 + row][k] * W[(w + 4j)*32 + col][k] over k < K, bf16 products accumulated in fp32 (X in LDS with row
-// stride LDX elements, W [*, K] bf16 in global memory)
-template <int K, int LDX, int NJ, int NCB>
+// stride LDX elements, W [*, K] bf16 in global memory).  NRB row blocks of 32 (2: the 64-row tile; 4: a 128-row tile whose
+// weight pieces are loaded once for twice the rows); an element's sum is the same chain for every NRB.
+template <int K, int LDX, int NJ, int NCB, int NRB = 2>
 __device__ __forceinline__ void mfma_layer_bf16(const __bf16* __restrict__ X, const __bf16* __restrict__ W, int wave, int lane,
-                                                f32x16 (&acc)[2][NJ]) {
+                                                f32x16 (&acc)[NRB][NJ]) {
     static_assert(K % 16 == 0 && LDX % 8 == 0, "16-byte pieces");
     const int lr = lane & 31, lh = lane >> 5;
 #pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
+    for (int rb = 0; rb < NRB; ++rb)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[rb][j][r] = 0.f;
-    const __bf16* xa0 = X + (size_t)lr * LDX + 8 * lh;
-    const __bf16* xa1 = X + (size_t)(32 + lr) * LDX + 8 * lh;
+    const __bf16* xa[NRB];
+#pragma unroll
+    for (int rb = 0; rb < NRB; ++rb) xa[rb] = X + (size_t)(rb * 32 + lr) * LDX + 8 * lh;
     const __bf16* wb[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -154,13 +156,14 @@ __device__ __forceinline__ void mfma_layer_bf16(const __bf16* __restrict__ X, co
 #pragma unroll
             for (int j = 0; j < NJ; ++j) bn[j] = *reinterpret_cast<const bf16x8*>(wb[j] + 16 * (q + 1));
         }
-        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(xa0 + 16 * q);
-        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(xa1 + 16 * q);
+        bf16x8 a[NRB];
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) a[rb] = *reinterpret_cast<const bf16x8*>(xa[rb] + 16 * q);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             if (wave + 4 * j < NCB) {
-                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b[j], acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b[j], acc[1][j], 0, 0, 0);
+#pragma unroll
+                for (int rb = 0; rb < NRB; ++rb) acc[rb][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rb], b[j], acc[rb][j], 0, 0, 0);
             }
         }
     }

@@ -31,6 +31,24 @@
 // computed by the same instruction sequence in every variant, tiles are cut from the cloud's own first row and reduced in
 // ascending order: a cloud's output depends only on its own valid rows -- bit for bit the same for any B, any position in the
 // batch, any capacity N, any pad contents, any number of splits and any run.
+//
+// The bf16 kernel (pcl_pointnet_stack_infer_bf16_f32, pointnet_stack_infer_bf16_kernel) keeps that geometry -- one workgroup per
+// row tile of one cloud, tile-major, the early exit, per-tile partials in the never-cleared workspace, the same second launch, the
+// same splits, no atomics -- with layers 2-5 on v_mfma_f32_32x32x16_bf16 (infer::mfma_layer_bf16) and X1 / X2 as [rows][K + 8]
+// bf16 tiles.  Numerics contract (mirrors pcl_sa_level_infer_bf16_f32, infer.hip):
+//   - layer 1 is the fp32 fmaf expression above with its epilogue in fp32; z_1 is rounded to nearest even to bf16 ((__bf16));
+//   - layers 2-5 are bf16 x bf16 products accumulated in fp32, k-blocks of 16 in ascending order; every epilogue
+//     act(scale * y + shift) runs in fp32; z_2 .. z_4 are rounded to nearest even to bf16;
+//   - z_5 is never rounded; the max, the partials and out are fp32; W0, scale and shift stay fp32;
+//   - a cloud's output depends only on its own valid rows: the same bits for any B, position, capacity N, pad contents, split
+//     count, rows per workgroup and run.
+// Two things differ from the fp32 kernel's shape, both sized in DESIGN.md section 21:
+//   - the layer-5 epilogue runs on the tile's extreme raw accumulators, not on every element: for 0 <= slope <= 1 (checked on the
+//     host) u -> act(fl(fl(scale * u) + shift)) is monotone because fp32 rounding is, non-decreasing for scale >= 0 and
+//     non-increasing for scale < 0, so the max over rows of the epilogue IS the epilogue of the max (scale >= 0) or the min
+//     (scale < 0) of the accumulators, bit for bit.  Rows >= n_b are selected out of both (a pad row may hold anything);
+//   - a workgroup may take 128 rows (four 32-row blocks per weight piece: half the weight bytes per row from L2); it stores the
+//     same partial into both of its 64-row slots (max is idempotent), so the second launch and the workspace layout are shared.
 #include "common.h"
 #include "infer_mfma.h"
 
@@ -40,6 +58,8 @@ namespace {
 using infer::act;
 using infer::f32x16;
 using infer::mfma_layer;
+using infer::mfma_layer_bf16;
+using infer::bf16x4;
 
 constexpr int PN_T = 256;          // threads per workgroup (4 waves)
 constexpr int PN_RT = 64;          // rows per tile (two 32-row MFMA blocks)
@@ -151,6 +171,124 @@ __global__ __launch_bounds__(PN_T, 2) void pointnet_stack_infer_kernel(const PnA
     }
 }
 
+// ------------------------------------------------------------------------------------------------- the bf16 instantiation
+constexpr int PN16_LD1 = PN_C1 + 8, PN16_LD4 = PN_C4 + 8;   // X1 holds z_1 / z_3 (64 wide), X2 z_2 (64) then z_4 (128): [rows][K + 8] bf16
+constexpr size_t pn16_lds(int nrb) { return 2 * (size_t)32 * nrb * (PN16_LD1 + PN16_LD4); }   // 26 624 B (64 rows), 53 248 B (128)
+
+// layers 2-4: z = bf16(act(scale W_l x + shift)) from X (LDS, stride K + 8) into Y (LDS, stride LDY)
+template <int l, int K, int CO, int LDY, int NRB>
+__device__ __forceinline__ void pn16_layer(const PnArgs& a, const __bf16* X, __bf16* Y, int wave, int lane) {
+    constexpr int NCB = CO / 32, NJ = (NCB + 3) / 4;
+    const int lr = lane & 31, lh = lane >> 5;
+    f32x16 acc[NRB][NJ];
+    mfma_layer_bf16<K, K + 8, NJ, NCB, NRB>(X, reinterpret_cast<const __bf16*>(a.W[l]), wave, lane, acc);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int cb = wave + 4 * j;
+        if (cb < NCB) {
+            const int col = cb * 32 + lr;
+            const float sc = a.scl[l][col], sh = a.shf[l][col];
+#pragma unroll
+            for (int rb = 0; rb < NRB; ++rb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    Y[row * LDY + col] = (__bf16)act(sc * acc[rb][j][r] + sh, a.slope);
+                }
+        }
+    }
+}
+
+// NRB: 32-row blocks per workgroup (2 or 4)
+template <int NRB>
+__global__ __launch_bounds__(PN_T, 2) void pointnet_stack_infer_bf16_kernel(const PnArgs a) {
+    constexpr int RT = 32 * NRB;
+    constexpr int NJ5 = 4 / NRB, PASS5 = 4 * NJ5 * 32;   // layer 5: 64 accumulator registers either way, passes of 256 / 128 columns
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __bf16* X1 = reinterpret_cast<__bf16*>(smem);  // [RT][LD1]
+    __bf16* X2 = X1 + RT * PN16_LD1;               // [RT][LD4] (z_2 at stride LD1)
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+    const int t = blockIdx.x / a.B, b = blockIdx.x - t * a.B;     // tile-major
+    const int nb = a.n_valid ? min(max(a.n_valid[b], 1), a.N) : a.N;
+    const int row0 = t * RT;
+    if (row0 >= nb) return;                        // a tile of pad rows only (uniform exit, ahead of every barrier)
+    const int nrows = min(RT, nb - row0);
+
+    // 1. layer 1 in fp32, rounded into the bf16 tile
+    {
+        constexpr int TPR = PN_C1 / 4;
+        const int c4 = (tid % TPR) * 4;
+        float w[4][3], sc1[4], sh1[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) w[i][d] = a.W0[(size_t)(c4 + i) * a.ldw0 + d];
+            sc1[i] = a.scl[0][c4 + i]; sh1[i] = a.shf[0][c4 + i];
+        }
+        const float* xb = a.x + (size_t)b * a.sb;
+        for (int r = tid / TPR; r < RT; r += PN_T / TPR) {
+            const float* p = xb + (size_t)min(row0 + r, a.N - 1) * a.sn;
+            const float px = p[0], py = p[a.sc], pz = p[2 * a.sc];
+            bf16x4 zb;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float y = fmaf(w[i][2], pz, fmaf(w[i][1], py, w[i][0] * px));
+                zb[i] = (__bf16)act(sc1[i] * y + sh1[i], a.slope);
+            }
+            *reinterpret_cast<bf16x4*>(X1 + r * PN16_LD1 + c4) = zb;
+        }
+    }
+    __syncthreads();
+    // 2. layers 2-4
+    pn16_layer<1, PN_C1, PN_C2, PN16_LD1, NRB>(a, X1, X2, wave, lane);
+    __syncthreads();
+    pn16_layer<2, PN_C2, PN_C3, PN16_LD1, NRB>(a, X2, X1, wave, lane);
+    __syncthreads();
+    pn16_layer<3, PN_C3, PN_C4, PN16_LD4, NRB>(a, X1, X2, wave, lane);
+    __syncthreads();
+    // 3. layer 5 in passes; the workgroup's 64-row slots of the partials both take its maxima
+    float* part = a.part + ((size_t)b * a.tpc + t * (RT / PN_RT)) * PN_C5;
+    const bool second = RT > PN_RT && row0 + PN_RT < nb;
+    const bool full = nrows == RT;
+    const int c_begin = blockIdx.y * a.cols_per_split, c_end = c_begin + a.cols_per_split;
+    for (int c0 = c_begin; c0 < c_end; c0 += PASS5) {
+        f32x16 acc[NRB][NJ5];
+        mfma_layer_bf16<PN_C4, PN16_LD4, NJ5, 4 * NJ5, NRB>(X2, reinterpret_cast<const __bf16*>(a.W[4]) + (size_t)c0 * PN_C4, wave, lane,
+                                                                 acc);
+#pragma unroll
+        for (int j = 0; j < NJ5; ++j) {
+            const int col = c0 + (wave + 4 * j) * 32 + lr;
+            const float sc = a.scl[4][col], sh = a.shf[4][col];
+            float mx = -INFINITY, mn = INFINITY;   // the extreme accumulators of the tile's valid rows (header comment)
+            if (full) {
+#pragma unroll
+                for (int rb = 0; rb < NRB; ++rb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        mx = fmaxf(mx, acc[rb][j][r]);
+                        mn = fminf(mn, acc[rb][j][r]);
+                    }
+            } else {
+#pragma unroll
+                for (int rb = 0; rb < NRB; ++rb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const bool ok = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh < nrows;
+                        mx = fmaxf(mx, ok ? acc[rb][j][r] : -INFINITY);
+                        mn = fminf(mn, ok ? acc[rb][j][r] : INFINITY);
+                    }
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            mn = fminf(mn, __shfl_xor(mn, 32));
+            mx = act(sc * (sc >= 0.f ? mx : mn) + sh, a.slope);
+            if (lh == 0) {
+                part[col] = mx;
+                if (second) part[PN_C5 + col] = mx;
+            }
+        }
+    }
+}
+
 // out[b][c] = max over the cloud's live tiles, ascending
 __global__ __launch_bounds__(PN_T) void pointnet_tile_max_kernel(const float* __restrict__ part, const int32_t* __restrict__ n_valid,
                                                                  int N, int tpc, float* __restrict__ out, int ldo) {
@@ -162,6 +300,10 @@ __global__ __launch_bounds__(PN_T) void pointnet_tile_max_kernel(const float* __
     for (int t = 1; t < live; ++t) mx = fmaxf(mx, p[(size_t)t * PN_C5]);
     out[(size_t)b * ldo + c] = mx;
 }
+
+// Rows per workgroup of the bf16 kernel, a pure function of the sizes: 128 once there is a 128-row tile for each of the MI355X's
+// 256 CUs, else 64 (measured either side of it).  The result's bits do not depend on it.
+int pn16_rows(int B, int N) { return (long long)B * ((N + 127) / 128) >= 256 ? 128 : 64; }
 
 bool pn_shape_ok(int C0, int L, const int32_t* w) {
     return C0 == PN_C0 && L == 5 && w && w[0] == PN_C1 && w[1] == PN_C2 && w[2] == PN_C3 && w[3] == PN_C4 && w[4] == PN_C5;
@@ -185,11 +327,22 @@ extern "C" int pcl_pointnet_stack_infer_splits(int B, int N) {
     return tiles <= 128 ? 4 : tiles <= 256 ? 2 : 1;
 }
 
-extern "C" int pcl_pointnet_stack_infer_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid,
-                                            int B, int N, int C0, const float* W0, int ldw0, int L, const int32_t* widths,
-                                            const float* const* W, const float* const* scale, const float* const* shift, float slope,
-                                            void* workspace, size_t workspace_bytes, float* out, int ldo, void* stream) {
-    const char* who = "pcl_pointnet_stack_infer_f32";
+namespace {
+
+template <int NRB>
+int pn16_launch(const char* who, const PnArgs& a, int splits, hipStream_t st) {
+    auto kern = pointnet_stack_infer_bf16_kernel<NRB>;
+    const int tiles = (a.N + 32 * NRB - 1) / (32 * NRB);
+    if (int rc = lds_opt_in(kern, pn16_lds(NRB), who)) return rc;
+    hipLaunchKernelGGL(kern, dim3(a.B * tiles, splits), dim3(PN_T), pn16_lds(NRB), st, a);
+    return check_launch(who);
+}
+
+// both precisions: every check runs before any HIP call.  W[l], l >= 1: fp32 (BF16 false) or bf16 (true) [C_l][C_{l-1}]
+template <bool BF16>
+int pn_stack_infer(const char* who, const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid, int B, int N,
+                   int C0, const float* W0, int ldw0, int L, const int32_t* widths, const void* const* W, const float* const* scale,
+                   const float* const* shift, float slope, void* workspace, size_t workspace_bytes, float* out, int ldo, void* stream) {
     PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", who);
     PCL_REQUIRE(L >= 1 && L <= 5, "%s: L=%d", who, L);
     PCL_REQUIRE(pn_shape_ok(C0, L, widths), "%s: no kernel for C0=%d L=%d widths %d/%d/%d/%d/%d (pcl_pointnet_stack_infer_supported)", who,
@@ -200,6 +353,8 @@ extern "C" int pcl_pointnet_stack_infer_f32(const float* x, size_t stride_b, siz
     PCL_REQUIRE((size_t)B * tpc < (1u << 31) / PN_RT, "%s: too many points", who);
     PCL_REQUIRE(ldw0 >= PN_C0 && ldo >= PN_C5, "%s: ldw0=%d ldo=%d for %d -> %d channels", who, ldw0, ldo, PN_C0, PN_C5);
     for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", who, l);
+    // the bf16 kernel's last epilogue runs on the extreme accumulators: monotone only for these slopes (header comment)
+    if (BF16) PCL_REQUIRE(slope >= 0.f && slope <= 1.f, "%s: slope %g outside [0, 1]", who, (double)slope);
     const size_t need = pcl_pointnet_stack_infer_workspace_bytes(B, N, PN_C5);
     if (!workspace || workspace_bytes < need) return fail(PCL_EWS, "%s: workspace %zu < %zu", who, workspace_bytes, need);
     bool aligned = al16(workspace);
@@ -209,17 +364,39 @@ extern "C" int pcl_pointnet_stack_infer_f32(const float* x, size_t stride_b, siz
     a.x = x; a.sb = stride_b; a.sn = stride_n; a.sc = stride_c;
     a.n_valid = n_valid; a.B = B; a.N = N; a.tpc = tpc;
     a.W0 = W0; a.ldw0 = ldw0;
-    for (int l = 0; l < L; ++l) { a.W[l] = W[l]; a.scl[l] = scale[l]; a.shf[l] = shift[l]; }
+    for (int l = 0; l < L; ++l) { a.W[l] = static_cast<const float*>(W[l]); a.scl[l] = scale[l]; a.shf[l] = shift[l]; }
     a.slope = slope;
     a.part = static_cast<float*>(workspace);
     const int splits = pcl_pointnet_stack_infer_splits(B, N);
     a.cols_per_split = PN_C5 / splits;
     static_assert(PN_C5 / 4 % PN_PASS == 0, "a split is a whole number of passes");
     hipStream_t st = as_stream(stream);
-    if (int rc = lds_opt_in(pointnet_stack_infer_kernel, PN_LDS, who)) return rc;
-    hipLaunchKernelGGL(pointnet_stack_infer_kernel, dim3(B * tpc, splits), dim3(PN_T), PN_LDS, st, a);
-    if (int rc = check_launch(who)) return rc;
+    if constexpr (BF16) {
+        if (int rc = pn16_rows(B, N) == 128 ? pn16_launch<4>(who, a, splits, st) : pn16_launch<2>(who, a, splits, st)) return rc;
+    } else {
+        if (int rc = lds_opt_in(pointnet_stack_infer_kernel, PN_LDS, who)) return rc;
+        hipLaunchKernelGGL(pointnet_stack_infer_kernel, dim3(B * tpc, splits), dim3(PN_T), PN_LDS, st, a);
+        if (int rc = check_launch(who)) return rc;
+    }
     hipLaunchKernelGGL(pointnet_tile_max_kernel, dim3(B, PN_C5 / PN_T), dim3(PN_T), 0, st, static_cast<const float*>(workspace), n_valid, N,
                        tpc, out, ldo);
     return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int pcl_pointnet_stack_infer_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid,
+                                            int B, int N, int C0, const float* W0, int ldw0, int L, const int32_t* widths,
+                                            const float* const* W, const float* const* scale, const float* const* shift, float slope,
+                                            void* workspace, size_t workspace_bytes, float* out, int ldo, void* stream) {
+    return pn_stack_infer<false>("pcl_pointnet_stack_infer_f32", x, stride_b, stride_n, stride_c, n_valid, B, N, C0, W0, ldw0, L, widths,
+                                 reinterpret_cast<const void* const*>(W), scale, shift, slope, workspace, workspace_bytes, out, ldo, stream);
+}
+
+extern "C" int pcl_pointnet_stack_infer_bf16_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid,
+                                                 int B, int N, int C0, const float* W0, int ldw0, int L, const int32_t* widths,
+                                                 const void* const* W, const float* const* scale, const float* const* shift, float slope,
+                                                 void* workspace, size_t workspace_bytes, float* out, int ldo, void* stream) {
+    return pn_stack_infer<true>("pcl_pointnet_stack_infer_bf16_f32", x, stride_b, stride_n, stride_c, n_valid, B, N, C0, W0, ldw0, L, widths,
+                                W, scale, shift, slope, workspace, workspace_bytes, out, ldo, stream);
 }

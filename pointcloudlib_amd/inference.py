@@ -22,7 +22,10 @@ take bf16 operands (activations rounded to nearest even, weights snapshot as bf1
 
 ``FrozenPointNet(net)`` is the same for ``networks.cls.pointnet.PointNet``: the five convs and the max over the points run as
 ``pcl_pointnet_stack_infer_f32`` (csrc/infer_pointnet.hip: activations in LDS, nothing but per-tile maxima written), then the
-head.  It is constructed directly: ``frozen()`` keeps its PointNet++ dispatch.
+head.  It is constructed directly: ``frozen()`` keeps its PointNet++ dispatch.  ``FrozenPointNet(net, precision="bf16")`` runs the
+stack as ``pcl_pointnet_stack_infer_bf16_f32``: layers 2-5 take bf16 operands (activations rounded to nearest even, weights
+snapshot as bf16 in ``refresh()``) and accumulate in fp32; layer 1, the epilogues, the max, the global feature and the head stay
+fp32.
 
 ``FrozenPointNetPartseg(net)`` is the same for ``networks.seg.pointnet_partseg.PointNet_partseg`` (csrc/infer_pointnet_seg.hip,
 DESIGN.md section 20): ``conv5`` has no activation, so the head's 4944-wide first layer folds to 832 columns on a row buffer
@@ -453,13 +456,19 @@ class FrozenPointNet:
     gives ``"module"``: an eval-mode copy of ``net.convs`` runs, dense through ``group_max``, ragged through ``mlp_segment_max``.
     ``refresh()`` re-reads weights and running statistics; ``net`` itself is never modified.
 
+    ``precision``: "fp32", or "bf16" for bf16 matrix operands in layers 2-5 of the fused stack (module docstring;
+    ``fnet.precision`` tells which).  The head stays fp32, and a ``"module"`` plan ignores the precision and stays fp32.
+
     The class is constructed directly; ``frozen(net)`` still takes the PointNet++ networks only (its tests pin that), and taking
     PointNet there is a later change."""
 
-    def __init__(self, net):
+    def __init__(self, net, precision="fp32"):
         if not isinstance(net, PointNet):
             raise TypeError(f"FrozenPointNet takes networks.cls.pointnet.PointNet, got {type(net).__name__}")
+        if precision not in PRECISIONS:
+            raise ValueError(f"FrozenPointNet: precision must be one of {PRECISIONS}, got {precision!r}")
         self.net = net
+        self.precision = precision
         self._convs = self._head = None
         self.refresh()
 
@@ -491,6 +500,11 @@ class FrozenPointNet:
         self.c_W = (ctypes.c_void_p * L)(*[w.data_ptr() for w in self.Ws])
         self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
         self.c_shift = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.shifts])
+        self.entry = "pcl_pointnet_stack_infer_f32"
+        if self.precision == "bf16":                                   # the bf16 operands of layers 2-5, rounded once here
+            self.Ws_bf16 = [None] + [w.to(torch.bfloat16).contiguous() for w in self.Ws[1:]]
+            self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in self.Ws_bf16])
+            self.entry = "pcl_pointnet_stack_infer_bf16_f32"
         return self
 
     def __call__(self, x, lengths=None):
@@ -510,7 +524,7 @@ class FrozenPointNet:
         ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device)
         out = torch.empty((B, self.width), dtype=torch.float32, device=x.device)
         W0 = self.Ws[0]
-        _lib.call("pcl_pointnet_stack_infer_f32", _p(x), x.stride(0), x.stride(2), x.stride(1), _p(lengths), B, N, C0, _p(W0), W0.shape[1],
+        _lib.call(self.entry, _p(x), x.stride(0), x.stride(2), x.stride(1), _p(lengths), B, N, C0, _p(W0), W0.shape[1],
                   len(self.Ws), self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(ws), ws_bytes, _p(out), out.shape[1],
                   _stream())
         return out

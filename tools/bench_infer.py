@@ -17,6 +17,9 @@ writes the JSON line to profiles/infer_bf16_bench_line.json as well.
 ``--nets pointnet`` compares ``net.eval()`` under ``no_grad`` with ``FrozenPointNet(net)`` (B in {8, 32, 256}, N = 1024; both forms
 read the same dense [B,3,N] tensor) and writes the JSON line to profiles/infer_pointnet_bench_line.json; with ``--ragged`` the four
 forms below, the frozen form reading the [B,N,3] clouds through a transposed view (profiles/infer_pointnet_ragged_bench_line.json).
+With ``--precision fp32 bf16`` every row also carries ``FrozenPointNet(net, precision="bf16")`` (the ``frozen_bf16_*`` columns
+above, same windows) and, recorded only, the max-abs distance of the global feature and the logits from an fp64 restatement under
+both precisions (``*_err_fp64_*``); the line goes to profiles/infer_pointnet_bf16_bench_line.json instead.
 
 ``--nets pointnet_partseg`` compares ``net.eval()`` under ``no_grad`` with ``FrozenPointNetPartseg(net)`` (B in {16, 64}, N = 2048;
 both forms read the same dense [B,3,N] tensor and the same one-hot label) with the peak memory of both, and writes the JSON line
@@ -59,6 +62,32 @@ def _peak(fn):
     fn()
     torch.cuda.synchronize()
     return torch.cuda.max_memory_allocated() - base
+
+
+def _pointnet_fp64(net, x_cf, chunk=16):
+    """fp64 restatement of ``PointNet`` in evaluation mode: x_cf [B,3,N] -> (global feature [B,1024], logits)."""
+    mlp = net.convs
+    feats = []
+    for b0 in range(0, x_cf.shape[0], chunk):
+        z = x_cf[b0:b0 + chunk].transpose(1, 2).double()
+        for l in range(mlp.n_layers):
+            rm, rv = getattr(mlp, f"running_mean_{l}").double(), getattr(mlp, f"running_var_{l}").double()
+            scale = mlp.gammas[l].double() * torch.rsqrt(rv + mlp.eps)
+            y = z @ mlp.weights[l].double().t()
+            if mlp.biases is not None:
+                y = y + mlp.biases[l].double()
+            y = scale * (y - rm) + mlp.betas[l].double()
+            z = torch.where(y > 0, y, y * mlp.slope)
+        feats.append(z.max(dim=1)[0])
+    feat = torch.cat(feats)
+    def linear(m, t):
+        t = t @ m.weight.double().t()
+        return t if m.bias is None else t + m.bias.double()
+
+    bn = net.bn6
+    h = (linear(net.linear1, feat) - bn.running_mean.double()) * torch.rsqrt(bn.running_var.double() + bn.eps) * bn.weight.double() \
+        + bn.bias.double()
+    return feat, linear(net.linear2, h.clamp(min=0.0))
 
 
 def _ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16=None):
@@ -153,6 +182,11 @@ def main():
             def fnet(xyz, nrm, lengths=None):                 # the tool's call shape; [B,N,3] read through a transposed view
                 return fpn(xyz.transpose(1, 2), lengths)
             fnet_bf16 = None
+            if "bf16" in a.precision:
+                fpn16 = FrozenPointNet(net, precision="bf16")
+
+                def fnet_bf16(xyz, nrm, lengths=None):
+                    return fpn16(xyz.transpose(1, 2), lengths)
         elif pn_seg:
             fps = FrozenPointNetPartseg(net)
 
@@ -178,6 +212,9 @@ def main():
             def frozen_fwd():
                 return fnet(xyz, nrm, *extra)
 
+            def frozen_bf16_fwd():
+                return fnet_bf16(xyz, nrm, *extra)
+
             if kind == "pointnet":
                 x_cf = xyz.transpose(1, 2).contiguous()       # the network's input layout, made once: both forms read it
 
@@ -187,6 +224,9 @@ def main():
 
                 def frozen_fwd():
                     return fpn(x_cf)
+
+                def frozen_bf16_fwd():
+                    return fpn16(x_cf)
 
             if pn_seg:
                 x_cf = xyz.transpose(1, 2).contiguous()       # the network's input layout, made once: both forms read it
@@ -208,7 +248,7 @@ def main():
             else:
                 forms = [("eval", eval_fwd), ("frozen", frozen_fwd)]
             if fnet_bf16 is not None:
-                forms.append(("frozen_bf16", lambda: fnet_bf16(xyz, nrm, *extra)))
+                forms.append(("frozen_bf16", frozen_bf16_fwd))
             for _ in range(a.warmup):
                 for _, fn in forms:
                     fn()
@@ -234,16 +274,23 @@ def main():
             if fnet_bf16 is not None:
                 case["bf16_vs_fp32"] = round(case["frozen_bf16_ms"] / case["frozen_ms"], 4)
                 case["bf16_below_fp32_min"] = case["frozen_bf16_ms"] < case["frozen_ms_min"]
-                lf, lb = frozen_fwd(), fnet_bf16(xyz, nrm, *extra)
+                lf, lb = frozen_fwd(), frozen_bf16_fwd()
                 case["max_abs_logit_diff_bf16_fp32"] = float((lf - lb).abs().max())
                 case["top1_agreement_bf16_fp32"] = float((lf.argmax(1) == lb.argmax(1)).float().mean())
+                if kind == "pointnet" and not a.frozen_only:  # recorded, not asserted: distance from fp64 under both precisions
+                    f64, l64 = _pointnet_fp64(net, x_cf)
+                    for tag, form in (("fp32", fpn), ("bf16", fpn16)):
+                        feat, logits = form.run(x_cf)
+                        case[f"feature_err_fp64_{tag}"] = float((feat.double() - f64).abs().max())
+                        case[f"logit_err_fp64_{tag}"] = float((logits.double() - l64).abs().max())
+                    case["top1_agreement_bf16_fp64"] = float((lb.argmax(1) == l64.argmax(1)).float().mean())
             res["cases"].append(case)
     print(json.dumps(res))
-    if "bf16" in a.precision and not a.ragged:
+    if "bf16" in a.precision and not a.ragged and not (pointnet_only and a.frozen_only):
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-        with open(os.path.join(ROOT, "profiles", "infer_bf16_bench_line.json"), "w") as f:
+        with open(os.path.join(ROOT, "profiles", "infer_pointnet_bf16_bench_line.json" if pointnet_only else "infer_bf16_bench_line.json"), "w") as f:
             f.write(json.dumps(res) + "\n")
-    if pointnet_only and not a.frozen_only:
+    elif pointnet_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "infer_pointnet_ragged_bench_line.json" if a.ragged else "infer_pointnet_bench_line.json"), "w") as f:
             f.write(json.dumps(res) + "\n")
