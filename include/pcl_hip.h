@@ -394,7 +394,8 @@ int pcl_pointconv_contract_bn_stat_rows(int G);
 int pcl_pointconv_contract_bn_bwd_f32(const float* dout, const float* Y, const float* scale, const float* shift, float slope,
                                       const float* density, const float* weights, int G, int ns, int C, int M, float* du,
                                       float* dweights, float* ddensity, double* stats_ws, void* stream);
-/* reference: gradient of misc/pointconv_utils.py:393-394 */
+/* reference: gradient of misc/pointconv_utils.py:393-394.  Both backward forms move 16-byte pieces of dout, weights and (C % 4 == 0) feat / Y:
+ * those must be 16-byte aligned (PCL_EINVAL otherwise; the forward takes any 4-byte alignment). */
 int pcl_pointconv_contract_bwd_f32(const float* dout, const float* feat, const float* density, const float* weights, int G,
                                    int ns, int C, int M, float* dfeat, float* dweights, float* ddensity, void* stream);
 
@@ -807,6 +808,7 @@ int pcl_xconv_core_supported(int K, int dm, int C);
 int pcl_xconv_core_partials(int R, int C);
 int pcl_xconv_core_fwd_f32(const float* X, const float* F1, int C1, const float* F2, int C2, const float* wd, const float* bias,
                            int R, int K, int dm, float* D, void* stream);
+/* (dD must be 16-byte aligned when dm > 1: a channel's dm gradients are read as one piece; PCL_EINVAL otherwise) */
 int pcl_xconv_core_bwd_f32(const float* X, const float* F1, int C1, const float* F2, int C2, const float* wd, const float* dD,
                            int R, int K, int dm, float* dX, float* dF1, float* dF2, float* dwd_part, float* dbias_part,
                            void* stream);

@@ -1096,7 +1096,7 @@ extern "C" int pcl_group_linear_bwd_gather_f32(const float* row_loc, const float
                                                int C1, float* dUf, float* dWx_part, float* dW0, int ldw, void* stream) {
     PCL_REQUIRE(row_loc && dU && Y && a && k1 && k2 && mu && in_off && in_rows && dUf, "pcl_group_linear_bwd_gather_f32: null pointer");
     PCL_REQUIRE(B >= 1 && N >= 1 && pcl_group_linear_bwd_gather_supported(C1), "pcl_group_linear_bwd_gather_f32: bad sizes (C1 = %d: 64, 128 or 256)", C1);
-    PCL_REQUIRE(al16(dU, Y, dUf), "pcl_group_linear_bwd_gather_f32: 16-byte aligned rows");
+    PCL_REQUIRE(al16(dU, Y, dUf) && al16(a, k1, k2, mu), "pcl_group_linear_bwd_gather_f32: 16-byte aligned rows");
     PCL_REQUIRE(!dW0 || (dWx_part && ldw >= 3), "pcl_group_linear_bwd_gather_f32: dW0 needs dWx_part and ldw >= 3");
     hipStream_t st = as_stream(stream);
     const float4* rl = reinterpret_cast<const float4*>(row_loc);

@@ -32,6 +32,12 @@ __device__ __forceinline__ float drop_scale(const Drop d, unsigned idx) {
     return u >= d.p ? 1.0f / (1.0f - d.p) : 0.f;
 }
 
+// May the column kernels move 16-byte pieces of rows of K floats?  K % 4 == 0 and 16-byte aligned bases (then every row is): the same for
+// all lanes.  X or W may be a view at any 4-byte offset (a slice of a flat parameter buffer); those go by scalars.
+__device__ __forceinline__ bool head_vec_rows(int K, const float* a, const float* b) {
+    return (K & 3) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
+
 // One workgroup per output column n, its 4 waves split K in 256-wide chunks; X rows are read straight from global
 // memory (L2-resident, 16-byte pieces), so a lane has RMAX + 1 independent loads in flight per chunk and no barrier
 // until the four partial sums meet in LDS.
@@ -40,7 +46,7 @@ __device__ __forceinline__ void head_col_dot(const float* __restrict__ X, const 
                                              int lane, float (&acc)[RMAX]) {
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) acc[r] = 0.f;
-    const bool vec = (K & 3) == 0;
+    const bool vec = head_vec_rows(K, X, Wn);
     for (int k0 = wave * HD_KC; k0 < K; k0 += 4 * HD_KC) {
         const int k = k0 + 4 * lane;
         float w[4];
@@ -176,7 +182,7 @@ __device__ __forceinline__ float head_col_dy(int lane, int n, float dout, const 
 template <int RMAX>
 __device__ __forceinline__ void head_col_dw(const float* __restrict__ X, float dy, int R, int K, int n, int wave, int lane,
                                             float* __restrict__ dW) {
-    const bool vec = (K & 3) == 0;
+    const bool vec = head_vec_rows(K, X, X);
     for (int k0 = wave * HD_KC; k0 < K; k0 += 4 * HD_KC) {
         const int k = k0 + 4 * lane;
         float a[4] = {0.f, 0.f, 0.f, 0.f};

@@ -1745,7 +1745,11 @@ static bool fwd_res_eligible(const LinArgs& a) {
     if (!g_lab.fwd_resident || (a.a_mode != A_BNACT && a.a_mode != A_PLAIN) || a.e_mode != E_STORE_STATS || a.gmax || a.n_begin != 0 || a.ldc != a.N) return false;
     if (!((a.K == 64 && (a.N == 64 || a.N == 128)) || (a.K == 128 && (a.N == 128 || a.N == 256)))) return false;
     if (a.M < 32768 || (size_t)a.M * (size_t)(a.N > a.K ? a.N : a.K) * 4 >= 0xffffffffull) return false;
-    if (!al16(a.bias, a.A, a.B)) return false;
+    // The fp32 kernel (linear_fwd_res_kernel) reads X and W through 16-byte BUFFER loads, which the hardware serves at any 4-byte alignment
+    // (as the fragment kernels of frag.hip do), and the bias by scalars: a parameter that is a slice of a flat buffer keeps this kernel and
+    // its results.  The bf16-plane form (linear_fwd_split_kernel, opt-in) reads the bias in 16-byte pieces: it asks for aligned operands.
+    const bool split = (g_lab.split_mfma & 1) != 0 || ((g_lab.split_mfma & 4) && a.K == 128 && a.N == 256);      // (launch_fwd_res's choice)
+    if (split && !al16(a.bias, a.A, a.B)) return false;
     return a.a_mode == A_PLAIN || (al16(a.sc, a.sh) && a.slope >= 0.f && a.slope <= 1.f);
 }
 template <int CI, int NS>
@@ -3049,7 +3053,8 @@ static void linear_grid(int M, int N, bool bwd, bool rag, int& gx, int& n_tiles,
 template <int AM, int EM, int GM = 0, bool RAG = false>
 static int launch_linear_t(const LinArgs& a_in, hipStream_t st) {
     LinArgs a = a_in;
-    const bool vec = (a.K % 4 == 0) && al16(a.A, a.B, a.A2) &&
+    // (the vector staging also reads the per-channel constants in 16-byte pieces: in evaluation mode `mu` is the caller's running mean)
+    const bool vec = (a.K % 4 == 0) && al16(a.A, a.B, a.A2) && al16(a.sc, a.sh, a.k2, a.mu, a.gz) && al16(a.arg) &&
                      (AM < A_DY || a.ldb % 4 == 0);
     int gx, n_tiles; bool narrow, low;
     linear_grid(a.M, a.N - a.n_begin, AM >= A_DY, RAG, gx, n_tiles, narrow, low);
@@ -3306,7 +3311,8 @@ extern "C" int pcl_linear_bwd_dw_rows_f32(const float* dU, const float* Y, const
     d.part = static_cast<float*>(workspace); d.P = P; d.I = Cout; d.J = Cin;
     d.rmeta = reinterpret_cast<const int2*>(row_meta); d.p_dev = n_rows_dev;
     d.a_mode = dU ? A_DY : A_DY_SPARSE; d.b_mode = prev_scale ? A_BNACT : A_PLAIN;
-    const bool vec = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(Y, Xprev, dU) && (!gz || al16(gz, arg));
+    const bool vec = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(Y, Xprev, dU) && (!gz || al16(gz, arg)) &&
+                     al16(a_, k1, k2, mu, prev_scale, prev_shift);      // (the channel constants go in 16-byte pieces too; mu may be a running mean)
     d.gx = gx; d.ti = ti; d.tj = tj; d.ldo = Cin;
     // one row-chunk workgroup per output tile (few rows, a large weight: the per-point Linear of PointConv's GroupAll
     // level is 32 x 16384 -> 1024): nothing to reduce, the tiles go straight into dW instead of through the workspace
@@ -3364,8 +3370,9 @@ extern "C" int pcl_linear_bwd_pair_f32(const float* dU, const float* Y, const fl
     linear_grid(P, Cin - first_col, true, false, gxl, n_tiles, narrow, low);
     a.gx = gxl; a.nt = n_tiles;
     // the two bodies' vector paths have different preconditions; the pair runs both on the same path (scalar when either needs it)
-    const bool vec_dw = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(Y, Xprev, dU) && (!gz || al16(gz, arg));
-    const bool vec_nt = (a.K % 4 == 0) && al16(a.A, a.B, a.A2) && a.ldb % 4 == 0;
+    const bool vec_dw = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(Y, Xprev, dU) && (!gz || al16(gz, arg)) &&
+                        al16(a_, k1, k2, mu, prev_scale, prev_shift);
+    const bool vec_nt = (a.K % 4 == 0) && al16(a.A, a.B, a.A2) && al16(a.sc, a.sh, a.k2, a.mu, a.gz) && al16(a.arg) && a.ldb % 4 == 0;
     const int n_dw = gx * ti * tj;
     if (vec_dw != vec_nt) {
         // (an operand aligned for one body's vector path only: the two plain launches, each on its own path -- the finish launch still sums the tiles)
@@ -3491,7 +3498,7 @@ extern "C" int pcl_linear_bwd_dw_plain_f32(const float* dy, const float* Xprev, 
     d.A = dy; d.Bsrc = Xprev; d.bsc = prev_scale; d.bsh = prev_shift; d.bslope = prev_slope;
     d.part = static_cast<float*>(workspace); d.P = P; d.I = Cout; d.J = Cin;
     d.a_mode = A_PLAIN; d.b_mode = prev_scale ? A_BNACT : A_PLAIN;
-    const bool vec = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(dy, Xprev);
+    const bool vec = (Cout % 4 == 0) && (Cin % 4 == 0) && al16(dy, Xprev, prev_scale, prev_shift);
     d.gx = gx; d.ti = ti; d.tj = tj; d.ldo = Cin;
     const bool direct = gx == 1;
     if (direct) { d.part = dW; d.ldo = dw_ld ? dw_ld : Cin; }

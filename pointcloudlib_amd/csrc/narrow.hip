@@ -351,7 +351,9 @@ __global__ __launch_bounds__(NW_T) void nw_bwd_kernel(const NwArgs p) {
         nw_lin<C2, C3>(z1, y2, sm + S::oW2, sm + S::oB2);
         {
             const float* g = p.dz + (size_t)row * C3;
-            if constexpr (C3 % 4 == 0) {
+            // (dz is the caller's upstream gradient: 16-byte pieces only of 16-byte aligned rows -- C3 % 4 == 0 and an aligned base, the
+            //  same for every thread; a view at an odd storage offset goes by scalars)
+            if (C3 % 4 == 0 && (reinterpret_cast<uintptr_t>(p.dz) & 15) == 0) {
 #pragma unroll
                 for (int c = 0; c < C3; c += 4) {
                     const float4 t = *reinterpret_cast<const float4*>(g + c);

@@ -623,6 +623,8 @@ extern "C" int pcl_pointconv_contract_bn_bwd_f32(const float* dout, const float*
     PCL_REQUIRE(G >= 1 && ns >= 1 && C >= 1 && M == PC_M && slope >= 0.f && slope <= 1.f, "pcl_pointconv_contract_bn_bwd_f32: bad sizes G=%d ns=%d C=%d M=%d", G, ns, C, M);
     PCL_REQUIRE((size_t)ns * C * 4 < 0x7fffffffull && (size_t)C * PC_M * 4 < 0x7fffffffull, "pcl_pointconv_contract_bn_bwd_f32: a group of ns=%d x C=%d floats is beyond the kernels' 32-bit group offsets", ns, C);
     PCL_REQUIRE(C % 4 != 0 || al16(scale, shift), "pcl_pointconv_contract_bn_bwd_f32: scale / shift must be 16-byte aligned");
+    // (both kernels move 16-byte pieces of dout's and weights' 16-float rows, and of Y's rows where C % 4 == 0; density goes by scalars)
+    PCL_REQUIRE(al16(dout, weights) && (C % 4 != 0 || al16(Y)), "pcl_pointconv_contract_bn_bwd_f32: dout, weights and (C %% 4 == 0) Y must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     const FeatBN bn = {scale, shift, slope};
     const int rows = pcl_pointconv_contract_bn_stat_rows(G);
@@ -650,6 +652,8 @@ extern "C" int pcl_pointconv_contract_bwd_f32(const float* dout, const float* fe
                                               void* stream) {
     PCL_REQUIRE(dout && feat && density && weights && dfeat && dweights && ddensity, "pcl_pointconv_contract_bwd_f32: null pointer");
     PCL_REQUIRE(G >= 1 && ns >= 1 && C >= 1 && M == PC_M, "pcl_pointconv_contract_bwd_f32: bad sizes G=%d ns=%d C=%d M=%d", G, ns, C, M);
+    // (the kernels move 16-byte pieces of dout's and weights' 16-float rows, and of feat's rows where C % 4 == 0; density goes by scalars)
+    PCL_REQUIRE(al16(dout, weights) && (C % 4 != 0 || al16(feat)), "pcl_pointconv_contract_bwd_f32: dout, weights and (C %% 4 == 0) feat must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(pointconv_contract_bwd_feat_kernel, dim3(G, pc_chan_blocks(G, C)), dim3(pc_block(C)), 0, st, dout, density, weights, ns, C, dfeat);
     int rc = check_launch("pcl_pointconv_contract_bwd_f32(feat)");

@@ -723,7 +723,12 @@ static int stack_bwd_impl(const pcl_mlp_stack_t* dp) {
         const float* psc = l > 0 ? s.vec[l - 1] : nullptr;
         const float* psh = l > 0 ? s.vec[l - 1] + cin : nullptr;
         const float* Yl = s.Y[l];
-        if (l > 0 && fused_bwd_enabled() && pcl_linear_bwd_fused_supported(cout, cin)) {
+        // The fused kernel moves 16-byte pieces of every operand.  All of them are carved here at 256 bytes except the caller's weight:
+        // a layer whose W sits elsewhere (a slice of a flat parameter buffer) takes the two generic launches below, which stage it
+        // by scalars (mlp_hip.py decides the same way; no pair launch either, so that both paths run the same kernels).
+        const bool fb_sizes = l > 0 && fused_bwd_enabled() && pcl_linear_bwd_fused_supported(cout, cin);
+        const bool fb_declined = fb_sizes && !al16(ly.W);
+        if (fb_sizes && !fb_declined) {
             // one pass forms dy once and produces BOTH the layer below's du (+ its BatchNorm-backward sums) and dW; the second
             // launch sums the partial tiles and turns those sums into the constants of layer l - 1
             float* dUp = t.dU[cur_du];
@@ -741,7 +746,7 @@ static int stack_bwd_impl(const pcl_mlp_stack_t* dp) {
             rows = pcl_linear_bwd_fused_stat_rows(P, cin);
             continue;
         }
-        if (!sd && !fr && !rmeta && (l > 0 || d.need_dx) && pcl_linear_bwd_pair_supported(P, cout, cin, l == 0 ? d.x_grad_from : 0)) {
+        if (!fb_declined && !sd && !fr && !rmeta && (l > 0 || d.need_dx) && pcl_linear_bwd_pair_supported(P, cout, cin, l == 0 ? d.x_grad_from : 0)) {
             // few-row layer on plain rows (the GroupAll level, decoders): dW's partial tiles and dX from ONE launch; the second launch sums
             // the tiles and -- the layer below's sums being complete by then -- forms ITS constants as well (round 6: four launches per
             // layer were consts, dW, reduce, dX).  Same kernels' arithmetic: bit-identical to the per-kernel path.

@@ -322,6 +322,8 @@ extern "C" int pcl_xconv_core_bwd_f32(const float* X, const float* F1, int C1, c
                 "pcl_xconv_core_bwd_f32: null pointer");
     PCL_REQUIRE(R >= 1 && C1 >= 1 && C2 >= 0 && pcl_xconv_core_supported(K, DM, C1 + C2),
                 "pcl_xconv_core_bwd_f32: unsupported sizes R=%d K=%d dm=%d C=%d+%d", R, K, DM, C1, C2);
+    // (a channel's DM upstream gradients are read as one float2 / float4 pieces; every other operand goes by scalars)
+    PCL_REQUIRE(DM == 1 || al16(dD), "pcl_xconv_core_bwd_f32: dD must be 16-byte aligned when depth_multiplier > 1");
     XcArgs a = {};
     a.X = X; a.F1 = F1; a.C1 = C1; a.F2 = F2; a.C2 = C2; a.wd = wd; a.R = R; a.dD = dD; a.dX = dX; a.dF1 = dF1; a.dF2 = dF2;
     a.dwd_part = dwd_part; a.dbias_part = dbias_part;

@@ -141,7 +141,9 @@ class _FusedMLP(torch.autograd.Function):
                           _P(shift), _P(mean), _P(invstd), _P(rmean), _P(rvar), st)
             elif bn:
                 invstd = torch.rsqrt(rvar + eps)
-                mean = rmean
+                # (the backward kernels read the mean in 16-byte pieces next to their own constants: a running mean that is a slice
+                #  of a flat buffer at an odd offset is copied once, cout floats)
+                mean = rmean if rmean.data_ptr() % 16 == 0 else rmean.clone()
                 scale = gamma * invstd
                 shift = beta - scale * rmean
             else:
@@ -287,7 +289,10 @@ class _FusedMLP(torch.autograd.Function):
             Xprev = Ys[l - 1] if l > 0 else x
             psc = scales[l - 1] if l > 0 else None
             psh = shifts[l - 1] if l > 0 else None
-            if l > 0 and cin == fan_in and _FUSED_BWD and _lib.size_query("pcl_linear_bwd_fused_supported", cout, cin):
+            # (the fused kernel moves 16-byte pieces of every operand: a weight that is a slice of a flat parameter buffer at an odd
+            #  offset sends the layer down the two generic launches below -- csrc/stack.hip decides the same way)
+            if (l > 0 and cin == fan_in and _FUSED_BWD and _lib.size_query("pcl_linear_bwd_fused_supported", cout, cin)
+                    and W.data_ptr() % 16 == 0):
                 # one pass forms dy once and produces BOTH the previous layer's du (+ its BatchNorm-backward sums) and dW
                 nbytes = _lib.size_query("pcl_linear_bwd_fused_workspace_bytes", P, cout, cin)
                 ws = _empty(((nbytes + 3) // 4,), dev)

@@ -154,6 +154,8 @@ class _XConvCore(torch.autograd.Function):
         C1, C2 = F1.shape[-1], (F2.shape[-1] if F2 is not None else 0)
         C, dm = wd.shape[0], wd.shape[1]
         dD = dD.contiguous()
+        if dm > 1 and dD.data_ptr() % 16:
+            dD = dD.clone()          # the kernel reads a channel's dm gradients as one 8- or 16-byte piece: a view at an odd offset is staged
         dev = X.device
         dX, dF1 = torch.empty_like(X), torch.empty_like(F1)
         dF2 = torch.empty_like(F2) if F2 is not None else None

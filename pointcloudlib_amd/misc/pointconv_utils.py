@@ -68,6 +68,10 @@ def knn_point(nsample, xyz, new_xyz, form=None):
         xyz, new_xyz = _dev(xyz, "xyz"), _dev(new_xyz, "new_xyz")
         B, N, _ = xyz.shape
         S = new_xyz.shape[1]
+        if xyz.data_ptr() % 16 or N % 4:
+            # (the kernel loads a cloud's references as 16-byte pieces; the library's own definition, form="direct", takes any view)
+            raise RuntimeError(f"knn_point(form='matmul'): xyz must be 16-byte aligned and N a multiple of 4 "
+                               f"(data_ptr % 16 = {xyz.data_ptr() % 16}, N = {N})")
         out = torch.empty((B, S, nsample), dtype=torch.int32, device=xyz.device)
         _lib.call("pcl_knn_point_matmul_f32", _p(xyz), _p(new_xyz), B, N, S, int(nsample), 1, _p(out), _stream())
         return out
@@ -120,12 +124,18 @@ def sample_and_group_all(xyz, points, density_scale=None):
     return new_xyz, new_points, grouped_xyz, density_scale.view(B, 1, N, 1)
 
 
+def _al16(t):
+    """``t`` itself, or a copy in a fresh allocation when it is a view at an odd storage offset: the contraction's backward kernels
+    move 16-byte pieces of the upstream gradient, the weights and the features (csrc/pointconv.hip requires the alignment)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _PointConvContract(torch.autograd.Function):
     """out[B,S,C*16] = sum_s feat[B,S,ns,C] * density[B,S,ns,1] * weights[B,S,ns,16]   (:393-394)."""
 
     @staticmethod
     def forward(ctx, feat, density, weights):
-        feat, density, weights = _dev(feat, "feat"), _dev(density, "density"), _dev(weights, "weights")
+        feat, density, weights = _al16(_dev(feat, "feat")), _dev(density, "density"), _al16(_dev(weights, "weights"))
         B, S, ns, C = feat.shape
         M = weights.shape[-1]
         out = torch.empty((B, S, C * M), dtype=torch.float32, device=feat.device)
@@ -139,7 +149,7 @@ class _PointConvContract(torch.autograd.Function):
         feat, density, weights = ctx.saved_tensors
         B, S, ns, C = feat.shape
         M = weights.shape[-1]
-        gout = _dev(gout, "grad")
+        gout = _al16(_dev(gout, "grad"))
         dfeat, dw, dd = torch.empty_like(feat), torch.empty_like(weights), torch.empty_like(density)
         _lib.call("pcl_pointconv_contract_bwd_f32", _p(gout), _p(feat), _p(density), _p(weights), B * S, ns, C, M, _p(dfeat),
                   _p(dw), _p(dd), _stream())
@@ -156,7 +166,7 @@ class _PointConvContractBN(torch.autograd.Function):
     def forward(ctx, Y, link, density, weights):
         B, S, ns, C = Y.shape
         M = weights.shape[-1]
-        density, weights = _dev(density, "density"), _dev(weights, "weights")
+        density, weights = _dev(density, "density"), _al16(_dev(weights, "weights"))
         out = torch.empty((B, S, C * M), dtype=torch.float32, device=Y.device)
         _lib.call("pcl_pointconv_contract_bn_f32", _p(Y), _p(link.scale), _p(link.shift), float(link.slope), _p(density), _p(weights), B * S, ns, C,
                   M, _p(out), _stream(), algo_bytes=4 * B * S * (ns * (C + 1 + M) + C * M), algo_flops=2 * B * S * ns * C * M)
@@ -170,7 +180,7 @@ class _PointConvContractBN(torch.autograd.Function):
         link = ctx.link
         B, S, ns, C = Y.shape
         M = weights.shape[-1]
-        gout = _dev(gout, "grad")
+        gout = _al16(_dev(gout, "grad"))
         du, dw, dd = torch.empty_like(Y), torch.empty_like(weights), torch.empty_like(density)
         rows = _lib.size_query("pcl_pointconv_contract_bn_stat_rows", B * S)
         stats = torch.empty((rows, 2, C), dtype=torch.float64, device=Y.device)
