@@ -27,6 +27,10 @@
 //   - a group's result depends only on its own rows: not on B, on the group's place in the launch or on GT;
 //   - no atomics, run-to-run identical; rounding is the plain C++ conversion (v_cvt_pk_bf16_f32).
 // X1 / X2 are [64][C + 8] bf16 (infer_mfma.h), half the bytes of the fp32 tiles.
+//
+// The tile sizes, the MFMA steps, the accumulator-to-row map (infer::acc_row) and the 4-channel tile store come from
+// infer_mfma.h.  Layers 2 and 3 keep their epilogue loops here: layer 3's max per group is this kernel's alone, and layer 2
+// through infer::tile_layer compiled to 6 % more instructions and 4-6 more registers in this kernel's tile loop.
 #include <type_traits>
 
 #include "common.h"
@@ -35,15 +39,8 @@
 namespace pcl {
 namespace {
 
-using infer::act;
-using infer::f32x16;
-using infer::imax;
-using infer::mfma_layer;
-using infer::mfma_layer_bf16;
-using infer::bf16x4;
+using namespace infer;
 
-constexpr int IF_T = 256;        // threads per workgroup (4 waves)
-constexpr int IF_RT = 64;        // rows per tile (two 32-row MFMA blocks)
 constexpr int IF_MAXGT = 16;     // groups per workgroup at most
 constexpr size_t IF_LDS_CAP = 80 * 1024;     // two workgroups per CU
 
@@ -60,31 +57,30 @@ struct InferArgs {
 
 template <int C1, int C2, int C3, bool BF16>
 struct InferShape {
-    // +4 floats / +8 bf16 (one 16-byte piece): ds_read_b128 rows on distinct banks
-    static constexpr int LD1 = BF16 ? C1 + 8 : C1 + 4, LD2 = BF16 ? C2 + 8 : C2 + 4;
-    static constexpr int ESZ = BF16 ? 2 : 4;                               // bytes per element of X1 / X2
+    using XT = std::conditional_t<BF16, __bf16, float>;                    // element of X1 / X2
+    static constexpr int LD1 = C1 + row_pad<XT>, LD2 = C2 + row_pad<XT>;
     static size_t lds_bytes(int GT) {
-        return ESZ * ((size_t)IF_RT * LD1 + IF_RT * LD2) + 4 * (size_t)GT * C3 + 32 * IF_RT + 8 * IF_RT + 4 * (IF_MAXGT + 4);
+        return sizeof(XT) * ((size_t)RT * LD1 + RT * LD2) + 4 * (size_t)GT * C3 + 32 * RT + 8 * RT + 4 * (IF_MAXGT + 4);
     }
 };
 
 template <int C1, int C2, int C3, bool BF16>
-__global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs a) {
+__global__ __launch_bounds__(NT, 2) void sa_level_infer_kernel(const InferArgs a) {
     using S = InferShape<C1, C2, C3, BF16>;
-    using XT = std::conditional_t<BF16, __bf16, float>;                    // element of X1 / X2
+    using XT = typename S::XT;
     constexpr int LD1 = S::LD1, LD2 = S::LD2;
     constexpr int NCB2 = C2 / 32, NCB3 = C3 / 32;
     constexpr int NJ2 = (NCB2 + 3) / 4, NJ3 = (NCB3 + 3) / 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int GT = a.GT;
     XT* X1 = reinterpret_cast<XT*>(smem);                   // [RT][LD1]
-    XT* X2 = X1 + IF_RT * LD1;                              // [RT][LD2]
-    float* rmax = reinterpret_cast<float*>(X2 + IF_RT * LD2);             // [GT][C3]
+    XT* X2 = X1 + RT * LD1;                                 // [RT][LD2]
+    float* rmax = reinterpret_cast<float*>(X2 + RT * LD2);                // [GT][C3]
     float4* rloc = reinterpret_cast<float4*>(rmax + (size_t)GT * C3);     // [RT]
-    float4* rfeat = rloc + IF_RT;                           // [RT]
-    int* rsrc = reinterpret_cast<int*>(rfeat + IF_RT);      // [RT]
-    int* rgrp = rsrc + IF_RT;                               // [RT]
-    int* gstart = rgrp + IF_RT;                             // [GT + 1]
+    float4* rfeat = rloc + RT;                              // [RT]
+    int* rsrc = reinterpret_cast<int*>(rfeat + RT);         // [RT]
+    int* rgrp = rsrc + RT;                                  // [RT]
+    int* gstart = rgrp + RT;                                // [GT + 1]
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const int g0 = blockIdx.x * GT;
@@ -97,9 +93,9 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
         }
         gstart[ngt] = run;
     }
-    for (int e = tid; e < ngt * C3; e += IF_T) rmax[e] = -INFINITY;
-    // layer 1: a thread always works on the same four channels (IF_T is a multiple of C1 / 4): their constants in registers
-    static_assert(IF_T % (C1 / 4) == 0, "layer-1 channel split");
+    for (int e = tid; e < ngt * C3; e += NT) rmax[e] = -INFINITY;
+    // layer 1: a thread always works on the same four channels (NT is a multiple of C1 / 4): their constants in registers
+    static_assert(NT % (C1 / 4) == 0, "layer-1 channel split");
     const int c4 = (tid % (C1 / 4)) * 4, r_first = tid / (C1 / 4);
     float wx[4][3], wf[4][4], sc1[4], sh1[4];
 #pragma unroll
@@ -114,10 +110,10 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
     __syncthreads();
     const int R = gstart[ngt];
 
-    for (int t0 = 0; t0 < R; t0 += IF_RT) {
-        const int nvalid = min(IF_RT, R - t0);
+    for (int t0 = 0; t0 < R; t0 += RT) {
+        const int nvalid = min(RT, R - t0);
         // 1. row records
-        if (tid < IF_RT) {
+        if (tid < RT) {
             const int rr = t0 + min(tid, nvalid - 1);
             int gi = 0;
             while (gi + 1 < ngt && gstart[gi + 1] <= rr) ++gi;
@@ -139,7 +135,7 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
         }
         __syncthreads();
         // 2. layer 1 (the folded first conv), four channels per thread
-        for (int r = r_first; r < IF_RT; r += IF_T / (C1 / 4)) {
+        for (int r = r_first; r < RT; r += NT / (C1 / 4)) {
             const float4 L = rloc[r], F = rfeat[r];
             float u[4] = {0.f, 0.f, 0.f, 0.f};
             if (a.Uf) {
@@ -153,14 +149,7 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
                 y = fmaf(wf[i][3], F.w, fmaf(wf[i][2], F.z, fmaf(wf[i][1], F.y, fmaf(wf[i][0], F.x, y))));
                 z[i] = act(sc1[i] * y + sh1[i], a.slope);
             }
-            if constexpr (BF16) {
-                bf16x4 zb;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) zb[i] = (__bf16)z[i];
-                *reinterpret_cast<bf16x4*>(X1 + (size_t)r * LD1 + c4) = zb;
-            } else {
-                *reinterpret_cast<float4*>(X1 + (size_t)r * LD1 + c4) = make_float4(z[0], z[1], z[2], z[3]);
-            }
+            tile_store4(X1 + (size_t)r * LD1 + c4, z);
         }
         __syncthreads();
         // 3. layer 2
@@ -178,7 +167,7 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
                     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                            const int row = acc_row(rb, r, lh);
                             X2[(size_t)row * LD2 + col] = (XT)act(sc * acc[rb][j][r] + sh, a.slope);
                         }
                 }
@@ -210,7 +199,7 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
                         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
-                                const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                                const int row = acc_row(rb, r, lh);
                                 if (row >= lo && row < hi) mx = fmaxf(mx, acc[rb][j][r]);
                             }
                         mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -221,7 +210,7 @@ __global__ __launch_bounds__(IF_T, 2) void sa_level_infer_kernel(const InferArgs
         }
         __syncthreads();
     }
-    for (int e = tid; e < ngt * C3; e += IF_T) {
+    for (int e = tid; e < ngt * C3; e += NT) {
         const int gi = e / C3, c = e - gi * C3;
         a.out[(size_t)(g0 + gi) * a.ldo + a.col0 + c] = rmax[e];
     }
@@ -237,7 +226,7 @@ int launch_infer(const char* fn, InferArgs a, hipStream_t st) {
     auto kern = sa_level_infer_kernel<C1, C2, C3, BF16>;
     if (int rc = lds_opt_in(kern, lds, fn)) return rc;
     const int blocks = (a.G + GT - 1) / GT;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(IF_T), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NT), lds, st, a);
     return check_launch(fn);
 }
 

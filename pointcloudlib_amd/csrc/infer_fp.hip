@@ -14,6 +14,8 @@
 //   3. the last layer's tile goes straight from the accumulators to out[rows, ldo] (its first `ncols` columns; the last
 //      layer may be padded to a 32-multiple with zero weights).  Optionally one intermediate layer is also stored (tap).
 // Nothing but the final tile (and the tap) is written to memory; no atomics, so two calls give identical bits.
+// The tile sizes, the MFMA step and the accumulator-to-row map (infer::acc_row) come from infer_mfma.h; fp_layer keeps its own
+// epilogue loop (a run-time activation flag, the tap and the ragged zeroing are this kernel's alone).
 //
 // RAGGED (pcl_fp_level_infer_ragged_f32): cloud b's target rows are its first n = clamp(n_valid[b], 1, N); every wave forms the tile's
 // 64-bit row-validity mask with one ballot.  A tile without a valid row stores its zeros and leaves before any layer work; in a mixed
@@ -25,13 +27,8 @@
 namespace pcl {
 namespace {
 
-using infer::act;
-using infer::f32x16;
-using infer::imax;
-using infer::mfma_layer;
+using namespace infer;
 
-constexpr int FP_T = 256;        // threads per workgroup (4 waves)
-constexpr int FP_RT = 64;        // rows per tile (two 32-row MFMA blocks)
 constexpr int FP_MAXL = 5;
 constexpr int FP_MAXCS = 8;      // inline skip channels at most (FP1: xyz + normal)
 
@@ -49,9 +46,9 @@ struct FpArgs {
 
 template <int L, int C1, int C2, int C3, int C4, int C5>
 struct FpShape {
-    static constexpr int LDA = imax(C1, C3) + 4;                       // X1: layers 1, 3; +4 floats: ds_read_b128 rows on distinct banks
-    static constexpr int LDB = imax(C2, C4) + 4;                       // X2: layers 2, 4 (L >= 3)
-    static constexpr size_t lds_bytes = 4 * (size_t)FP_RT * (LDA + (L >= 3 ? LDB : 0));
+    static constexpr int LDA = imax(C1, C3) + row_pad<float>;            // X1: layers 1, 3
+    static constexpr int LDB = imax(C2, C4) + row_pad<float>;            // X2: layers 2, 4 (L >= 3)
+    static constexpr size_t lds_bytes = 4 * (size_t)RT * (LDA + (L >= 3 ? LDB : 0));
 };
 
 // layer l >= 1 (0-based): z = act?(scale W_l x + shift) from X (LDS) into Y (LDS), or -- LAST -- into out
@@ -74,7 +71,7 @@ __device__ __forceinline__ void fp_layer(const FpArgs& a, const float* X, float*
             for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int row = acc_row(rb, r, lh);
                     float z = sc * acc[rb][j][r] + sh;
                     if (do_act) z = act(z, a.slope);
                     float zs = z;                                          // what is stored: exact zeros on a cloud's pad rows
@@ -91,29 +88,29 @@ __device__ __forceinline__ void fp_layer(const FpArgs& a, const float* X, float*
 }
 
 template <int L, int C1, int C2, int C3, int C4, int C5, bool RAGGED>
-__global__ __launch_bounds__(FP_T, 2) void fp_level_infer_kernel(const FpArgs a) {
+__global__ __launch_bounds__(NT, 2) void fp_level_infer_kernel(const FpArgs a) {
     using S = FpShape<L, C1, C2, C3, C4, C5>;
     constexpr int LDA = S::LDA, LDB = S::LDB;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* X1 = smem;                                        // [RT][LDA]
-    float* X2 = X1 + FP_RT * LDA;                            // [RT][LDB] (L >= 3)
+    float* X2 = X1 + RT * LDA;                               // [RT][LDB] (L >= 3)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int row0 = blockIdx.x * FP_RT;
-    const int nvalid = min(FP_RT, a.R - row0);
+    const int row0 = blockIdx.x * RT;
+    const int nvalid = min(RT, a.R - row0);
     unsigned long long vmask = ~0ull;                        // bit r: tile row r is a point of its cloud (ragged)
     if constexpr (RAGGED) {
         const int gr = row0 + min(lane, nvalid - 1), b = gr / a.N;
         vmask = __ballot(lane < nvalid && gr - b * a.N < min(max(a.n_valid[b], 1), a.N));      // the same in every wave
         if (vmask == 0) {                                    // pad rows only: zeros, no layer work (uniform exit, ahead of every barrier)
-            for (int i = tid; i < nvalid * a.ncols; i += FP_T) a.out[(size_t)(row0 + i / a.ncols) * a.ldo + i % a.ncols] = 0.f;
+            for (int i = tid; i < nvalid * a.ncols; i += NT) a.out[(size_t)(row0 + i / a.ncols) * a.ldo + i % a.ncols] = 0.f;
             if (a.tap_layer >= 0)
-                for (int i = tid; i < nvalid * a.tapw; i += FP_T) a.tap[(size_t)(row0 + i / a.tapw) * a.ldt + i % a.tapw] = 0.f;
+                for (int i = tid; i < nvalid * a.tapw; i += NT) a.tap[(size_t)(row0 + i / a.tapw) * a.ldt + i % a.tapw] = 0.f;
             return;
         }
     }
 
-    // 1. layer 1 (the folded first conv): a thread always works on the same four channels (FP_T is a multiple of C1 / 4)
-    static_assert(FP_T % (C1 / 4) == 0, "layer-1 channel split");
+    // 1. layer 1 (the folded first conv): a thread always works on the same four channels (NT is a multiple of C1 / 4)
+    static_assert(NT % (C1 / 4) == 0, "layer-1 channel split");
     {
         const int c4 = (tid % (C1 / 4)) * 4;
         float wf[4][FP_MAXCS], sc1[4], sh1[4];
@@ -124,7 +121,7 @@ __global__ __launch_bounds__(FP_T, 2) void fp_level_infer_kernel(const FpArgs a)
             sc1[i] = a.sc[0][c4 + i]; sh1[i] = a.sh[0][c4 + i];
         }
         const bool act1 = a.act_mask & 1;
-        for (int r = tid / (C1 / 4); r < FP_RT; r += FP_T / (C1 / 4)) {
+        for (int r = tid / (C1 / 4); r < RT; r += NT / (C1 / 4)) {
             const int gr = row0 + min(r, nvalid - 1);            // the tile's tail repeats its last row (never stored)
             const int b = gr / a.N;
             float y[4] = {0.f, 0.f, 0.f, 0.f};
@@ -192,8 +189,8 @@ int launch_fp(const char* who, const FpArgs& a, hipStream_t st) {
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
     auto kern = fp_level_infer_kernel<L, C1, C2, C3, C4, C5, RAGGED>;
     if (int rc = lds_opt_in(kern, lds, who)) return rc;
-    const int blocks = (a.R + FP_RT - 1) / FP_RT;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(FP_T), lds, st, a);
+    const int blocks = (a.R + RT - 1) / RT;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NT), lds, st, a);
     return check_launch(who);
 }
 

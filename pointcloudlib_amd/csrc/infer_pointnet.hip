@@ -8,20 +8,20 @@
 // A workgroup (4 waves) owns one 64-row tile of ONE cloud (tiles never span clouds) and, with `splits` column splits of the last
 // layer over grid.y, 1024 / splits of its columns:
 //   1. layer 1 (K = 3) elementwise from the three coordinates, read at the caller's strides ([B,3,N] or [B,N,3] as it is),
-//      four channels per thread -> X1 (LDS);
-//   2. layers 2-4 on the fp32 MFMA (infer_mfma.h), ping-ponging between X1 and X2, two [64][132] fp32 tiles in LDS;
-//   3. layer 5 (128 -> 1024, 89 % of the FLOPs) in passes of 256 columns (NJ = 2: 64 accumulator registers, no scratch):
+//      four channels per thread -> X1 (LDS) (infer::points_layer);
+//   2. layers 2-4 on the fp32 MFMA (infer::tile_layer), ping-ponging between X1 and X2, two [64][132] fp32 tiles in LDS;
+//   3. layer 5 (128 -> 1024, 89 % of the FLOPs) in passes of 256 columns (infer::max_passes; 64 accumulator registers, no scratch):
 //      scale / shift / act in the epilogue, rows >= n_b selected to -inf, the max over the lane's 32 rows in registers, then
 //      across the two lane halves; z_5 reaches neither LDS nor memory.  Lane half 0 stores the tile's partial maxima
 //      part[tile][col] (the caller's workspace).
 // A tile whose first row is >= n_b leaves before any load; its partials are never read, so the workspace is never cleared.
-// Workgroups are numbered tile-major (blockIdx.x = t * B + b): the tiles that ragged clouds leave empty are the high t of every
-// cloud, and dispatched last they cost next to nothing; numbered cloud by cloud, interleaved with live tiles, each empty
-// workgroup was measured to cost nearly what a live one does.  A
+// Workgroups are numbered tile-major (blockIdx.x = t * B + b, infer::cloud_tile): the tiles that ragged clouds leave empty are
+// the high t of every cloud, and dispatched last they cost next to nothing; numbered cloud by cloud, interleaved with live
+// tiles, each empty workgroup was measured to cost nearly what a live one does.  A
 // partial tile computes all 64 rows: rows of a GEMM are independent, so whatever a pad row holds (NaN included) stays in that row.
 // Rows beyond the capacity N repeat row N - 1 (never read out of bounds) and are masked like every row >= n_b.
-// A second small launch takes, per cloud and column, the max over the cloud's ceil(n_b / 64) live tiles in ascending order.  No
-// atomics and no inter-workgroup hand-off inside a launch.
+// A second small launch (infer::tile_max_kernel) takes, per cloud and column, the max over the cloud's ceil(n_b / 64) live tiles
+// in ascending order.  No atomics and no inter-workgroup hand-off inside a launch.
 //
 // With a split, layers 1-4 (11 % of the FLOPs) are recomputed per split.  splits = pcl_pointnet_stack_infer_splits(B, N), a pure
 // function of the sizes: few tiles (B = 8, N = 1024: 128 for 256 CUs) take 4 or 2 splits to fill the machine.
@@ -55,19 +55,10 @@
 namespace pcl {
 namespace {
 
-using infer::act;
-using infer::f32x16;
-using infer::mfma_layer;
-using infer::mfma_layer_bf16;
-using infer::bf16x4;
+using namespace infer;
 
-constexpr int PN_T = 256;          // threads per workgroup (4 waves)
-constexpr int PN_RT = 64;          // rows per tile (two 32-row MFMA blocks)
-constexpr int PN_LD = 132;         // row stride of X1 / X2: 128 + 4 floats, ds_read_b128 rows on distinct banks
 constexpr int PN_C0 = 3, PN_C1 = 64, PN_C2 = 64, PN_C3 = 64, PN_C4 = 128, PN_C5 = 1024;
-constexpr int PN_NJ = 2;           // layer 5: column blocks per wave and pass
-constexpr int PN_PASS = 4 * PN_NJ * 32;                                  // columns per pass (256)
-constexpr size_t PN_LDS = 4 * (size_t)2 * PN_RT * PN_LD;                 // 67 584 B: two workgroups per CU
+constexpr size_t PN_LDS = 4 * (size_t)2 * RT * LD128;                    // X1 and X2, 67 584 B: two workgroups per CU
 
 struct PnArgs {
     const float* x; size_t sb, sn, sc;
@@ -79,177 +70,61 @@ struct PnArgs {
     int cols_per_split;
 };
 
-// layers 2-4: z = act(scale W_l x + shift) from X (LDS) into Y (LDS)
-template <int l, int K, int CO>
-__device__ __forceinline__ void pn_layer(const PnArgs& a, const float* X, float* Y, int wave, int lane) {
-    constexpr int NCB = CO / 32, NJ = (NCB + 3) / 4;
-    const int lr = lane & 31, lh = lane >> 5;
-    f32x16 acc[2][NJ];
-    mfma_layer<K, PN_LD, NJ, NCB>(X, a.W[l], wave, lane, acc);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int cb = wave + 4 * j;
-        if (cb < NCB) {
-            const int col = cb * 32 + lr;
-            const float sc = a.scl[l][col], sh = a.shf[l][col];
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    Y[row * PN_LD + col] = act(sc * acc[rb][j][r] + sh, a.slope);
-                }
-        }
-    }
-}
-
-__global__ __launch_bounds__(PN_T, 2) void pointnet_stack_infer_kernel(const PnArgs a) {
+__global__ __launch_bounds__(NT, 2) void pointnet_stack_infer_kernel(const PnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* X1 = smem;                              // [RT][LD]
-    float* X2 = X1 + PN_RT * PN_LD;                // [RT][LD]
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
-    const int t = blockIdx.x / a.B, b = blockIdx.x - t * a.B;     // tile-major: see the header comment
-    const int nb = a.n_valid ? min(max(a.n_valid[b], 1), a.N) : a.N;
-    const int row0 = t * PN_RT;
-    if (row0 >= nb) return;                        // a tile of pad rows only (uniform exit, ahead of every barrier)
-    const int nrows = min(PN_RT, nb - row0);       // the tile's rows that are points of the cloud
-
+    float* X1 = smem;                              // [RT][LD128]
+    float* X2 = X1 + RT * LD128;                   // [RT][LD128]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
+    if (tile.empty()) return;
     // 1. layer 1: a thread always works on the same four channels
-    {
-        constexpr int TPR = PN_C1 / 4;             // threads per row
-        const int c4 = (tid % TPR) * 4;
-        float w[4][3], sc1[4], sh1[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) w[i][d] = a.W0[(size_t)(c4 + i) * a.ldw0 + d];
-            sc1[i] = a.scl[0][c4 + i]; sh1[i] = a.shf[0][c4 + i];
-        }
-        const float* xb = a.x + (size_t)b * a.sb;
-        for (int r = tid / TPR; r < PN_RT; r += PN_T / TPR) {
-            const float* p = xb + (size_t)min(row0 + r, a.N - 1) * a.sn;
-            const float px = p[0], py = p[a.sc], pz = p[2 * a.sc];
-            float z[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float y = fmaf(w[i][2], pz, fmaf(w[i][1], py, w[i][0] * px));
-                z[i] = act(sc1[i] * y + sh1[i], a.slope);
-            }
-            *reinterpret_cast<float4*>(X1 + r * PN_LD + c4) = make_float4(z[0], z[1], z[2], z[3]);
-        }
-    }
+    points_layer<float, RT, LD128, false, false>(a.x + (size_t)tile.b * a.sb, a.sn, a.sc, a.N, tile.row0, nullptr, a.W0, a.ldw0, a.scl[0],
+                                                 a.shf[0], a.slope, X1, nullptr, 0, tile.nrows, tid);
     __syncthreads();
     // 2. layers 2-4
-    pn_layer<1, PN_C1, PN_C2>(a, X1, X2, wave, lane);
+    tile_layer<PN_C1, LD128, PN_C2, LD128>(X1, a.W[1], a.scl[1], a.shf[1], a.slope, X2, wave, lane);
     __syncthreads();
-    pn_layer<2, PN_C2, PN_C3>(a, X2, X1, wave, lane);
+    tile_layer<PN_C2, LD128, PN_C3, LD128>(X2, a.W[2], a.scl[2], a.shf[2], a.slope, X1, wave, lane);
     __syncthreads();
-    pn_layer<3, PN_C3, PN_C4>(a, X1, X2, wave, lane);
+    tile_layer<PN_C3, LD128, PN_C4, LD128>(X1, a.W[3], a.scl[3], a.shf[3], a.slope, X2, wave, lane);
     __syncthreads();
-    // 3. layer 5 in passes of 256 columns; the max over the tile's rows in registers
-    float* part = a.part + ((size_t)b * a.tpc + t) * PN_C5;
-    const int c_begin = blockIdx.y * a.cols_per_split, c_end = c_begin + a.cols_per_split;
-    for (int c0 = c_begin; c0 < c_end; c0 += PN_PASS) {
-        f32x16 acc[2][PN_NJ];
-        mfma_layer<PN_C4, PN_LD, PN_NJ, 4 * PN_NJ>(X2, a.W[4] + (size_t)c0 * PN_C4, wave, lane, acc);
-#pragma unroll
-        for (int j = 0; j < PN_NJ; ++j) {
-            const int col = c0 + (wave + 4 * j) * 32 + lr;
-            const float sc = a.scl[4][col], sh = a.shf[4][col];
-            float mx = -INFINITY;
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const float z = act(sc * acc[rb][j][r] + sh, a.slope);
-                    mx = fmaxf(mx, row < nrows ? z : -INFINITY);
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            if (lh == 0) part[col] = mx;
-        }
-    }
+    // 3. layer 5 over this split's columns; the max over the tile's rows in registers
+    float* part = a.part + ((size_t)tile.b * a.tpc + tile.t) * PN_C5;
+    const int c_begin = blockIdx.y * a.cols_per_split;
+    max_passes<PN_C4, LD128, true>(X2, a.W[4], a.scl[4], a.shf[4], a.slope, tile.nrows, part, c_begin, c_begin + a.cols_per_split, wave, lane);
 }
 
 // ------------------------------------------------------------------------------------------------- the bf16 instantiation
-constexpr int PN16_LD1 = PN_C1 + 8, PN16_LD4 = PN_C4 + 8;   // X1 holds z_1 / z_3 (64 wide), X2 z_2 (64) then z_4 (128): [rows][K + 8] bf16
+// X1 holds z_1 / z_3 (64 wide), X2 z_2 (64) then z_4 (128): [rows][K + 8] bf16
+constexpr int PN16_LD1 = PN_C1 + row_pad<__bf16>, PN16_LD4 = PN_C4 + row_pad<__bf16>;
 constexpr size_t pn16_lds(int nrb) { return 2 * (size_t)32 * nrb * (PN16_LD1 + PN16_LD4); }   // 26 624 B (64 rows), 53 248 B (128)
-
-// layers 2-4: z = bf16(act(scale W_l x + shift)) from X (LDS, stride K + 8) into Y (LDS, stride LDY)
-template <int l, int K, int CO, int LDY, int NRB>
-__device__ __forceinline__ void pn16_layer(const PnArgs& a, const __bf16* X, __bf16* Y, int wave, int lane) {
-    constexpr int NCB = CO / 32, NJ = (NCB + 3) / 4;
-    const int lr = lane & 31, lh = lane >> 5;
-    f32x16 acc[NRB][NJ];
-    mfma_layer_bf16<K, K + 8, NJ, NCB, NRB>(X, reinterpret_cast<const __bf16*>(a.W[l]), wave, lane, acc);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int cb = wave + 4 * j;
-        if (cb < NCB) {
-            const int col = cb * 32 + lr;
-            const float sc = a.scl[l][col], sh = a.shf[l][col];
-#pragma unroll
-            for (int rb = 0; rb < NRB; ++rb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    Y[row * LDY + col] = (__bf16)act(sc * acc[rb][j][r] + sh, a.slope);
-                }
-        }
-    }
-}
 
 // NRB: 32-row blocks per workgroup (2 or 4)
 template <int NRB>
-__global__ __launch_bounds__(PN_T, 2) void pointnet_stack_infer_bf16_kernel(const PnArgs a) {
-    constexpr int RT = 32 * NRB;
+__global__ __launch_bounds__(NT, 2) void pointnet_stack_infer_bf16_kernel(const PnArgs a) {
+    constexpr int ROWS = 32 * NRB;
     constexpr int NJ5 = 4 / NRB, PASS5 = 4 * NJ5 * 32;   // layer 5: 64 accumulator registers either way, passes of 256 / 128 columns
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    __bf16* X1 = reinterpret_cast<__bf16*>(smem);  // [RT][LD1]
-    __bf16* X2 = X1 + RT * PN16_LD1;               // [RT][LD4] (z_2 at stride LD1)
+    __bf16* X1 = reinterpret_cast<__bf16*>(smem);  // [ROWS][LD1]
+    __bf16* X2 = X1 + ROWS * PN16_LD1;             // [ROWS][LD4] (z_2 at stride LD1)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
-    const int t = blockIdx.x / a.B, b = blockIdx.x - t * a.B;     // tile-major
-    const int nb = a.n_valid ? min(max(a.n_valid[b], 1), a.N) : a.N;
-    const int row0 = t * RT;
-    if (row0 >= nb) return;                        // a tile of pad rows only (uniform exit, ahead of every barrier)
-    const int nrows = min(RT, nb - row0);
-
+    const CloudTile tile = cloud_tile<ROWS>(a.B, a.N, a.n_valid);
+    if (tile.empty()) return;
     // 1. layer 1 in fp32, rounded into the bf16 tile
-    {
-        constexpr int TPR = PN_C1 / 4;
-        const int c4 = (tid % TPR) * 4;
-        float w[4][3], sc1[4], sh1[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) w[i][d] = a.W0[(size_t)(c4 + i) * a.ldw0 + d];
-            sc1[i] = a.scl[0][c4 + i]; sh1[i] = a.shf[0][c4 + i];
-        }
-        const float* xb = a.x + (size_t)b * a.sb;
-        for (int r = tid / TPR; r < RT; r += PN_T / TPR) {
-            const float* p = xb + (size_t)min(row0 + r, a.N - 1) * a.sn;
-            const float px = p[0], py = p[a.sc], pz = p[2 * a.sc];
-            bf16x4 zb;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float y = fmaf(w[i][2], pz, fmaf(w[i][1], py, w[i][0] * px));
-                zb[i] = (__bf16)act(sc1[i] * y + sh1[i], a.slope);
-            }
-            *reinterpret_cast<bf16x4*>(X1 + r * PN16_LD1 + c4) = zb;
-        }
-    }
+    points_layer<__bf16, ROWS, PN16_LD1, false, false>(a.x + (size_t)tile.b * a.sb, a.sn, a.sc, a.N, tile.row0, nullptr, a.W0, a.ldw0, a.scl[0],
+                                                       a.shf[0], a.slope, X1, nullptr, 0, tile.nrows, tid);
     __syncthreads();
     // 2. layers 2-4
-    pn16_layer<1, PN_C1, PN_C2, PN16_LD1, NRB>(a, X1, X2, wave, lane);
+    tile_layer<PN_C1, PN16_LD1, PN_C2, PN16_LD1, NRB>(X1, a.W[1], a.scl[1], a.shf[1], a.slope, X2, wave, lane);
     __syncthreads();
-    pn16_layer<2, PN_C2, PN_C3, PN16_LD1, NRB>(a, X2, X1, wave, lane);
+    tile_layer<PN_C2, PN16_LD1, PN_C3, PN16_LD1, NRB>(X2, a.W[2], a.scl[2], a.shf[2], a.slope, X1, wave, lane);
     __syncthreads();
-    pn16_layer<3, PN_C3, PN_C4, PN16_LD4, NRB>(a, X1, X2, wave, lane);
+    tile_layer<PN_C3, PN16_LD1, PN_C4, PN16_LD4, NRB>(X1, a.W[3], a.scl[3], a.shf[3], a.slope, X2, wave, lane);
     __syncthreads();
     // 3. layer 5 in passes; the workgroup's 64-row slots of the partials both take its maxima
-    float* part = a.part + ((size_t)b * a.tpc + t * (RT / PN_RT)) * PN_C5;
-    const bool second = RT > PN_RT && row0 + PN_RT < nb;
-    const bool full = nrows == RT;
+    float* part = a.part + ((size_t)tile.b * a.tpc + tile.t * (ROWS / RT)) * PN_C5;
+    const bool second = ROWS > RT && tile.row0 + RT < tile.nb;
+    const bool full = tile.nrows == ROWS;
     const int c_begin = blockIdx.y * a.cols_per_split, c_end = c_begin + a.cols_per_split;
     for (int c0 = c_begin; c0 < c_end; c0 += PASS5) {
         f32x16 acc[NRB][NJ5];
@@ -273,7 +148,7 @@ __global__ __launch_bounds__(PN_T, 2) void pointnet_stack_infer_bf16_kernel(cons
                 for (int rb = 0; rb < NRB; ++rb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const bool ok = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh < nrows;
+                        const bool ok = acc_row(rb, r, lh) < tile.nrows;
                         mx = fmaxf(mx, ok ? acc[rb][j][r] : -INFINITY);
                         mn = fminf(mn, ok ? acc[rb][j][r] : INFINITY);
                     }
@@ -287,18 +162,6 @@ __global__ __launch_bounds__(PN_T, 2) void pointnet_stack_infer_bf16_kernel(cons
             }
         }
     }
-}
-
-// out[b][c] = max over the cloud's live tiles, ascending
-__global__ __launch_bounds__(PN_T) void pointnet_tile_max_kernel(const float* __restrict__ part, const int32_t* __restrict__ n_valid,
-                                                                 int N, int tpc, float* __restrict__ out, int ldo) {
-    const int b = blockIdx.x, c = blockIdx.y * PN_T + threadIdx.x;
-    const int nb = n_valid ? min(max(n_valid[b], 1), N) : N;
-    const int live = (nb + PN_RT - 1) / PN_RT;
-    const float* p = part + (size_t)b * tpc * PN_C5 + c;
-    float mx = p[0];
-    for (int t = 1; t < live; ++t) mx = fmaxf(mx, p[(size_t)t * PN_C5]);
-    out[(size_t)b * ldo + c] = mx;
 }
 
 // Rows per workgroup of the bf16 kernel, a pure function of the sizes: 128 once there is a 128-row tile for each of the MI355X's
@@ -317,13 +180,13 @@ extern "C" int pcl_pointnet_stack_infer_supported(int C0, int L, const int32_t* 
 
 extern "C" size_t pcl_pointnet_stack_infer_workspace_bytes(int B, int N, int C_last) {
     if (B < 1 || N < 1 || C_last < 1) return 0;
-    return 4 * (size_t)B * ((N + PN_RT - 1) / PN_RT) * C_last;
+    return 4 * (size_t)B * ((N + RT - 1) / RT) * C_last;
 }
 
 // 512 workgroups are two per CU of the MI355X's 256: fewer tiles than that split the last layer's columns
 extern "C" int pcl_pointnet_stack_infer_splits(int B, int N) {
     if (B < 1 || N < 1) return 1;
-    const long long tiles = (long long)B * ((N + PN_RT - 1) / PN_RT);
+    const long long tiles = (long long)B * ((N + RT - 1) / RT);
     return tiles <= 128 ? 4 : tiles <= 256 ? 2 : 1;
 }
 
@@ -334,7 +197,7 @@ int pn16_launch(const char* who, const PnArgs& a, int splits, hipStream_t st) {
     auto kern = pointnet_stack_infer_bf16_kernel<NRB>;
     const int tiles = (a.N + 32 * NRB - 1) / (32 * NRB);
     if (int rc = lds_opt_in(kern, pn16_lds(NRB), who)) return rc;
-    hipLaunchKernelGGL(kern, dim3(a.B * tiles, splits), dim3(PN_T), pn16_lds(NRB), st, a);
+    hipLaunchKernelGGL(kern, dim3(a.B * tiles, splits), dim3(NT), pn16_lds(NRB), st, a);
     return check_launch(who);
 }
 
@@ -349,8 +212,8 @@ int pn_stack_infer(const char* who, const float* x, size_t stride_b, size_t stri
                 C0, L, widths[0], L > 1 ? widths[1] : 0, L > 2 ? widths[2] : 0, L > 3 ? widths[3] : 0, L > 4 ? widths[4] : 0);
     PCL_REQUIRE(x && W0 && out, "%s: null pointer (x, W0 or out)", who);
     PCL_REQUIRE(B >= 1 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
-    const int tpc = (N + PN_RT - 1) / PN_RT;
-    PCL_REQUIRE((size_t)B * tpc < (1u << 31) / PN_RT, "%s: too many points", who);
+    const int tpc = (N + RT - 1) / RT;
+    PCL_REQUIRE((size_t)B * tpc < (1u << 31) / RT, "%s: too many points", who);
     PCL_REQUIRE(ldw0 >= PN_C0 && ldo >= PN_C5, "%s: ldw0=%d ldo=%d for %d -> %d channels", who, ldw0, ldo, PN_C0, PN_C5);
     for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", who, l);
     // the bf16 kernel's last epilogue runs on the extreme accumulators: monotone only for these slopes (header comment)
@@ -369,17 +232,17 @@ int pn_stack_infer(const char* who, const float* x, size_t stride_b, size_t stri
     a.part = static_cast<float*>(workspace);
     const int splits = pcl_pointnet_stack_infer_splits(B, N);
     a.cols_per_split = PN_C5 / splits;
-    static_assert(PN_C5 / 4 % PN_PASS == 0, "a split is a whole number of passes");
+    static_assert(PN_C5 / 4 % MAX_PASS == 0, "a split is a whole number of passes");
     hipStream_t st = as_stream(stream);
     if constexpr (BF16) {
         if (int rc = pn16_rows(B, N) == 128 ? pn16_launch<4>(who, a, splits, st) : pn16_launch<2>(who, a, splits, st)) return rc;
     } else {
         if (int rc = lds_opt_in(pointnet_stack_infer_kernel, PN_LDS, who)) return rc;
-        hipLaunchKernelGGL(pointnet_stack_infer_kernel, dim3(B * tpc, splits), dim3(PN_T), PN_LDS, st, a);
+        hipLaunchKernelGGL(pointnet_stack_infer_kernel, dim3(B * tpc, splits), dim3(NT), PN_LDS, st, a);
         if (int rc = check_launch(who)) return rc;
     }
-    hipLaunchKernelGGL(pointnet_tile_max_kernel, dim3(B, PN_C5 / PN_T), dim3(PN_T), 0, st, static_cast<const float*>(workspace), n_valid, N,
-                       tpc, out, ldo);
+    hipLaunchKernelGGL(tile_max_kernel<PN_C5>, dim3(B, PN_C5 / NT), dim3(NT), 0, st, static_cast<const float*>(workspace), n_valid, N, tpc,
+                       out, ldo);
     return check_launch(who);
 }
 

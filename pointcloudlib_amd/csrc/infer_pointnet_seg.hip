@@ -15,6 +15,9 @@
 // rows >= n_b are selected to -inf under a max; per-tile partial maxima go to a never-cleared workspace and are reduced in
 // ascending tile order; no atomics, no inter-workgroup hand-off; layers run on infer::mfma_layer.  Rows of a GEMM are
 // independent: a pad row inside a live tile (NaN included) stays in that row; rows beyond the capacity repeat row N - 1.
+// The pieces both files run live in infer_mfma.h: the tile prologue (infer::cloud_tile), the K = 3 layer (infer::points_layer,
+// here also with the 3 x 3 transform and the store into F), the last layer under a max (infer::max_passes) and the tile reduce
+// (infer::tile_max_kernel).  seg_layer keeps its own epilogue loop: it alone also stores rows to F and has an identity form.
 // stn and trunk are two instantiations of one kernel body (seg_front_kernel<TRUNK>).
 //
 // Numerics: K = 3 layers are fmaf(w2, z, fmaf(w1, y, w0 * x)), the 3 x 3 transform the same chain in ascending k; every other
@@ -27,29 +30,20 @@
 namespace pcl {
 namespace {
 
-using infer::act;
-using infer::f32x16;
-using infer::mfma_layer;
-using infer::mfma_layer_acc;
+using namespace infer;
 
-constexpr int SG_T = 256;          // threads per workgroup (4 waves)
-constexpr int SG_RT = 64;          // rows per tile
-constexpr int SG_LD = 132;         // row stride of a 128-wide LDS tile (128 + 4: ds_read_b128 rows on distinct banks)
-constexpr int SG_LD4 = 516;        // ... of the 512-wide out4 tile
-constexpr int SG_LDH = 260;        // ... of the head's 256-wide tile
-constexpr int SG_NJ = 2;           // column blocks per wave and pass under a max (64 accumulator registers)
-constexpr int SG_PASS = 4 * SG_NJ * 32;
+constexpr int SG_LD4 = 512 + row_pad<float>;       // row stride of the 512-wide out4 tile
+constexpr int SG_LDH = 256 + row_pad<float>;       // ... of the head's 256-wide tile
 constexpr int SG_C1 = 64, SG_C2 = 128, SG_C3 = 128, SG_C4 = 512, SG_C5 = 2048, SG_CT = 1024;
 constexpr int SG_F2 = SG_C1, SG_F3 = SG_F2 + SG_C2, SG_F4 = SG_F3 + SG_C3, SG_FK = SG_F4 + SG_C4;      // F's column blocks; 832
 constexpr int SG_H1 = 256, SG_H2 = 256, SG_H3 = 128, SG_PMAX = 128;
 constexpr int SG_CHUNK = 128;      // K-chunk of the head's first layer: 832 = 6 * 128 + 64
-constexpr size_t SG_LDS_FRONT = 4 * (size_t)2 * SG_RT * SG_LD;           // 67 584 B: two workgroups per CU
-constexpr size_t SG_LDS_GLOBAL = 4 * (size_t)SG_RT * SG_LD4;             // 132 096 B: one workgroup per CU
+constexpr size_t SG_LDS_FRONT = 4 * (size_t)2 * RT * LD128;              // 67 584 B: two workgroups per CU
+constexpr size_t SG_LDS_GLOBAL = 4 * (size_t)RT * SG_LD4;                // 132 096 B: one workgroup per CU
 constexpr size_t SG_LDS_HEAD = SG_LDS_FRONT;                             // the two chunk buffers, then the [64][260] tile over them
-static_assert(4 * (size_t)SG_RT * SG_LDH <= SG_LDS_HEAD, "the head's tile lies over its chunk buffers");
-static_assert(2 * SG_RT * SG_LD <= SG_RT * SG_LD4, "out3 and its transform lie inside the out4 tile");
-
-__device__ __forceinline__ int acc_row(int rb, int r, int lh) { return rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh; }
+static_assert(4 * (size_t)RT * SG_LDH <= SG_LDS_HEAD, "the head's tile lies over its chunk buffers");
+static_assert(2 * RT * LD128 <= RT * SG_LD4, "out3 and its transform lie inside the out4 tile");
+static_assert(SG_CT % MAX_PASS == 0 && SG_C5 % MAX_PASS == 0, "whole passes under the max");
 
 // One layer of a 64-row tile: z = act(scale * (X W^T) + shift), or z = X W^T when scl is null, from X (LDS, row stride LDX) into
 // Y (LDS, row stride LDY) and, when G is not null, its rows < nrows into G (global, row stride ldg) as well.  INPLACE: Y may lie
@@ -82,36 +76,6 @@ __device__ __forceinline__ void seg_layer(const float* X, const float* __restric
     }
 }
 
-// The last layer under a max, in passes of 256 columns: z = scale * (X W^T) + shift (ACT: and the activation), rows >= nrows
-// selected to -inf, the max over the lane's 32 rows in registers, then across the two lane halves -> part[col], col < C
-template <int K, int LDX, int C, bool ACT>
-__device__ __forceinline__ void seg_max_passes(const float* X, const float* __restrict__ W, const float* __restrict__ scl,
-                                               const float* __restrict__ shf, float slope, int nrows, float* __restrict__ part, int wave,
-                                               int lane) {
-    static_assert(C % SG_PASS == 0, "whole passes");
-    const int lr = lane & 31, lh = lane >> 5;
-    for (int c0 = 0; c0 < C; c0 += SG_PASS) {
-        f32x16 acc[2][SG_NJ];
-        mfma_layer<K, LDX, SG_NJ, 4 * SG_NJ>(X, W + (size_t)c0 * K, wave, lane, acc);
-#pragma unroll
-        for (int j = 0; j < SG_NJ; ++j) {
-            const int col = c0 + (wave + 4 * j) * 32 + lr;
-            const float sc = scl[col], sh = shf[col];
-            float mx = -INFINITY;
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float u = sc * acc[rb][j][r] + sh;
-                    const float z = ACT ? act(u, slope) : u;
-                    mx = fmaxf(mx, acc_row(rb, r, lh) < nrows ? z : -INFINITY);
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            if (lh == 0) part[col] = mx;
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------- stn and trunk
 struct SegFrontArgs {
     const float* x; size_t sb, sn, sc;
@@ -125,86 +89,45 @@ struct SegFrontArgs {
     float* part;                                   // [B * tpc][1024]
 };
 
-// the K = 3 layer from the coordinates at the caller's strides, four channels per thread -> X1 (and, TRUNK, F[., 0:64])
 template <bool TRUNK>
-__device__ __forceinline__ void seg_points_layer(const SegFrontArgs& a, float* X1, int b, int row0, int nrows, int tid) {
-    constexpr int TPR = SG_C1 / 4;                 // threads per row
-    const float* scl = TRUNK ? a.cscl[0] : a.sscl[0];
-    const float* shf = TRUNK ? a.cshf[0] : a.sshf[0];
-    const int c4 = (tid % TPR) * 4;
-    float w[4][3], sc1[4], sh1[4], T[9];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) w[i][d] = a.W0[(size_t)(c4 + i) * a.ldw0 + d];
-        sc1[i] = scl[c4 + i]; sh1[i] = shf[c4 + i];
-    }
-    if (TRUNK) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) T[i] = a.T3[(size_t)b * 9 + i];
-    }
-    const float* xb = a.x + (size_t)b * a.sb;
-    for (int r = tid / TPR; r < SG_RT; r += SG_T / TPR) {
-        const float* p = xb + (size_t)min(row0 + r, a.N - 1) * a.sn;
-        float px = p[0], py = p[a.sc], pz = p[2 * a.sc];
-        if (TRUNK) {
-            const float qx = fmaf(pz, T[6], fmaf(py, T[3], px * T[0]));
-            const float qy = fmaf(pz, T[7], fmaf(py, T[4], px * T[1]));
-            const float qz = fmaf(pz, T[8], fmaf(py, T[5], px * T[2]));
-            px = qx; py = qy; pz = qz;
-        }
-        float z[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float y = fmaf(w[i][2], pz, fmaf(w[i][1], py, w[i][0] * px));
-            z[i] = act(sc1[i] * y + sh1[i], a.slope);
-        }
-        const float4 z4 = make_float4(z[0], z[1], z[2], z[3]);
-        *reinterpret_cast<float4*>(X1 + r * SG_LD + c4) = z4;
-        if (TRUNK && r < nrows) *reinterpret_cast<float4*>(a.F + ((size_t)b * a.N + row0 + r) * a.ldf + c4) = z4;
-    }
-}
-
-template <bool TRUNK>
-__global__ __launch_bounds__(SG_T, 2) void seg_front_kernel(const SegFrontArgs a) {
+__global__ __launch_bounds__(NT, 2) void seg_front_kernel(const SegFrontArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* X1 = smem;                              // [RT][LD]
-    float* X2 = X1 + SG_RT * SG_LD;                // [RT][LD]
+    float* X1 = smem;                              // [RT][LD128]
+    float* X2 = X1 + RT * LD128;                   // [RT][LD128]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int t = blockIdx.x / a.B, b = blockIdx.x - t * a.B;     // tile-major
-    const int nb = a.n_valid ? min(max(a.n_valid[b], 1), a.N) : a.N;
-    const int row0 = t * SG_RT;
-    if (row0 >= nb) return;                        // a tile of pad rows only (uniform exit, ahead of every barrier)
-    const int nrows = min(SG_RT, nb - row0);
-    seg_points_layer<TRUNK>(a, X1, b, row0, nrows, tid);
+    const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
+    if (tile.empty()) return;
+    const int b = tile.b, t = tile.t, row0 = tile.row0, nrows = tile.nrows;
+    // the K = 3 layer -> X1 (and, TRUNK, on the transformed point and also into F[., 0:64])
+    points_layer<float, RT, LD128, TRUNK, TRUNK>(a.x + (size_t)b * a.sb, a.sn, a.sc, a.N, row0, TRUNK ? a.T3 + (size_t)b * 9 : nullptr, a.W0,
+                                                 a.ldw0, TRUNK ? a.cscl[0] : a.sscl[0], TRUNK ? a.cshf[0] : a.sshf[0], a.slope, X1,
+                                                 TRUNK ? a.F + ((size_t)b * a.N + row0) * a.ldf : nullptr, a.ldf, nrows, tid);
     __syncthreads();
     float *Xa = X1, *Xb = X2;                      // the T-Net's 64-wide first activation, and the other tile
     if (TRUNK) {
         float* Fr = a.F + ((size_t)b * a.N + row0) * a.ldf;
-        seg_layer<SG_C1, SG_LD, SG_C2, SG_LD, false>(X1, a.cW[1], a.cscl[1], a.cshf[1], a.slope, X2, Fr + SG_F2, a.ldf, nrows, wave, lane);
+        seg_layer<SG_C1, LD128, SG_C2, LD128, false>(X1, a.cW[1], a.cscl[1], a.cshf[1], a.slope, X2, Fr + SG_F2, a.ldf, nrows, wave, lane);
         __syncthreads();
-        seg_layer<SG_C2, SG_LD, SG_C3, SG_LD, false>(X2, a.cW[2], a.cscl[2], a.cshf[2], a.slope, X1, Fr + SG_F3, a.ldf, nrows, wave, lane);
+        seg_layer<SG_C2, LD128, SG_C3, LD128, false>(X2, a.cW[2], a.cscl[2], a.cshf[2], a.slope, X1, Fr + SG_F3, a.ldf, nrows, wave, lane);
         __syncthreads();
-        seg_layer<SG_C3, SG_LD, 64, SG_LD, false>(X1, a.sW[0], a.sscl[0], a.sshf[0], a.slope, X2, nullptr, 0, nrows, wave, lane);
+        seg_layer<SG_C3, LD128, 64, LD128, false>(X1, a.sW[0], a.sscl[0], a.sshf[0], a.slope, X2, nullptr, 0, nrows, wave, lane);
         __syncthreads();
         Xa = X2; Xb = X1;
     }
-    seg_layer<64, SG_LD, 128, SG_LD, false>(Xa, a.sW[1], a.sscl[1], a.sshf[1], a.slope, Xb, nullptr, 0, nrows, wave, lane);
+    seg_layer<64, LD128, 128, LD128, false>(Xa, a.sW[1], a.sscl[1], a.sshf[1], a.slope, Xb, nullptr, 0, nrows, wave, lane);
     __syncthreads();
-    seg_max_passes<128, SG_LD, SG_CT, true>(Xb, a.sW[2], a.sscl[2], a.sshf[2], a.slope, nrows, a.part + ((size_t)b * a.tpc + t) * SG_CT,
-                                            wave, lane);
+    max_passes<128, LD128, true>(Xb, a.sW[2], a.sscl[2], a.sshf[2], a.slope, nrows, a.part + ((size_t)b * a.tpc + t) * SG_CT, 0, SG_CT, wave,
+                                 lane);
 }
 
-// out[b][c] = max over the cloud's live tiles, ascending (pointnet_tile_max_kernel's scheme for C columns)
-__global__ __launch_bounds__(SG_T) void seg_tile_max_kernel(const float* __restrict__ part, const int32_t* __restrict__ n_valid, int N,
-                                                            int tpc, int C, float* __restrict__ out, int ldo) {
-    const int b = blockIdx.x, c = blockIdx.y * SG_T + threadIdx.x;
-    const int nb = n_valid ? min(max(n_valid[b], 1), N) : N;
-    const int live = (nb + SG_RT - 1) / SG_RT;
-    const float* p = part + (size_t)b * tpc * C + c;
-    float mx = p[0];
-    for (int t = 1; t < live; ++t) mx = fmaxf(mx, p[(size_t)t * C]);
-    out[(size_t)b * ldo + c] = mx;
+// columns [k0, k0 + kw) of the tile's rows of F -> buf [RT][LD128]
+__device__ __forceinline__ void seg_stage(const float* __restrict__ Fb, int ldf, int N, int row0, int k0, int kw, float* buf, int tid) {
+    const int per = kw / 4;
+    for (int i = tid; i < RT * per; i += NT) {
+        const int r = i / per, c4 = (i - r * per) * 4;
+        const float* src = Fb + (size_t)min(row0 + r, N - 1) * ldf + k0 + c4;
+        *reinterpret_cast<float4*>(buf + r * LD128 + c4) = *reinterpret_cast<const float4*>(src);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------- global
@@ -217,32 +140,26 @@ struct SegGlobalArgs {
     float* part;                                   // [B * tpc][2048]
 };
 
-__global__ __launch_bounds__(SG_T, 1) void seg_global_kernel(const SegGlobalArgs a) {
+__global__ __launch_bounds__(NT, 1) void seg_global_kernel(const SegGlobalArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* X4 = smem;                              // [RT][LD4]: out4; before it exists, out3 and its transform lie inside
-    float* X1 = smem;                              // [RT][LD]
-    float* X2 = X1 + SG_RT * SG_LD;                // [RT][LD]
+    float* X1 = smem;                              // [RT][LD128]
+    float* X2 = X1 + RT * LD128;                   // [RT][LD128]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int t = blockIdx.x / a.B, b = blockIdx.x - t * a.B;
-    const int nb = a.n_valid ? min(max(a.n_valid[b], 1), a.N) : a.N;
-    const int row0 = t * SG_RT;
-    if (row0 >= nb) return;
-    const int nrows = min(SG_RT, nb - row0);
+    const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
+    if (tile.empty()) return;
+    const int b = tile.b, t = tile.t, row0 = tile.row0, nrows = tile.nrows;
     const float* Fb = a.F + (size_t)b * a.N * a.ldf;
-    for (int i = tid; i < SG_RT * (SG_C3 / 4); i += SG_T) {
-        const int r = i / (SG_C3 / 4), c4 = (i % (SG_C3 / 4)) * 4;
-        const float* src = Fb + (size_t)min(row0 + r, a.N - 1) * a.ldf + SG_F3 + c4;
-        *reinterpret_cast<float4*>(X1 + r * SG_LD + c4) = *reinterpret_cast<const float4*>(src);
-    }
+    seg_stage(Fb, a.ldf, a.N, row0, SG_F3, SG_C3, X1, tid);
     __syncthreads();
-    seg_layer<SG_C3, SG_LD, SG_C3, SG_LD, false>(X1, a.TT + (size_t)b * SG_C3 * SG_C3, nullptr, nullptr, a.slope, X2, nullptr, 0, nrows, wave,
+    seg_layer<SG_C3, LD128, SG_C3, LD128, false>(X1, a.TT + (size_t)b * SG_C3 * SG_C3, nullptr, nullptr, a.slope, X2, nullptr, 0, nrows, wave,
                                                  lane);
     __syncthreads();
     float* Fr = a.F + ((size_t)b * a.N + row0) * a.ldf;
-    seg_layer<SG_C3, SG_LD, SG_C4, SG_LD4, true>(X2, a.W[0], a.scl[0], a.shf[0], a.slope, X4, Fr + SG_F4, a.ldf, nrows, wave, lane);
+    seg_layer<SG_C3, LD128, SG_C4, SG_LD4, true>(X2, a.W[0], a.scl[0], a.shf[0], a.slope, X4, Fr + SG_F4, a.ldf, nrows, wave, lane);
     __syncthreads();
-    seg_max_passes<SG_C4, SG_LD4, SG_C5, false>(X4, a.W[1], a.scl[1], a.shf[1], a.slope, nrows, a.part + ((size_t)b * a.tpc + t) * SG_C5, wave,
-                                                lane);
+    max_passes<SG_C4, SG_LD4, false>(X4, a.W[1], a.scl[1], a.shf[1], a.slope, nrows, a.part + ((size_t)b * a.tpc + t) * SG_C5, 0, SG_C5, wave,
+                                     lane);
 }
 
 // ------------------------------------------------------------------------------------------------------- head
@@ -256,54 +173,38 @@ struct SegHeadArgs {
     float* out; size_t ob, oc, on;
 };
 
-// columns [k0, k0 + kw) of the tile's rows of F -> buf [RT][LD]
-__device__ __forceinline__ void seg_stage(const float* __restrict__ Fb, int ldf, int N, int row0, int k0, int kw, float* buf, int tid) {
-    const int per = kw / 4;
-    for (int i = tid; i < SG_RT * per; i += SG_T) {
-        const int r = i / per, c4 = (i - r * per) * 4;
-        const float* src = Fb + (size_t)min(row0 + r, N - 1) * ldf + k0 + c4;
-        *reinterpret_cast<float4*>(buf + r * SG_LD + c4) = *reinterpret_cast<const float4*>(src);
-    }
-}
-
-__global__ __launch_bounds__(SG_T, 2) void seg_head_kernel(const SegHeadArgs a) {
+__global__ __launch_bounds__(NT, 2) void seg_head_kernel(const SegHeadArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Y = smem;                               // [RT][LDH], over the two chunk buffers once layer 1 has read them
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
-    const int t = blockIdx.x / a.B, b = blockIdx.x - t * a.B;
-    const int nb = a.n_valid ? min(max(a.n_valid[b], 1), a.N) : a.N;
-    const int row0 = t * SG_RT;
+    const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
+    const int b = tile.b, row0 = tile.row0, nrows = tile.nrows;
     float* ob = a.out + (size_t)b * a.ob;
-    if (row0 >= nb) {                              // a tile of pad rows only: its logits are zeros; nothing is loaded
+    if (tile.empty()) {                               // a tile of pad rows only: its logits are zeros; nothing is loaded
         if (row0 + lane < a.N)
             for (int c = wave; c < a.part_num; c += 4) ob[(size_t)c * a.oc + (size_t)(row0 + lane) * a.on] = 0.f;
         return;
     }
-    const int nrows = min(SG_RT, nb - row0);
     const float* Fb = a.F + (size_t)b * a.N * a.ldf;
     // layer 1: 832 -> 256 over K-chunks of 128 (the last one 64), the next chunk staged while this one is multiplied
     constexpr int NFULL = SG_FK / SG_CHUNK, REST = SG_FK - NFULL * SG_CHUNK;
     static_assert(REST == 64 && NFULL % 2 == 0, "the chunk schedule below");
-    f32x16 acc[2][SG_NJ];
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int j = 0; j < SG_NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rb][j][r] = 0.f;
+    constexpr int NJ = SG_H1 / 32 / 4;
+    f32x16 acc[2][NJ];
+    acc_clear(acc);
     seg_stage(Fb, a.ldf, a.N, row0, 0, SG_CHUNK, smem, tid);
     __syncthreads();
     for (int c = 0; c < NFULL; ++c) {
-        const float* cur = smem + (c & 1) * SG_RT * SG_LD;
-        float* nxt = smem + ((c + 1) & 1) * SG_RT * SG_LD;
+        const float* cur = smem + (c & 1) * RT * LD128;
+        float* nxt = smem + ((c + 1) & 1) * RT * LD128;
         seg_stage(Fb, a.ldf, a.N, row0, (c + 1) * SG_CHUNK, c + 1 < NFULL ? SG_CHUNK : REST, nxt, tid);
-        mfma_layer_acc<SG_CHUNK, SG_LD, SG_NJ, SG_H1 / 32>(cur, a.W[0] + c * SG_CHUNK, SG_FK, wave, lane, acc);
+        mfma_layer_acc<SG_CHUNK, LD128, NJ, SG_H1 / 32>(cur, a.W[0] + c * SG_CHUNK, SG_FK, wave, lane, acc);
         __syncthreads();
     }
-    mfma_layer_acc<REST, SG_LD, SG_NJ, SG_H1 / 32>(smem, a.W[0] + NFULL * SG_CHUNK, SG_FK, wave, lane, acc);
+    mfma_layer_acc<REST, LD128, NJ, SG_H1 / 32>(smem, a.W[0] + NFULL * SG_CHUNK, SG_FK, wave, lane, acc);
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < SG_NJ; ++j) {
+    for (int j = 0; j < NJ; ++j) {
         const int col = (wave + 4 * j) * 32 + lr;
         const float sc = a.scl[0][col], sh = a.shf[0][col], cb = a.bias[(size_t)b * a.ldb + col];
 #pragma unroll
@@ -343,7 +244,7 @@ __global__ __launch_bounds__(SG_T, 2) void seg_head_kernel(const SegHeadArgs a) 
 // NV: 16-byte pieces per lane (K <= 256 NV); the narrow layers take the small instantiations and their occupancy.
 constexpr int SG_ROWS_V = 9;                       // the widest: K <= 2304
 template <int NV>
-__global__ __launch_bounds__(SG_T) void seg_rows_kernel(const float* __restrict__ x, int ldx, int R, int K, const float* __restrict__ W,
+__global__ __launch_bounds__(NT) void seg_rows_kernel(const float* __restrict__ x, int ldx, int R, int K, const float* __restrict__ W,
                                                         const float* __restrict__ scl, const float* __restrict__ shf, float slope,
                                                         float* __restrict__ y, int ldy, int C) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -402,12 +303,12 @@ bool seg_shape_ok(int stack, int C0, int L, const int32_t* w) {
     return false;
 }
 
-int tiles_of(int N) { return (N + SG_RT - 1) / SG_RT; }
+int tiles_of(int N) { return (N + RT - 1) / RT; }
 
 // what every launcher asks of its sizes
 int seg_sizes_ok(const char* who, int B, int N) {
     PCL_REQUIRE(B >= 1 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
-    PCL_REQUIRE((size_t)B * tiles_of(N) < (1u << 31) / SG_RT, "%s: too many points", who);
+    PCL_REQUIRE((size_t)B * tiles_of(N) < (1u << 31) / RT, "%s: too many points", who);
     return PCL_OK;
 }
 
@@ -465,9 +366,9 @@ extern "C" int pcl_pointnet_seg_stn_infer_f32(const float* x, size_t stride_b, s
     a.part = static_cast<float*>(workspace);
     hipStream_t st = as_stream(stream);
     if (int rc = lds_opt_in(seg_front_kernel<false>, SG_LDS_FRONT, who)) return rc;
-    hipLaunchKernelGGL(seg_front_kernel<false>, dim3(B * a.tpc), dim3(SG_T), SG_LDS_FRONT, st, a);
+    hipLaunchKernelGGL(seg_front_kernel<false>, dim3(B * a.tpc), dim3(NT), SG_LDS_FRONT, st, a);
     if (int rc = check_launch(who)) return rc;
-    hipLaunchKernelGGL(seg_tile_max_kernel, dim3(B, SG_CT / SG_T), dim3(SG_T), 0, st, a.part, n_valid, N, a.tpc, SG_CT, out, ldo);
+    hipLaunchKernelGGL(tile_max_kernel<SG_CT>, dim3(B, SG_CT / NT), dim3(NT), 0, st, a.part, n_valid, N, a.tpc, out, ldo);
     return check_launch(who);
 }
 
@@ -502,9 +403,9 @@ extern "C" int pcl_pointnet_seg_trunk_infer_f32(const float* x, size_t stride_b,
     a.part = static_cast<float*>(workspace);
     hipStream_t st = as_stream(stream);
     if (int rc = lds_opt_in(seg_front_kernel<true>, SG_LDS_FRONT, who)) return rc;
-    hipLaunchKernelGGL(seg_front_kernel<true>, dim3(B * a.tpc), dim3(SG_T), SG_LDS_FRONT, st, a);
+    hipLaunchKernelGGL(seg_front_kernel<true>, dim3(B * a.tpc), dim3(NT), SG_LDS_FRONT, st, a);
     if (int rc = check_launch(who)) return rc;
-    hipLaunchKernelGGL(seg_tile_max_kernel, dim3(B, SG_CT / SG_T), dim3(SG_T), 0, st, a.part, n_valid, N, a.tpc, SG_CT, out, ldo);
+    hipLaunchKernelGGL(tile_max_kernel<SG_CT>, dim3(B, SG_CT / NT), dim3(NT), 0, st, a.part, n_valid, N, a.tpc, out, ldo);
     return check_launch(who);
 }
 
@@ -531,9 +432,9 @@ extern "C" int pcl_pointnet_seg_global_infer_f32(float* F, int ldf, size_t f_byt
     a.part = static_cast<float*>(workspace);
     hipStream_t st = as_stream(stream);
     if (int rc = lds_opt_in(seg_global_kernel, SG_LDS_GLOBAL, who)) return rc;
-    hipLaunchKernelGGL(seg_global_kernel, dim3(B * a.tpc), dim3(SG_T), SG_LDS_GLOBAL, st, a);
+    hipLaunchKernelGGL(seg_global_kernel, dim3(B * a.tpc), dim3(NT), SG_LDS_GLOBAL, st, a);
     if (int rc = check_launch(who)) return rc;
-    hipLaunchKernelGGL(seg_tile_max_kernel, dim3(B, SG_C5 / SG_T), dim3(SG_T), 0, st, a.part, n_valid, N, a.tpc, SG_C5, out, ldo);
+    hipLaunchKernelGGL(tile_max_kernel<SG_C5>, dim3(B, SG_C5 / NT), dim3(NT), 0, st, a.part, n_valid, N, a.tpc, out, ldo);
     return check_launch(who);
 }
 
@@ -564,7 +465,7 @@ extern "C" int pcl_pointnet_seg_head_infer_f32(const float* F, int ldf, size_t f
     a.out = out; a.ob = stride_b; a.oc = stride_c; a.on = stride_n;
     hipStream_t st = as_stream(stream);
     if (int rc = lds_opt_in(seg_head_kernel, SG_LDS_HEAD, who)) return rc;
-    hipLaunchKernelGGL(seg_head_kernel, dim3(B * a.tpc), dim3(SG_T), SG_LDS_HEAD, st, a);
+    hipLaunchKernelGGL(seg_head_kernel, dim3(B * a.tpc), dim3(NT), SG_LDS_HEAD, st, a);
     return check_launch(who);
 }
 
@@ -577,7 +478,7 @@ extern "C" int pcl_pointnet_seg_rows_f32(const float* x, int ldx, int R, int K, 
     PCL_REQUIRE(ldx >= K && ldx % 4 == 0 && ldy >= C && al16(x, W), "%s: x and W must be 16-byte aligned, ldx=%d a multiple of 4, ldy=%d", who,
                 ldx, ldy);
     hipStream_t st = as_stream(stream);
-    const dim3 grid((C + 3) / 4), block(SG_T);
+    const dim3 grid((C + 3) / 4), block(NT);
     if (K <= 256) hipLaunchKernelGGL(seg_rows_kernel<1>, grid, block, 0, st, x, ldx, R, K, W, scale, shift, slope, y, ldy, C);
     else if (K <= 1024) hipLaunchKernelGGL(seg_rows_kernel<4>, grid, block, 0, st, x, ldx, R, K, W, scale, shift, slope, y, ldy, C);
     else hipLaunchKernelGGL(seg_rows_kernel<SG_ROWS_V>, grid, block, 0, st, x, ldx, R, K, W, scale, shift, slope, y, ldy, C);

@@ -83,33 +83,65 @@ def _eval_consts(mlp, l):
     return scale.float().contiguous(), shift.float().contiguous()
 
 
-class _Fused:
+def _pad32(t, fill):
+    """``t`` ([C, ...] or [C]) with its first dimension padded to a multiple of 32 with ``fill``."""
+    c = t.shape[0]
+    cp = -(-c // 32) * 32
+    if cp == c:
+        return t.contiguous()
+    out = torch.full((cp,) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)
+    out[:c] = t
+    return out
+
+
+_OWN = object()                    # _SegStack(first=_OWN): the first weight is the first layer's own
+
+
+class _SegStack:
+    """Snapshot of consecutive layers ``[(mlp, l)]`` for a frozen-inference launcher: dense fp32 weights ``Ws``, eval constants
+    ``scales`` / ``shifts``, the layer ``widths``, and the ctypes arrays ``c_widths / c_W / c_scale / c_shift`` over them.
+
+    ``first``: what stands for the first weight -- by default a clone of the layer's own; ``None`` when the first layer is
+    folded and the kernel takes it apart from the arrays; or a tensor that replaces it.  ``bf16``: also ``Ws_bf16``, the weights
+    of layers 2 and up rounded once to bf16 (``[None, ...]``), and ``c_W`` points at those.  ``pad_last``: the last layer's
+    weight, scale and shift padded to a multiple of 32 rows (zero weights); ``widths`` keeps the layer's own."""
+
+    def __init__(self, layers, first=_OWN, bf16=False, pad_last=False):
+        self.L = L = len(layers)
+        self.widths = [mlp.weights[l].shape[0] for mlp, l in layers]
+        self.Ws, self.scales, self.shifts = [], [], []
+        for i, (mlp, l) in enumerate(layers):
+            sc, sh = _eval_consts(mlp, l)
+            W = mlp.weights[l].detach().float()
+            if pad_last and i == L - 1:
+                W, sc, sh = _pad32(W, 0.0), _pad32(sc, 1.0), _pad32(sh, 0.0)
+            self.Ws.append(W.contiguous().clone() if i or first is _OWN else first)
+            self.scales.append(sc)
+            self.shifts.append(sh)
+        operands = self.Ws
+        if bf16:                                                       # the bf16 operands of layers 2 and up, rounded once here
+            operands = self.Ws_bf16 = [None] + [w.to(torch.bfloat16).contiguous() for w in self.Ws[1:]]
+        self.c_widths = (ctypes.c_int32 * L)(*self.widths)
+        self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in operands])
+        self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
+        self.c_shift = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.shifts])
+
+
+class _Fused(_SegStack):
     """Snapshot of one ball-query scale for pcl_sa_level_infer_f32 (or, ``precision="bf16"``, pcl_sa_level_infer_bf16_f32)."""
 
     def __init__(self, mlp, use_xyz, C, precision="fp32"):
+        super().__init__([(mlp, l) for l in range(len(mlp.weights))], first=None, bf16=precision == "bf16")
         self.precision = precision
         W0 = mlp.weights[0].detach().float().contiguous().clone()
         self.use_xyz, self.C, self.slope = use_xyz, C, float(mlp.slope)
         off = 3 if use_xyz else 0
-        self.widths = [w.shape[0] for w in mlp.weights]
         self.W0 = W0
         self.ldw = W0.shape[1]
         self.Wx = W0[:, :3] if use_xyz else None                       # view: the kernel reads it with the row stride ldw
         self.inline = 0 < C <= 4
         self.Wf = None if C == 0 else (W0[:, off:] if self.inline else W0[:, off:].contiguous())
-        self.Ws = [None] + [mlp.weights[l].detach().float().contiguous().clone() for l in range(1, len(self.widths))]
-        consts = [_eval_consts(mlp, l) for l in range(len(self.widths))]
-        self.scales, self.shifts = [c[0] for c in consts], [c[1] for c in consts]
-        L = len(self.widths)
-        self.c_widths = (ctypes.c_int32 * L)(*self.widths)
-        self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in self.Ws])
-        self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
-        self.c_shift = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.shifts])
-        self.entry = "pcl_sa_level_infer_f32"
-        if precision == "bf16":                                        # the bf16 operands of layers 2 and up, rounded once here
-            self.Ws_bf16 = [None] + [w.to(torch.bfloat16).contiguous() for w in self.Ws[1:]]
-            self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in self.Ws_bf16])
-            self.entry = "pcl_sa_level_infer_bf16_f32"
+        self.entry = "pcl_sa_level_infer_bf16_f32" if precision == "bf16" else "pcl_sa_level_infer_f32"
 
     def run(self, xyz, new_xyz, feature, idx, cnt, out, col0):
         B, N, _ = xyz.shape
@@ -261,18 +293,7 @@ class FrozenPointNet2(_FrozenEncoder):
         return feats, logits[0] if len(logits) == 1 else torch.cat(logits)
 
 
-def _pad32(t, fill):
-    """``t`` ([C, ...] or [C]) with its first dimension padded to a multiple of 32 with ``fill``."""
-    c = t.shape[0]
-    cp = -(-c // 32) * 32
-    if cp == c:
-        return t.contiguous()
-    out = torch.full((cp,) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)
-    out[:c] = t
-    return out
-
-
-class _FusedFP:
+class _FusedFP(_SegStack):
     """Snapshot of one feature-propagation level for pcl_fp_level_infer_f32, optionally with the head layers behind it.
 
     ``D1`` skip channels (the first ``n_onehot`` of them the one-hot class label, a per-cloud bias), then the coarse
@@ -290,24 +311,9 @@ class _FusedFP:
         layers = [(mlp, l, l < mlp.n_layers - 1 or mlp.last_act) for l in range(mlp.n_layers)]
         for h in head:
             layers += [(h, l, l < h.n_layers - 1 or h.last_act) for l in range(h.n_layers)]
-        self.widths = [m.weights[l].shape[0] for m, l, _ in layers]
         self.act_mask = sum(1 << i for i, (_, _, a) in enumerate(layers) if a)
         self.tap_layer = mlp.n_layers - 1 if head else None          # the level's own output, stored beside the head's
-        L = len(layers)
-        self.Ws, self.scales, self.shifts = [None], [], []
-        for i, (m, l, _) in enumerate(layers):
-            sc, sh = _eval_consts(m, l)
-            W = m.weights[l].detach().float()
-            if i == L - 1:                                           # the last layer: padded to 32 columns with zero weights
-                W, sc, sh = _pad32(W, 0.0), _pad32(sc, 1.0), _pad32(sh, 0.0)
-            if i:
-                self.Ws.append(W.contiguous().clone())
-            self.scales.append(sc)
-            self.shifts.append(sh)
-        self.c_widths = (ctypes.c_int32 * L)(*self.widths)
-        self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in self.Ws])
-        self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
-        self.c_shift = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.shifts])
+        super().__init__([(m, l) for m, l, _ in layers], first=None, pad_last=True)   # the last layer: padded to 32 columns
 
     @staticmethod
     def _rows(X, W, P):
@@ -494,17 +500,12 @@ class FrozenPointNet:
             self._convs = self._refresh_copy(self._convs, mlp)
             return self
         self.slope, self.width, self.c_widths = float(mlp.slope), widths[-1], c_widths
-        self.Ws = [w.detach().float().contiguous().clone() for w in mlp.weights]
-        consts = [_eval_consts(mlp, l) for l in range(L)]
-        self.scales, self.shifts = [c[0] for c in consts], [c[1] for c in consts]
-        self.c_W = (ctypes.c_void_p * L)(*[w.data_ptr() for w in self.Ws])
-        self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
-        self.c_shift = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.shifts])
-        self.entry = "pcl_pointnet_stack_infer_f32"
-        if self.precision == "bf16":                                   # the bf16 operands of layers 2-5, rounded once here
-            self.Ws_bf16 = [None] + [w.to(torch.bfloat16).contiguous() for w in self.Ws[1:]]
-            self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in self.Ws_bf16])
-            self.entry = "pcl_pointnet_stack_infer_bf16_f32"
+        bf16 = self.precision == "bf16"                                # layers 2-5 then take the stack's bf16 operands
+        s = _SegStack([(mlp, l) for l in range(L)], bf16=bf16)
+        self.Ws, self.scales, self.shifts, self.c_W, self.c_scale, self.c_shift = s.Ws, s.scales, s.shifts, s.c_W, s.c_scale, s.c_shift
+        if bf16:
+            self.Ws_bf16 = s.Ws_bf16
+        self.entry = "pcl_pointnet_stack_infer_bf16_f32" if bf16 else "pcl_pointnet_stack_infer_f32"
         return self
 
     def __call__(self, x, lengths=None):
@@ -564,21 +565,6 @@ def transposed_fc3(weight, bias, k):
     perm = torch.arange(k * k, device=weight.device).view(k, k).t().reshape(-1)
     b = bias.detach() + torch.eye(k, device=weight.device, dtype=bias.dtype).reshape(-1)      # the identity is symmetric
     return weight.detach()[perm].contiguous(), b[perm].contiguous()
-
-
-class _SegStack:
-    """Dense weights, eval constants and the ctypes arrays of consecutive layers ``[(mlp, l)]`` for the csrc/infer_pointnet_seg.hip
-    launchers."""
-
-    def __init__(self, layers, Ws=None):
-        self.Ws = [mlp.weights[l].detach().float().contiguous().clone() for mlp, l in layers] if Ws is None else Ws
-        consts = [_eval_consts(mlp, l) for mlp, l in layers]
-        self.scales, self.shifts = [c[0] for c in consts], [c[1] for c in consts]
-        self.L = len(self.Ws)
-        self.widths = (ctypes.c_int32 * self.L)(*[w.shape[0] for w in self.Ws])
-        self.c_W = (ctypes.c_void_p * self.L)(*[w.data_ptr() for w in self.Ws])
-        self.c_scale = (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in self.scales])
-        self.c_shift = (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in self.shifts])
 
 
 def _seg_rows(x, W, scale, shift, slope, out=None):
@@ -672,10 +658,9 @@ class FrozenPointNetPartseg:
         Wout = torch.zeros((rows, net.convs4.in_features), dtype=torch.float32, device=Wrow.device)
         Wout[:self.part_num] = net.convs4.weight.detach()
         self.bias_out = net.convs4.bias.detach().float().contiguous().clone()
-        self.head = _SegStack([(net.convs, l) for l in range(3)],
-                              [Wrow] + [net.convs.weights[l].detach().float().contiguous().clone() for l in (1, 2)])
+        self.head = _SegStack([(net.convs, l) for l in range(3)], first=Wrow)
         self.Wout = Wout
-        self.head_widths = (ctypes.c_int32 * 4)(*[w.shape[0] for w in self.head.Ws], self.part_num)
+        self.head_widths = (ctypes.c_int32 * 4)(*self.head.widths, self.part_num)
         self.head_W = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in self.head.Ws], Wout.data_ptr())
         return self
 
@@ -717,20 +702,20 @@ class FrozenPointNetPartseg:
         strides = (x.stride(0), x.stride(2), x.stride(1))
         s = self.stn
         g = torch.empty((B, 1024), dtype=torch.float32, device=dev)
-        _lib.call("pcl_pointnet_seg_stn_infer_f32", _p(x), *strides, _p(lengths), B, N, s.L, s.widths, _p(s.Ws[0]), 3, s.c_W, s.c_scale,
+        _lib.call("pcl_pointnet_seg_stn_infer_f32", _p(x), *strides, _p(lengths), B, N, s.L, s.c_widths, _p(s.Ws[0]), 3, s.c_W, s.c_scale,
                   s.c_shift, self.slope, _p(ws), ws_bytes, _p(g), 1024, st)
         T3 = self._run_tail(self.stn_tail, g)
         c, s = self.trunk, self.fstn
         g = torch.empty((B, 1024), dtype=torch.float32, device=dev)
-        _lib.call("pcl_pointnet_seg_trunk_infer_f32", _p(x), *strides, _p(lengths), B, N, _p(T3), c.L, c.widths, _p(c.Ws[0]), 3, c.c_W,
-                  c.c_scale, c.c_shift, s.L, s.widths, s.c_W, s.c_scale, s.c_shift, self.slope, _p(F), self.LDF, f_bytes, _p(ws), ws_bytes,
-                  _p(g), 1024, st)
+        _lib.call("pcl_pointnet_seg_trunk_infer_f32", _p(x), *strides, _p(lengths), B, N, _p(T3), c.L, c.c_widths, _p(c.Ws[0]), 3, c.c_W,
+                  c.c_scale, c.c_shift, s.L, s.c_widths, s.c_W, s.c_scale, s.c_shift, self.slope, _p(F), self.LDF, f_bytes, _p(ws),
+                  ws_bytes, _p(g), 1024, st)
         TT = self._run_tail(self.fstn_tail, g)
         c = self.glob
         glob = torch.empty((B, 2048 + self.N_LABEL), dtype=torch.float32, device=dev)      # out_max | label
         glob[:, 2048:] = label
-        _lib.call("pcl_pointnet_seg_global_infer_f32", _p(F), self.LDF, f_bytes, _p(lengths), B, N, _p(TT), c.L, c.widths, c.c_W, c.c_scale,
-                  c.c_shift, self.slope, _p(ws), ws_bytes, _p(glob), glob.stride(0), st)
+        _lib.call("pcl_pointnet_seg_global_infer_f32", _p(F), self.LDF, f_bytes, _p(lengths), B, N, _p(TT), c.L, c.c_widths, c.c_W,
+                  c.c_scale, c.c_shift, self.slope, _p(ws), ws_bytes, _p(glob), glob.stride(0), st)
         bias = _seg_rows(glob, self.Wglob, None, self.c0, 1.0)
         h = self.head
         out = torch.empty((B, self.part_num, N), dtype=torch.float32, device=dev)
