@@ -970,6 +970,32 @@ int pcl_pointnet_seg_head_infer_f32(const float* F, int ldf, size_t f_bytes, con
                                     const float* cloud_bias, int ldb, int L, const int32_t* widths, const float* const* W,
                                     int w_out_rows, const float* const* scale, const float* const* shift, const float* bias_out,
                                     float slope, float* out, size_t stride_b, size_t stride_c, size_t stride_n, void* stream);
+/* No reference counterpart: the global and head launches with bf16 matrix operands (FrozenPointNetPartseg(net, precision="bf16"),
+ * DESIGN.md section 23).  Arguments, checks, errors, workspaces and launch geometry of their fp32 counterparts, except that every
+ * W[l] is bf16 [C_l, C_{l-1}]: all layers, dense, 16-byte aligned, the head's last weight in whole 32-row blocks.  Every check runs
+ * before any HIP call.  The stn and trunk launches, pcl_pointnet_seg_rows_f32, F (fp32 [B*N, ldf]), TT, scale, shift and the
+ * biases stay fp32; pcl_pointnet_seg_infer_supported and the two _workspace_bytes queries answer for both precisions.  Numerics:
+ *   global: out3 is staged from F in fp32; x2 = out3 . T128[b] stays on the fp32 MFMA step with the chain of
+ *     pcl_pointnet_seg_global_infer_f32 (two run-time fp32 operands, 1.4 % of the FLOPs); x2 is rounded to nearest even to bf16;
+ *     conv4 = bf16 x bf16 products accumulated in fp32 (v_mfma_f32_32x32x16_bf16, k-blocks of 16 ascending), epilogue
+ *     act(scale * y + shift) in fp32; out4 goes to F[., 320:832] in fp32, unrounded, for the rows < n_b, and on to conv5 rounded to
+ *     bf16; conv5 likewise accumulated in fp32, its epilogue scale * y + shift in fp32 with no activation and never rounded; the
+ *     max, the partials and out are fp32.
+ *   head: every element of F[., 0:832] is rounded to nearest even to bf16 as it is staged (out4 becomes the value the global launch
+ *     multiplied); layer 1 is one fp32 accumulation per element over k-blocks of 16 ascending across the whole K = 832, then
+ *     + cloud_bias[b] and the epilogue in fp32; z1, z2, z3 are rounded to bf16; all four layers take bf16 operands, the last one
+ *     linear + bias_out in fp32; logits are fp32, never rounded, and exact zeros for pad points.
+ * A cloud's results depend only on its own valid points: the same bits for any B, position, capacity N, pad contents (NaN
+ * included) and run; no atomics. */
+int pcl_pointnet_seg_global_infer_bf16_f32(float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N, const float* TT,
+                                           int L, const int32_t* widths, const void* const* W, const float* const* scale,
+                                           const float* const* shift, float slope, void* workspace, size_t workspace_bytes,
+                                           float* out, int ldo, void* stream);
+/* No reference counterpart: the head launch of the comment above */
+int pcl_pointnet_seg_head_infer_bf16_f32(const float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N,
+                                         const float* cloud_bias, int ldb, int L, const int32_t* widths, const void* const* W,
+                                         int w_out_rows, const float* const* scale, const float* const* shift, const float* bias_out,
+                                         float slope, float* out, size_t stride_b, size_t stride_c, size_t stride_n, void* stream);
 /* No reference counterpart: y[r, c] = act(scale[c] * (x[r] . W[c]) + shift[c]) for the B-row tails (the T-Nets' fully connected
  * layers, the per-cloud bias): x [R, ldx], W [C, K] dense, K a multiple of 4 up to 2304, scale NULL = 1, slope 1 = no activation.
  * One wave per column, the rows in turn, one fixed summation order: a row's result does not depend on R. */

@@ -109,15 +109,19 @@ __device__ __forceinline__ void mfma_layer(const float* __restrict__ X, const fl
     mfma_layer_acc<K, LDX, NJ, NCB>(X, W, K, wave, lane, acc);
 }
 
-// acc[rb][j] = X[rb*32 + row][k] * W[(w + 4j)*32 + col][k] over k < K, bf16 products accumulated in fp32 (X in LDS with row
-// stride LDX elements, W [*, K] bf16 in global memory).  NRB row blocks of 32 (2: the 64-row tile; 4: a 128-row tile whose
-// weight pieces are loaded once for twice the rows); an element's sum is the same chain for every NRB.
-template <int K, int LDX, int NJ, int NCB, int NRB = 2>
-__device__ __forceinline__ void mfma_layer_bf16(const __bf16* __restrict__ X, const __bf16* __restrict__ W, int wave, int lane,
-                                                f32x16 (&acc)[NRB][NJ]) {
+// acc[rb][j] += X[rb*32 + row][k] * W[(w + 4j)*32 + col][k] over k < K, bf16 products accumulated in fp32; acc is NOT cleared.
+// X in LDS with row stride LDX elements; W bf16 with row stride ldw elements -- as for mfma_layer_acc the tile may hold columns
+// [k0, k0 + K) of a wider input, W then points at column k0 of a [*, ldw] matrix (16-byte aligned there, ldw a multiple of 8).
+// Chunks accumulated in ascending order give one fp32 accumulation per element over k-blocks of 16 ascending across the whole
+// width.  NRB row blocks of 32 (2: the 64-row tile; 4: a 128-row tile whose weight pieces are loaded once for twice the rows);
+// an element's sum is the same chain for every NRB.  UNROLL: k-blocks per trip of the loop (by default all of them: no loop); a
+// caller that runs the step inside a loop over column passes on an unchanged tile takes fewer, or the compiler lifts every read
+// of the tile out of that loop and into more registers than there are.
+template <int K, int LDX, int NJ, int NCB, int NRB = 2, int UNROLL = K / 16>
+__device__ __forceinline__ void mfma_layer_bf16_acc(const __bf16* __restrict__ X, const __bf16* __restrict__ W, int ldw, int wave,
+                                                    int lane, f32x16 (&acc)[NRB][NJ]) {
     static_assert(K % 16 == 0 && LDX % 8 == 0, "16-byte pieces");
     const int lr = lane & 31, lh = lane >> 5;
-    acc_clear(acc);
     const __bf16* xa[NRB];
 #pragma unroll
     for (int rb = 0; rb < NRB; ++rb) xa[rb] = X + (size_t)(rb * 32 + lr) * LDX + 8 * lh;
@@ -125,12 +129,12 @@ __device__ __forceinline__ void mfma_layer_bf16(const __bf16* __restrict__ X, co
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int cb = imax(0, wave + 4 * j < NCB ? wave + 4 * j : 0);
-        wb[j] = W + (size_t)(cb * 32 + lr) * K + 8 * lh;
+        wb[j] = W + (size_t)(cb * 32 + lr) * ldw + 8 * lh;
     }
     bf16x8 bn[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) bn[j] = *reinterpret_cast<const bf16x8*>(wb[j]);
-#pragma unroll
+#pragma unroll UNROLL
     for (int q = 0; q < K / 16; ++q) {
         bf16x8 b[NJ];
 #pragma unroll
@@ -150,6 +154,14 @@ __device__ __forceinline__ void mfma_layer_bf16(const __bf16* __restrict__ X, co
             }
         }
     }
+}
+
+// acc[rb][j] = X[rb*32 + row][k] * W[(w + 4j)*32 + col][k] over k < K (W [*, K] bf16 in global memory): the step above from zero
+template <int K, int LDX, int NJ, int NCB, int NRB = 2, int UNROLL = K / 16>
+__device__ __forceinline__ void mfma_layer_bf16(const __bf16* __restrict__ X, const __bf16* __restrict__ W, int wave, int lane,
+                                                f32x16 (&acc)[NRB][NJ]) {
+    acc_clear(acc);
+    mfma_layer_bf16_acc<K, LDX, NJ, NCB, NRB, UNROLL>(X, W, K, wave, lane, acc);
 }
 
 // four consecutive channels of one row into a tile: one 16-byte (fp32) or 8-byte (bf16, rounded to nearest even) store

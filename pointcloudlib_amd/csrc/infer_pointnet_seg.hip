@@ -24,6 +24,23 @@
 // layer is one fp32 chain per element in the k order of infer::mfma_layer (the K = 832 layer: its chunks in ascending order, the
 // same chain); epilogues are scale * y + shift (two roundings) and the leaky ReLU.  A cloud's results depend only on its own
 // valid rows: bit for bit the same for any B, any position in the batch, any capacity N, any pad contents and any run.
+//
+// The bf16 kernels (pcl_pointnet_seg_global_infer_bf16_f32 / seg_global_bf16_kernel, pcl_pointnet_seg_head_infer_bf16_f32 /
+// seg_head_bf16_kernel) keep the geometry of their fp32 counterparts with the wide layers on
+// v_mfma_f32_32x32x16_bf16 (infer::mfma_layer_bf16).  stn, trunk, the B-row tails, the tile max, the layout of F (fp32
+// [B*N, ldf]) and every scale, shift and bias stay fp32.  Numerics contract:
+//   global: out3 is staged from F in fp32; x2 = out3 . T128[b] stays on the fp32 MFMA step (both operands are run-time fp32 data;
+//           1.4 % of the launch's FLOPs) with the fp32 kernel's chain; x2 is rounded to nearest even to bf16; conv4 is bf16 x bf16
+//           accumulated in fp32, k-blocks of 16 ascending, its epilogue act(scale * y + shift) in fp32; out4 goes to F[., 320:832]
+//           in fp32, unrounded, for the rows < n_b, and to the LDS tile rounded to bf16; conv5 is bf16 x bf16 accumulated in fp32,
+//           its epilogue scale * y + shift in fp32 with no activation and never rounded; the max, the partials and out are fp32.
+//   head:   every staged element of F is rounded to bf16 as it enters LDS (the out4 the head multiplies is the value the global
+//           kernel multiplied); layer 1 takes its K-chunks in ascending order: one fp32 accumulation per element over k-blocks of
+//           16 ascending across the whole K = 832, then + bias[b] and the epilogue in fp32; z_1, z_2, z_3 are rounded to bf16; all
+//           four layers run on bf16 operands, the last one linear + bias_out in fp32; logits are fp32 and never rounded; logits of
+//           pad points are exact zeros, also in tiles that do nothing else.
+// Weights are bf16, rounded once by the caller (the folded K = 832 weight straight from fp64).  A cloud's results depend only on
+// its own valid rows: the same bits for any B, position, capacity N, pad contents (NaN included) and run; no atomics.
 #include "common.h"
 #include "infer_mfma.h"
 
@@ -237,6 +254,176 @@ __global__ __launch_bounds__(NT, 2) void seg_head_kernel(const SegHeadArgs a) {
             ob[(size_t)c * a.oc + (size_t)(row0 + lane) * a.on] = lane < nrows ? Y[lane * SG_LDH + c] : 0.f;
 }
 
+// ------------------------------------------------------------------------------------------------------- the bf16 kernels
+// pcl_pointnet_seg_global_infer_bf16_f32 and pcl_pointnet_seg_head_infer_bf16_f32 (header comment): the geometry of the fp32
+// kernels above -- one workgroup per 64-row tile of one cloud, tile-major, the early exit, partials in the never-cleared workspace,
+// the same second launch -- on infer::mfma_layer_bf16, with [64][K + 8] bf16 tiles.
+constexpr int SG16_LD128 = 128 + row_pad<__bf16>;  // row stride of a 128-wide bf16 tile (x2, the head's K-chunks)
+constexpr int SG16_LD4 = 512 + row_pad<__bf16>;    // ... of the 512-wide out4 tile
+constexpr int SG16_LDH = 256 + row_pad<__bf16>;    // ... of the head's 256-wide tile
+constexpr size_t SG16_LDS_GLOBAL = 2 * (size_t)RT * SG16_LD4;            // 66 560 B: two workgroups per CU
+constexpr size_t SG16_LDS_HEAD = 2 * (size_t)2 * RT * SG16_LD128;        // 34 816 B: the two chunk buffers; the tiles lie over them
+static_assert(4 * (size_t)RT * LD128 + 2 * (size_t)RT * SG16_LD128 <= SG16_LDS_GLOBAL, "fp32 out3 and bf16 x2 lie inside the out4 tile");
+static_assert(2 * (size_t)RT * SG16_LDH <= SG16_LDS_HEAD && 4 * (size_t)RT * LD128 <= SG16_LDS_HEAD,
+              "the head's bf16 tile and its fp32 logits lie over the chunk buffers");
+
+// seg_layer on bf16 operands: Y = bf16(z), z = act(scale * (X W^T) + shift) in fp32; G takes z itself, unrounded
+template <int K, int LDX, int CO, int LDY, bool INPLACE>
+__device__ __forceinline__ void seg_layer_bf16(const __bf16* X, const __bf16* __restrict__ W, const float* __restrict__ scl,
+                                               const float* __restrict__ shf, float slope, __bf16* Y, float* __restrict__ G, int ldg,
+                                               int nrows, int wave, int lane) {
+    constexpr int NCB = CO / 32, NJ = (NCB + 3) / 4;
+    const int lr = lane & 31, lh = lane >> 5;
+    f32x16 acc[2][NJ];
+    mfma_layer_bf16<K, LDX, NJ, NCB>(X, W, wave, lane, acc);
+    if (INPLACE) __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int cb = wave + 4 * j;
+        if (cb < NCB) {
+            const int col = cb * 32 + lr;
+            const float sc = scl[col], sh = shf[col];
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = acc_row(rb, r, lh);
+                    const float z = act(sc * acc[rb][j][r] + sh, slope);
+                    Y[row * LDY + col] = (__bf16)z;
+                    if (G && row < nrows) G[(size_t)row * ldg + col] = z;
+                }
+        }
+    }
+}
+
+// columns [k0, k0 + kw) of the tile's rows of F, rounded to bf16 -> buf [RT][SG16_LD128]
+__device__ __forceinline__ void seg_stage_bf16(const float* __restrict__ Fb, int ldf, int N, int row0, int k0, int kw, __bf16* buf, int tid) {
+    const int per = kw / 4;
+    for (int i = tid; i < RT * per; i += NT) {
+        const int r = i / per, c4 = (i - r * per) * 4;
+        const float4 v = *reinterpret_cast<const float4*>(Fb + (size_t)min(row0 + r, N - 1) * ldf + k0 + c4);
+        const float z[4] = {v.x, v.y, v.z, v.w};
+        tile_store4(buf + r * SG16_LD128 + c4, z);
+    }
+}
+
+// a.W[l] point at bf16
+__global__ __launch_bounds__(NT, 2) void seg_global_bf16_kernel(const SegGlobalArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __bf16* X4 = reinterpret_cast<__bf16*>(smem);  // [RT][SG16_LD4]: out4; before it exists, out3 (fp32) and x2 lie inside
+    float* X1 = smem;                              // [RT][LD128] fp32
+    __bf16* X2 = reinterpret_cast<__bf16*>(smem + RT * LD128);      // [RT][SG16_LD128]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+    const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
+    if (tile.empty()) return;
+    const int b = tile.b, t = tile.t, row0 = tile.row0, nrows = tile.nrows;
+    const float* Fb = a.F + (size_t)b * a.N * a.ldf;
+    seg_stage(Fb, a.ldf, a.N, row0, SG_F3, SG_C3, X1, tid);
+    __syncthreads();
+    {   // x2 = out3 . T128[b]: the fp32 kernel's step and chain, rounded into X2
+        f32x16 acc[2][1];
+        mfma_layer<SG_C3, LD128, 1, SG_C3 / 32>(X1, a.TT + (size_t)b * SG_C3 * SG_C3, wave, lane, acc);
+        const int col = wave * 32 + lr;
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) X2[acc_row(rb, r, lh) * SG16_LD128 + col] = (__bf16)acc[rb][0][r];
+    }
+    __syncthreads();
+    float* Fr = a.F + ((size_t)b * a.N + row0) * a.ldf;
+    seg_layer_bf16<SG_C3, SG16_LD128, SG_C4, SG16_LD4, true>(X2, reinterpret_cast<const __bf16*>(a.W[0]), a.scl[0], a.shf[0], a.slope, X4,
+                                                             Fr + SG_F4, a.ldf, nrows, wave, lane);
+    __syncthreads();
+    // conv5 under the max, as infer::max_passes without the activation
+    const __bf16* W5 = reinterpret_cast<const __bf16*>(a.W[1]);
+    float* part = a.part + ((size_t)b * a.tpc + t) * SG_C5;
+    for (int c0 = 0; c0 < SG_C5; c0 += MAX_PASS) {
+        f32x16 acc[2][MAX_NJ];
+        mfma_layer_bf16<SG_C4, SG16_LD4, MAX_NJ, 4 * MAX_NJ, 2, 8>(X4, W5 + (size_t)c0 * SG_C4, wave, lane, acc);
+#pragma unroll
+        for (int j = 0; j < MAX_NJ; ++j) {
+            const int col = c0 + (wave + 4 * j) * 32 + lr;
+            const float sc = a.scl[1][col], sh = a.shf[1][col];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, acc_row(rb, r, lh) < nrows ? sc * acc[rb][j][r] + sh : -INFINITY);
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            if (lh == 0) part[col] = mx;
+        }
+    }
+}
+
+// a.W[l] point at bf16
+__global__ __launch_bounds__(NT, 2) void seg_head_bf16_kernel(const SegHeadArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __bf16* S = reinterpret_cast<__bf16*>(smem);   // the two chunk buffers [RT][SG16_LD128]
+    __bf16* Y = S;                                 // [RT][SG16_LDH], over them once layer 1 has read them
+    float* Yf = smem;                              // [RT][LD128] fp32: the logits on their way to the transposed store
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+    const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
+    const int b = tile.b, row0 = tile.row0, nrows = tile.nrows;
+    float* ob = a.out + (size_t)b * a.ob;
+    if (tile.empty()) {                               // a tile of pad rows only: its logits are zeros; nothing is loaded
+        if (row0 + lane < a.N)
+            for (int c = wave; c < a.part_num; c += 4) ob[(size_t)c * a.oc + (size_t)(row0 + lane) * a.on] = 0.f;
+        return;
+    }
+    const float* Fb = a.F + (size_t)b * a.N * a.ldf;
+    const __bf16* W1 = reinterpret_cast<const __bf16*>(a.W[0]);
+    // layer 1: the fp32 kernel's chunk schedule; every element of F is rounded as it enters LDS
+    constexpr int NFULL = SG_FK / SG_CHUNK, REST = SG_FK - NFULL * SG_CHUNK;
+    static_assert(REST == 64 && NFULL % 2 == 0, "the chunk schedule below");
+    constexpr int NJ = SG_H1 / 32 / 4;
+    f32x16 acc[2][NJ];
+    acc_clear(acc);
+    seg_stage_bf16(Fb, a.ldf, a.N, row0, 0, SG_CHUNK, S, tid);
+    __syncthreads();
+    for (int c = 0; c < NFULL; ++c) {
+        const __bf16* cur = S + (c & 1) * RT * SG16_LD128;
+        __bf16* nxt = S + ((c + 1) & 1) * RT * SG16_LD128;
+        seg_stage_bf16(Fb, a.ldf, a.N, row0, (c + 1) * SG_CHUNK, c + 1 < NFULL ? SG_CHUNK : REST, nxt, tid);
+        mfma_layer_bf16_acc<SG_CHUNK, SG16_LD128, NJ, SG_H1 / 32>(cur, W1 + c * SG_CHUNK, SG_FK, wave, lane, acc);
+        __syncthreads();
+    }
+    mfma_layer_bf16_acc<REST, SG16_LD128, NJ, SG_H1 / 32>(S, W1 + NFULL * SG_CHUNK, SG_FK, wave, lane, acc);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int col = (wave + 4 * j) * 32 + lr;
+        const float sc = a.scl[0][col], sh = a.shf[0][col], cb = a.bias[(size_t)b * a.ldb + col];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) Y[acc_row(rb, r, lh) * SG16_LDH + col] = (__bf16)act(sc * (acc[rb][j][r] + cb) + sh, a.slope);
+    }
+    __syncthreads();
+    seg_layer_bf16<SG_H1, SG16_LDH, SG_H2, SG16_LDH, true>(Y, reinterpret_cast<const __bf16*>(a.W[1]), a.scl[1], a.shf[1], a.slope, Y, nullptr,
+                                                           0, nrows, wave, lane);
+    __syncthreads();
+    seg_layer_bf16<SG_H2, SG16_LDH, SG_H3, SG16_LDH, true>(Y, reinterpret_cast<const __bf16*>(a.W[2]), a.scl[2], a.shf[2], a.slope, Y, nullptr,
+                                                           0, nrows, wave, lane);
+    __syncthreads();
+    // layer 4: linear + bias in fp32 on the column blocks that hold a part; the logits are never rounded
+    const int ncb = (a.part_num + 31) / 32;
+    f32x16 lo[2][1];
+    if (wave < ncb) mfma_layer_bf16<SG_H3, SG16_LDH, 1, 4>(Y, reinterpret_cast<const __bf16*>(a.W[3]), wave, lane, lo);
+    __syncthreads();
+    if (wave < ncb) {
+        const int col = wave * 32 + lr;
+        const float bo = col < a.part_num ? a.bout[col] : 0.f;
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) Yf[acc_row(rb, r, lh) * LD128 + col] = lo[rb][0][r] + bo;
+    }
+    __syncthreads();
+    if (row0 + lane < a.N)
+        for (int c = wave; c < a.part_num; c += 4)
+            ob[(size_t)c * a.oc + (size_t)(row0 + lane) * a.on] = lane < nrows ? Yf[lane * LD128 + c] : 0.f;
+}
+
 // ------------------------------------------------------------------------------------------------------- B-row tails
 // y[r][c] = act(scale[c] * (x[r] . W[c]) + shift[c]) (scale null: 1): one wave per column with its weight row in registers, the
 // rows four at a time (a row beyond R repeats row R - 1 and is not stored).  Lane l sums its k = 4 (l + 64 i) + e in ascending (i, e), then the lanes are summed by halving: a value does not
@@ -409,11 +596,14 @@ extern "C" int pcl_pointnet_seg_trunk_infer_f32(const float* x, size_t stride_b,
     return check_launch(who);
 }
 
-extern "C" int pcl_pointnet_seg_global_infer_f32(float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N, const float* TT,
-                                                 int L, const int32_t* widths, const float* const* W, const float* const* scale,
-                                                 const float* const* shift, float slope, void* workspace, size_t workspace_bytes,
-                                                 float* out, int ldo, void* stream) {
-    const char* who = "pcl_pointnet_seg_global_infer_f32";
+namespace {
+
+// both precisions of a launch: every check runs before any HIP call.  W[l]: fp32 (BF16 false) or bf16 (true) [C_l][C_{l-1}];
+// aligned: the entry's answer to whether every W[l] (and TT) is 16-byte aligned, reported here in its place among the checks
+template <bool BF16>
+int seg_global_infer(const char* who, float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N, const float* TT, int L,
+                     const int32_t* widths, const void* const* W, const float* const* scale, const float* const* shift, float slope,
+                     void* workspace, size_t workspace_bytes, float* out, int ldo, bool aligned, void* stream) {
     PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", who);
     PCL_REQUIRE(seg_shape_ok(PCL_SEG_GLOBAL, SG_C3, L, widths), "%s: no kernel for these widths (pcl_pointnet_seg_infer_supported)", who);
     PCL_REQUIRE(TT && out, "%s: null pointer (TT or out)", who);
@@ -422,27 +612,29 @@ extern "C" int pcl_pointnet_seg_global_infer_f32(float* F, int ldf, size_t f_byt
     for (int l = 0; l < 2; ++l) PCL_REQUIRE(scale[l] && shift[l] && W[l], "%s: layer %d: null pointer", who, l);
     if (int rc = seg_rows_ok(who, F, ldf, f_bytes, B, N)) return rc;
     if (int rc = seg_part_ok(who, workspace, workspace_bytes, B, N, SG_C5)) return rc;
-    PCL_REQUIRE(al16(TT, W[0], W[1]), "%s: TT and the weights must be 16-byte aligned", who);
+    PCL_REQUIRE(aligned, "%s: TT and the weights must be 16-byte aligned", who);
     SegGlobalArgs a = {};
     a.F = F; a.ldf = ldf;
     a.n_valid = n_valid; a.B = B; a.N = N; a.tpc = tiles_of(N);
     a.TT = TT;
-    for (int l = 0; l < 2; ++l) { a.W[l] = W[l]; a.scl[l] = scale[l]; a.shf[l] = shift[l]; }
+    for (int l = 0; l < 2; ++l) { a.W[l] = static_cast<const float*>(W[l]); a.scl[l] = scale[l]; a.shf[l] = shift[l]; }
     a.slope = slope;
     a.part = static_cast<float*>(workspace);
     hipStream_t st = as_stream(stream);
-    if (int rc = lds_opt_in(seg_global_kernel, SG_LDS_GLOBAL, who)) return rc;
-    hipLaunchKernelGGL(seg_global_kernel, dim3(B * a.tpc), dim3(NT), SG_LDS_GLOBAL, st, a);
+    auto kern = BF16 ? seg_global_bf16_kernel : seg_global_kernel;
+    const size_t lds = BF16 ? SG16_LDS_GLOBAL : SG_LDS_GLOBAL;
+    if (int rc = lds_opt_in(kern, lds, who)) return rc;
+    hipLaunchKernelGGL(kern, dim3(B * a.tpc), dim3(NT), lds, st, a);
     if (int rc = check_launch(who)) return rc;
     hipLaunchKernelGGL(tile_max_kernel<SG_C5>, dim3(B, SG_C5 / NT), dim3(NT), 0, st, a.part, n_valid, N, a.tpc, out, ldo);
     return check_launch(who);
 }
 
-extern "C" int pcl_pointnet_seg_head_infer_f32(const float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N,
-                                               const float* cloud_bias, int ldb, int L, const int32_t* widths, const float* const* W,
-                                               int w_out_rows, const float* const* scale, const float* const* shift, const float* bias_out,
-                                               float slope, float* out, size_t stride_b, size_t stride_c, size_t stride_n, void* stream) {
-    const char* who = "pcl_pointnet_seg_head_infer_f32";
+template <bool BF16>
+int seg_head_infer(const char* who, const float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N, const float* cloud_bias,
+                   int ldb, int L, const int32_t* widths, const void* const* W, int w_out_rows, const float* const* scale,
+                   const float* const* shift, const float* bias_out, float slope, float* out, size_t stride_b, size_t stride_c,
+                   size_t stride_n, bool aligned, void* stream) {
     PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", who);
     PCL_REQUIRE(seg_shape_ok(PCL_SEG_HEAD, SG_FK, L, widths), "%s: no kernel for these widths (pcl_pointnet_seg_infer_supported)", who);
     const int part_num = widths[3];
@@ -453,20 +645,59 @@ extern "C" int pcl_pointnet_seg_head_infer_f32(const float* F, int ldf, size_t f
                 (part_num + 31) / 32 * 32, w_out_rows);
     for (int l = 0; l < 4; ++l) PCL_REQUIRE(W[l] && (l == 3 || (scale[l] && shift[l])), "%s: layer %d: null pointer", who, l);
     if (int rc = seg_rows_ok(who, F, ldf, f_bytes, B, N)) return rc;
-    PCL_REQUIRE(al16(W[0], W[1], W[2], W[3]), "%s: the weights must be 16-byte aligned", who);
+    PCL_REQUIRE(aligned, "%s: the weights must be 16-byte aligned", who);
     SegHeadArgs a = {};
     a.F = F; a.ldf = ldf;
     a.n_valid = n_valid; a.B = B; a.N = N; a.tpc = tiles_of(N);
     a.bias = cloud_bias; a.ldb = ldb;
-    for (int l = 0; l < 4; ++l) a.W[l] = W[l];
+    for (int l = 0; l < 4; ++l) a.W[l] = static_cast<const float*>(W[l]);
     for (int l = 0; l < 3; ++l) { a.scl[l] = scale[l]; a.shf[l] = shift[l]; }
     a.bout = bias_out; a.part_num = part_num;
     a.slope = slope;
     a.out = out; a.ob = stride_b; a.oc = stride_c; a.on = stride_n;
     hipStream_t st = as_stream(stream);
-    if (int rc = lds_opt_in(seg_head_kernel, SG_LDS_HEAD, who)) return rc;
-    hipLaunchKernelGGL(seg_head_kernel, dim3(B * a.tpc), dim3(NT), SG_LDS_HEAD, st, a);
+    auto kern = BF16 ? seg_head_bf16_kernel : seg_head_kernel;
+    const size_t lds = BF16 ? SG16_LDS_HEAD : SG_LDS_HEAD;
+    if (int rc = lds_opt_in(kern, lds, who)) return rc;
+    hipLaunchKernelGGL(kern, dim3(B * a.tpc), dim3(NT), lds, st, a);
     return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int pcl_pointnet_seg_global_infer_f32(float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N, const float* TT,
+                                                 int L, const int32_t* widths, const float* const* W, const float* const* scale,
+                                                 const float* const* shift, float slope, void* workspace, size_t workspace_bytes,
+                                                 float* out, int ldo, void* stream) {
+    return seg_global_infer<false>("pcl_pointnet_seg_global_infer_f32", F, ldf, f_bytes, n_valid, B, N, TT, L, widths,
+                                   reinterpret_cast<const void* const*>(W), scale, shift, slope, workspace, workspace_bytes, out, ldo,
+                                   W && L == 2 && al16(TT, W[0], W[1]), stream);
+}
+
+extern "C" int pcl_pointnet_seg_global_infer_bf16_f32(float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N,
+                                                      const float* TT, int L, const int32_t* widths, const void* const* W,
+                                                      const float* const* scale, const float* const* shift, float slope, void* workspace,
+                                                      size_t workspace_bytes, float* out, int ldo, void* stream) {
+    return seg_global_infer<true>("pcl_pointnet_seg_global_infer_bf16_f32", F, ldf, f_bytes, n_valid, B, N, TT, L, widths, W, scale, shift,
+                                  slope, workspace, workspace_bytes, out, ldo, L == 2 && all16(W, 2, TT), stream);
+}
+
+extern "C" int pcl_pointnet_seg_head_infer_f32(const float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N,
+                                               const float* cloud_bias, int ldb, int L, const int32_t* widths, const float* const* W,
+                                               int w_out_rows, const float* const* scale, const float* const* shift, const float* bias_out,
+                                               float slope, float* out, size_t stride_b, size_t stride_c, size_t stride_n, void* stream) {
+    return seg_head_infer<false>("pcl_pointnet_seg_head_infer_f32", F, ldf, f_bytes, n_valid, B, N, cloud_bias, ldb, L, widths,
+                                 reinterpret_cast<const void* const*>(W), w_out_rows, scale, shift, bias_out, slope, out, stride_b, stride_c,
+                                 stride_n, W && L == 4 && al16(W[0], W[1], W[2], W[3]), stream);
+}
+
+extern "C" int pcl_pointnet_seg_head_infer_bf16_f32(const float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N,
+                                                    const float* cloud_bias, int ldb, int L, const int32_t* widths, const void* const* W,
+                                                    int w_out_rows, const float* const* scale, const float* const* shift,
+                                                    const float* bias_out, float slope, float* out, size_t stride_b, size_t stride_c,
+                                                    size_t stride_n, void* stream) {
+    return seg_head_infer<true>("pcl_pointnet_seg_head_infer_bf16_f32", F, ldf, f_bytes, n_valid, B, N, cloud_bias, ldb, L, widths, W,
+                                w_out_rows, scale, shift, bias_out, slope, out, stride_b, stride_c, stride_n, L == 4 && all16(W, 4), stream);
 }
 
 extern "C" int pcl_pointnet_seg_rows_f32(const float* x, int ldx, int R, int K, const float* W, int C, const float* scale,

@@ -30,7 +30,10 @@ fp32.
 ``FrozenPointNetPartseg(net)`` is the same for ``networks.seg.pointnet_partseg.PointNet_partseg`` (csrc/infer_pointnet_seg.hip,
 DESIGN.md section 20): ``conv5`` has no activation, so the head's 4944-wide first layer folds to 832 columns on a row buffer
 ``out1 | out2 | out3 | out4`` plus a per-cloud bias (``fold_partseg_head``); neither the concatenation nor ``out5`` is ever
-stored."""
+stored.  ``FrozenPointNetPartseg(net, precision="bf16")`` runs the two wide launches as ``pcl_pointnet_seg_global_infer_bf16_f32``
+and ``pcl_pointnet_seg_head_infer_bf16_f32``: conv4, conv5 and the head's four layers take bf16 operands (activations rounded to
+nearest even, every weight snapshot as bf16 in ``refresh()``) and accumulate in fp32; the T-Nets, the trunk, the product with
+``T128``, the row buffer, the epilogues, the max, the per-cloud bias and the logits stay fp32."""
 import copy
 import ctypes
 
@@ -104,9 +107,11 @@ class _SegStack:
     ``first``: what stands for the first weight -- by default a clone of the layer's own; ``None`` when the first layer is
     folded and the kernel takes it apart from the arrays; or a tensor that replaces it.  ``bf16``: also ``Ws_bf16``, the weights
     of layers 2 and up rounded once to bf16 (``[None, ...]``), and ``c_W`` points at those.  ``pad_last``: the last layer's
-    weight, scale and shift padded to a multiple of 32 rows (zero weights); ``widths`` keeps the layer's own."""
+    weight, scale and shift padded to a multiple of 32 rows (zero weights); ``widths`` keeps the layer's own.  ``bf16_first``
+    (with ``bf16``): ALL layers as bf16 -- ``_OWN`` rounds the first layer's own weight like the others, a bf16 tensor stands
+    for it (a folded weight its caller rounded straight from fp64); by default the first entry stays ``None``."""
 
-    def __init__(self, layers, first=_OWN, bf16=False, pad_last=False):
+    def __init__(self, layers, first=_OWN, bf16=False, pad_last=False, bf16_first=None):
         self.L = L = len(layers)
         self.widths = [mlp.weights[l].shape[0] for mlp, l in layers]
         self.Ws, self.scales, self.shifts = [], [], []
@@ -121,6 +126,8 @@ class _SegStack:
         operands = self.Ws
         if bf16:                                                       # the bf16 operands of layers 2 and up, rounded once here
             operands = self.Ws_bf16 = [None] + [w.to(torch.bfloat16).contiguous() for w in self.Ws[1:]]
+            if bf16_first is not None:
+                operands[0] = self.Ws[0].to(torch.bfloat16).contiguous() if bf16_first is _OWN else bf16_first
         self.c_widths = (ctypes.c_int32 * L)(*self.widths)
         self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in operands])
         self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
@@ -551,11 +558,19 @@ def fold_partseg_head(Wh, W5, s5, t5, dtype=torch.float32):
         Wh . concat = Wrow . [out1|out2|out3|out4] + Wglob . [out_max|label] + c0,
         Wrow = [Wh_1 | Wh_2 | Wh_3 | Wh_4 + Wh_5 diag(s5) W5],  c0 = Wh_5 t5,  Wglob = [Wh_g | Wh_label].
 
-    Formed in fp64 and rounded once to ``dtype``; plain torch, any device."""
+    Formed in fp64 and rounded once to ``dtype``; plain torch, any device.  ``torch.bfloat16`` too is one rounding: torch casts
+    fp64 to bf16 through fp32, which rounds twice, so the nearest bf16 value (ties to even) is taken in fp64 first."""
     g, lab, o1, o2, o3, o4, o5 = Wh.detach().double().split(list(PARTSEG_CONCAT), dim=1)
     W5, s5, t5 = W5.detach().double(), s5.detach().double(), t5.detach().double()
     Wrow = torch.cat([o1, o2, o3, o4 + (o5 * s5) @ W5], dim=1)
-    return Wrow.to(dtype).contiguous(), torch.cat([g, lab], dim=1).to(dtype).contiguous(), (o5 @ t5).to(dtype).contiguous()
+
+    def once(t):
+        if dtype is torch.bfloat16:
+            m, e = torch.frexp(t)                          # t = m * 2^e, 0.5 <= |m| < 1: 8 significant bits = round(m * 256)
+            t = torch.ldexp(torch.round(m * 256.0), e - 8)
+        return t.to(dtype).contiguous()
+
+    return once(Wrow), once(torch.cat([g, lab], dim=1)), once(o5 @ t5)
 
 
 def transposed_fc3(weight, bias, k):
@@ -589,15 +604,24 @@ class FrozenPointNetPartseg:
     and the transposed ``fstn.fc3`` (``transposed_fc3``) are snapshot once, and a forward is the four launches of
     csrc/infer_pointnet_seg.hip with the B-row tails between them.  Anything else gives ``"module"``: an eval-mode copy of the
     whole network runs (``forward``; ragged ``forward_packed`` scattered into zeros).  ``refresh()`` re-reads weights and running
-    statistics; ``net`` itself is never modified.  Constructed directly: ``frozen()`` keeps its PointNet++ dispatch."""
+    statistics; ``net`` itself is never modified.  Constructed directly: ``frozen()`` keeps its PointNet++ dispatch.
+
+    ``precision``: "fp32", or "bf16" for bf16 matrix operands in the global and head launches (module docstring, DESIGN.md
+    section 23; ``fnet.precision`` tells which): every weight of the two launches is snapshot as bf16 in ``refresh()``, the folded
+    ``Wrow`` rounded once straight from fp64.  The two T-Net launches, the trunk, the B-row tails, ``T3``, ``T128``, the row buffer
+    and the per-cloud bias stay fp32, a forward allocates what the fp32 forward does, and a ``"module"`` plan ignores the
+    precision and stays fp32."""
 
     N_LABEL = 16
     LDF = 832                      # row stride of the row buffer out1 | out2 | out3 | out4
 
-    def __init__(self, net):
+    def __init__(self, net, precision="fp32"):
         if not isinstance(net, PointNet_partseg):
             raise TypeError(f"FrozenPointNetPartseg takes networks.seg.pointnet_partseg.PointNet_partseg, got {type(net).__name__}")
+        if precision not in PRECISIONS:
+            raise ValueError(f"FrozenPointNetPartseg: precision must be one of {PRECISIONS}, got {precision!r}")
         self.net = net
+        self.precision = precision
         self._module = None
         self.refresh()
 
@@ -647,7 +671,8 @@ class FrozenPointNetPartseg:
         self.stn = _SegStack([(net.stn.convs, l) for l in range(3)])
         self.trunk = _SegStack([(net.conv1, 0), (net.conv2, 0), (net.conv3, 0)])
         self.fstn = _SegStack([(net.fstn.convs, l) for l in range(3)])
-        self.glob = _SegStack([(net.conv4, 0), (net.conv5, 0)])
+        bf16 = self.precision == "bf16"                  # the global and head launches then take bf16 operands, all layers
+        self.glob = _SegStack([(net.conv4, 0), (net.conv5, 0)], bf16=bf16, bf16_first=_OWN if bf16 else None)
         k3 = net.stn.k
         eye3 = torch.eye(k3, device=net.stn.fc3.bias.device, dtype=net.stn.fc3.bias.dtype).reshape(-1)
         self.stn_tail = self._tail(net.stn, (net.stn.fc3.weight.detach(), net.stn.fc3.bias.detach() + eye3))
@@ -658,10 +683,19 @@ class FrozenPointNetPartseg:
         Wout = torch.zeros((rows, net.convs4.in_features), dtype=torch.float32, device=Wrow.device)
         Wout[:self.part_num] = net.convs4.weight.detach()
         self.bias_out = net.convs4.bias.detach().float().contiguous().clone()
-        self.head = _SegStack([(net.convs, l) for l in range(3)], first=Wrow)
+        Wrow16 = None
+        if bf16:                                         # fp64 -> bf16 in one rounding, not through the fp32 Wrow
+            Wrow16 = fold_partseg_head(net.convs.weights[0], net.conv5.weights[0], s5, t5, dtype=torch.bfloat16)[0]
+        self.head = _SegStack([(net.convs, l) for l in range(3)], first=Wrow, bf16=bf16, bf16_first=Wrow16)
         self.Wout = Wout
         self.head_widths = (ctypes.c_int32 * 4)(*self.head.widths, self.part_num)
-        self.head_W = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in self.head.Ws], Wout.data_ptr())
+        operands = self.head.Ws + [Wout]
+        if bf16:
+            self.Wout_bf16 = Wout.to(torch.bfloat16).contiguous()
+            operands = self.head.Ws_bf16 + [self.Wout_bf16]
+        self.head_W = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in operands])
+        self.global_entry = "pcl_pointnet_seg_global_infer_bf16_f32" if bf16 else "pcl_pointnet_seg_global_infer_f32"
+        self.head_entry = "pcl_pointnet_seg_head_infer_bf16_f32" if bf16 else "pcl_pointnet_seg_head_infer_f32"
         return self
 
     def __call__(self, point_cloud, label, lengths=None):
@@ -714,12 +748,12 @@ class FrozenPointNetPartseg:
         c = self.glob
         glob = torch.empty((B, 2048 + self.N_LABEL), dtype=torch.float32, device=dev)      # out_max | label
         glob[:, 2048:] = label
-        _lib.call("pcl_pointnet_seg_global_infer_f32", _p(F), self.LDF, f_bytes, _p(lengths), B, N, _p(TT), c.L, c.c_widths, c.c_W,
+        _lib.call(self.global_entry, _p(F), self.LDF, f_bytes, _p(lengths), B, N, _p(TT), c.L, c.c_widths, c.c_W,
                   c.c_scale, c.c_shift, self.slope, _p(ws), ws_bytes, _p(glob), glob.stride(0), st)
         bias = _seg_rows(glob, self.Wglob, None, self.c0, 1.0)
         h = self.head
         out = torch.empty((B, self.part_num, N), dtype=torch.float32, device=dev)
-        _lib.call("pcl_pointnet_seg_head_infer_f32", _p(F), self.LDF, f_bytes, _p(lengths), B, N, _p(bias), bias.stride(0), 4,
+        _lib.call(self.head_entry, _p(F), self.LDF, f_bytes, _p(lengths), B, N, _p(bias), bias.stride(0), 4,
                   self.head_widths, self.head_W, self.Wout.shape[0], h.c_scale, h.c_shift, _p(self.bias_out), self.slope, _p(out),
                   out.stride(0), out.stride(1), out.stride(2), st)
         return T3.view(B, 3, 3), TT.view(B, 128, 128).transpose(1, 2), glob[:, :2048], out

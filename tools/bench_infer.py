@@ -24,7 +24,10 @@ both precisions (``*_err_fp64_*``); the line goes to profiles/infer_pointnet_bf1
 ``--nets pointnet_partseg`` compares ``net.eval()`` under ``no_grad`` with ``FrozenPointNetPartseg(net)`` (B in {16, 64}, N = 2048;
 both forms read the same dense [B,3,N] tensor and the same one-hot label) with the peak memory of both, and writes the JSON line
 to profiles/infer_pointnet_partseg_bench_line.json; with ``--ragged`` the four forms below
-(profiles/infer_pointnet_partseg_ragged_bench_line.json).
+(profiles/infer_pointnet_partseg_ragged_bench_line.json).  With ``--precision fp32 bf16`` every row also carries
+``FrozenPointNetPartseg(net, precision="bf16")`` (``frozen_bf16_ms``, ``bf16_vs_fp32``, ``bf16_below_fp32_min``, the max-abs logit
+distance and the per-point top-1 agreement of the two precisions); the line goes to
+profiles/infer_pointnet_partseg_bf16_bench_line.json instead.
 
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
@@ -193,6 +196,11 @@ def main():
             def fnet(xyz, nrm, onehot, lengths=None):         # the tool's call shape; [B,N,3] read through a transposed view
                 return fps(xyz.transpose(1, 2), onehot, lengths)
             fnet_bf16 = None
+            if "bf16" in a.precision:
+                fps16 = FrozenPointNetPartseg(net, precision="bf16")
+
+                def fnet_bf16(xyz, nrm, onehot, lengths=None):
+                    return fps16(xyz.transpose(1, 2), onehot, lengths)
         else:
             fnet = frozen(net)
             fnet_bf16 = frozen(net, precision="bf16") if "bf16" in a.precision else None
@@ -237,6 +245,9 @@ def main():
 
                 def frozen_fwd():
                     return fps(x_cf, onehot)
+
+                def frozen_bf16_fwd():
+                    return fps16(x_cf, onehot)
 
             if a.ragged:
                 res["cases"].append(_ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16))
@@ -286,9 +297,11 @@ def main():
                     case["top1_agreement_bf16_fp64"] = float((lb.argmax(1) == l64.argmax(1)).float().mean())
             res["cases"].append(case)
     print(json.dumps(res))
-    if "bf16" in a.precision and not a.ragged and not (pointnet_only and a.frozen_only):
+    if "bf16" in a.precision and not a.ragged and not ((pointnet_only or pn_partseg_only) and a.frozen_only):
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-        with open(os.path.join(ROOT, "profiles", "infer_pointnet_bf16_bench_line.json" if pointnet_only else "infer_bf16_bench_line.json"), "w") as f:
+        name = ("infer_pointnet_bf16_bench_line.json" if pointnet_only else
+                "infer_pointnet_partseg_bf16_bench_line.json" if pn_partseg_only else "infer_bf16_bench_line.json")
+        with open(os.path.join(ROOT, "profiles", name), "w") as f:
             f.write(json.dumps(res) + "\n")
     elif pointnet_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
