@@ -98,12 +98,6 @@ inline int lds_opt_in(K* kernel, size_t bytes, const char* who) {
 // May a kernel move 16-byte pieces of these operands?  True when every pointer given is 16-byte aligned; null counts as aligned.
 template <class... T>
 inline bool al16(const T*... p) { return ((uintptr_t(0) | ... | reinterpret_cast<uintptr_t>(p)) & 15) == 0; }
-// The same question of a host array of n device pointers (a launcher's W[l]) and one more pointer; a null array counts as not aligned.
-inline bool all16(const void* const* p, int n, const void* also = nullptr) {
-    bool ok = p != nullptr && al16(also);
-    for (int i = 0; ok && i < n; ++i) ok = al16(p[i]);
-    return ok;
-}
 
 // XCD-aware logical block id for a 1-D grid whose consecutive blocks walk the clouds one after another (`bpc` blocks per
 // cloud, nblk = clouds * bpc).  The hardware deals consecutive workgroup ids to the 8 XCDs round-robin, each with its own

@@ -1,7 +1,8 @@
 // infer_mfma.h -- the tile pieces shared by the frozen-inference kernels (infer.hip, infer_fp.hip, infer_pointnet.hip,
 // infer_pointnet_seg.hip): the sizes of a tile, the MFMA layer steps and the accumulator-to-row map (acc_row), and on top of
 // them one LDS-to-LDS layer (tile_layer), the last layer under a max (max_passes), the K = 3 points layer (points_layer), the
-// tile-of-one-cloud prologue (cloud_tile) and the per-cloud tile-max kernel (tile_max_kernel).  What the kernels' headers promise
+// tile-of-one-cloud prologue (cloud_tile) and the per-cloud tile-max kernel (tile_max_kernel).  tile_layer, max_passes and
+// points_layer are one body each for fp32 and bf16 tiles, selected by the tile's element type.  What the kernels' headers promise
 // is held here once: rows of a tile are independent (a pad row's contents stay in that row), pad rows are selected out under a
 // max, and a value is the same chain of operations in every kernel that calls a piece.
 //
@@ -209,16 +210,20 @@ __device__ __forceinline__ void tile_layer(const XT* X, const void* W, const flo
 
 // The last layer under a max, in passes of MAX_PASS columns over [c_begin, c_end): z = scale * (X W^T) + shift (ACT: and the
 // activation), rows >= nrows selected to -inf, the max over the lane's 32 rows in registers, then across the two lane halves
-// -> part[col]; z reaches neither LDS nor memory.
-template <int K, int LDX, bool ACT>
-__device__ __forceinline__ void max_passes(const float* X, const float* __restrict__ W, const float* __restrict__ scl,
+// -> part[col]; z reaches neither LDS nor memory.  On mfma_layer (XT float) or mfma_layer_bf16 (XT __bf16) by the tile's element
+// type, W [*, K] of that type; the epilogue, the max and part are fp32 either way.  UNROLL: mfma_layer_bf16's k-blocks per trip.
+// This is the loop over column passes on an unchanged tile that its comment speaks of: at K = 512 fully unrolled the compiler
+// lifted all 64 ds_read_b128 of the tile out of the pass loop (256 registers, 452 B of scratch per lane); that caller takes 8.
+template <int K, int LDX, bool ACT, int UNROLL = K / 16, typename XT>
+__device__ __forceinline__ void max_passes(const XT* X, const XT* __restrict__ W, const float* __restrict__ scl,
                                            const float* __restrict__ shf, float slope, int nrows, float* __restrict__ part, int c_begin,
                                            int c_end, int wave, int lane) {
     W += (size_t)c_begin * K; scl += c_begin; shf += c_begin; part += c_begin;      // the passes count columns from c_begin
     const int lr = lane & 31, lh = lane >> 5;
     for (int c0 = 0; c0 < c_end - c_begin; c0 += MAX_PASS) {
         f32x16 acc[2][MAX_NJ];
-        mfma_layer<K, LDX, MAX_NJ, 4 * MAX_NJ>(X, W + (size_t)c0 * K, wave, lane, acc);
+        if constexpr (std::is_same_v<XT, float>) mfma_layer<K, LDX, MAX_NJ, 4 * MAX_NJ>(X, W + (size_t)c0 * K, wave, lane, acc);
+        else mfma_layer_bf16<K, LDX, MAX_NJ, 4 * MAX_NJ, 2, UNROLL>(X, W + (size_t)c0 * K, wave, lane, acc);
 #pragma unroll
         for (int j = 0; j < MAX_NJ; ++j) {
             const int col = c0 + (wave + 4 * j) * 32 + lr;

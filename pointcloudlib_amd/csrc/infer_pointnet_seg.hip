@@ -18,16 +18,17 @@
 // The pieces both files run live in infer_mfma.h: the tile prologue (infer::cloud_tile), the K = 3 layer (infer::points_layer,
 // here also with the 3 x 3 transform and the store into F), the last layer under a max (infer::max_passes) and the tile reduce
 // (infer::tile_max_kernel).  seg_layer keeps its own epilogue loop: it alone also stores rows to F and has an identity form.
-// stn and trunk are two instantiations of one kernel body (seg_front_kernel<TRUNK>).
+// There are three kernel bodies, each with one host launcher: seg_front_kernel<TRUNK> (stn and trunk), seg_global_kernel<XT> and
+// seg_head_kernel<XT>, XT (float or __bf16) being the element type of the LDS tiles and of the weights.  Row strides and LDS sizes
+// follow from row_pad<XT>; seg_stage, seg_layer and infer::max_passes pick their store and their MFMA step by that type.
 //
 // Numerics: K = 3 layers are fmaf(w2, z, fmaf(w1, y, w0 * x)), the 3 x 3 transform the same chain in ascending k; every other
 // layer is one fp32 chain per element in the k order of infer::mfma_layer (the K = 832 layer: its chunks in ascending order, the
 // same chain); epilogues are scale * y + shift (two roundings) and the leaky ReLU.  A cloud's results depend only on its own
 // valid rows: bit for bit the same for any B, any position in the batch, any capacity N, any pad contents and any run.
 //
-// The bf16 kernels (pcl_pointnet_seg_global_infer_bf16_f32 / seg_global_bf16_kernel, pcl_pointnet_seg_head_infer_bf16_f32 /
-// seg_head_bf16_kernel) keep the geometry of their fp32 counterparts with the wide layers on
-// v_mfma_f32_32x32x16_bf16 (infer::mfma_layer_bf16).  stn, trunk, the B-row tails, the tile max, the layout of F (fp32
+// XT = __bf16 (pcl_pointnet_seg_global_infer_bf16_f32, pcl_pointnet_seg_head_infer_bf16_f32) puts the wide
+// layers on v_mfma_f32_32x32x16_bf16 (infer::mfma_layer_bf16).  stn, trunk, the B-row tails, the tile max, the layout of F (fp32
 // [B*N, ldf]) and every scale, shift and bias stay fp32.  Numerics contract:
 //   global: out3 is staged from F in fp32; x2 = out3 . T128[b] stays on the fp32 MFMA step (both operands are run-time fp32 data;
 //           1.4 % of the launch's FLOPs) with the fp32 kernel's chain; x2 is rounded to nearest even to bf16; conv4 is bf16 x bf16
@@ -49,44 +50,63 @@ namespace {
 
 using namespace infer;
 
-constexpr int SG_LD4 = 512 + row_pad<float>;       // row stride of the 512-wide out4 tile
-constexpr int SG_LDH = 256 + row_pad<float>;       // ... of the head's 256-wide tile
+// row strides of a tile of XT (float or __bf16): 128 wide (x2, the head's K-chunks; LD128 for float), the 512-wide out4 tile, the
+// head's 256-wide tile, and the fp32 view of LDS the head's logits go through (float: the tile itself; __bf16: [RT][LD128])
+template <typename XT> constexpr int SG_LD128 = 128 + row_pad<XT>;
+template <typename XT> constexpr int SG_LD4 = 512 + row_pad<XT>;
+template <typename XT> constexpr int SG_LDH = 256 + row_pad<XT>;
+template <typename XT> constexpr int SG_LDO = std::is_same_v<XT, float> ? SG_LDH<float> : LD128;
 constexpr int SG_C1 = 64, SG_C2 = 128, SG_C3 = 128, SG_C4 = 512, SG_C5 = 2048, SG_CT = 1024;
 constexpr int SG_F2 = SG_C1, SG_F3 = SG_F2 + SG_C2, SG_F4 = SG_F3 + SG_C3, SG_FK = SG_F4 + SG_C4;      // F's column blocks; 832
 constexpr int SG_H1 = 256, SG_H2 = 256, SG_H3 = 128, SG_PMAX = 128;
 constexpr int SG_CHUNK = 128;      // K-chunk of the head's first layer: 832 = 6 * 128 + 64
 constexpr size_t SG_LDS_FRONT = 4 * (size_t)2 * RT * LD128;              // 67 584 B: two workgroups per CU
-constexpr size_t SG_LDS_GLOBAL = 4 * (size_t)RT * SG_LD4;                // 132 096 B: one workgroup per CU
-constexpr size_t SG_LDS_HEAD = SG_LDS_FRONT;                             // the two chunk buffers, then the [64][260] tile over them
-static_assert(4 * (size_t)RT * SG_LDH <= SG_LDS_HEAD, "the head's tile lies over its chunk buffers");
-static_assert(2 * RT * LD128 <= RT * SG_LD4, "out3 and its transform lie inside the out4 tile");
+// the out4 tile: 132 096 B (float, one workgroup per CU) or 66 560 B (__bf16, two)
+template <typename XT> constexpr size_t SG_LDS_GLOBAL = sizeof(XT) * RT * SG_LD4<XT>;
+template <typename XT> constexpr int SG_WGS_GLOBAL = std::is_same_v<XT, float> ? 1 : 2;
+// the head's two chunk buffers, its tile and its logits over them: 67 584 B (float) or 34 816 B (__bf16)
+template <typename XT> constexpr size_t SG_LDS_HEAD = sizeof(XT) * 2 * RT * SG_LD128<XT>;
+template <typename XT> constexpr bool sg_head_fits = sizeof(XT) * RT * SG_LDH<XT> <= SG_LDS_HEAD<XT> && 4 * RT * SG_LDO<XT> <= SG_LDS_HEAD<XT>;
+template <typename XT> constexpr bool sg_global_fits = 4 * RT * LD128 + sizeof(XT) * RT * SG_LD128<XT> <= SG_LDS_GLOBAL<XT>;
+static_assert(SG_LD128<float> == LD128, "out3 is staged in fp32 under both precisions");
+static_assert(sg_head_fits<float> && sg_head_fits<__bf16>, "the head's tile and its fp32 logits lie over its chunk buffers");
+static_assert(sg_global_fits<float> && sg_global_fits<__bf16>, "fp32 out3 and its transform x2 lie inside the out4 tile");
 static_assert(SG_CT % MAX_PASS == 0 && SG_C5 % MAX_PASS == 0, "whole passes under the max");
 
-// One layer of a 64-row tile: z = act(scale * (X W^T) + shift), or z = X W^T when scl is null, from X (LDS, row stride LDX) into
-// Y (LDS, row stride LDY) and, when G is not null, its rows < nrows into G (global, row stride ldg) as well.  INPLACE: Y may lie
-// over X -- every wave has finished reading X before any writes Y.
-template <int K, int LDX, int CO, int LDY, bool INPLACE>
-__device__ __forceinline__ void seg_layer(const float* X, const float* __restrict__ W, const float* __restrict__ scl,
-                                          const float* __restrict__ shf, float slope, float* Y, float* __restrict__ G, int ldg, int nrows,
-                                          int wave, int lane) {
+// acc += X W^T on the MFMA step of the tile's element type: X [RT][LDX] in LDS, W fp32 (XT float) or bf16 (XT __bf16) with row
+// stride ldw, as infer::mfma_layer_acc / mfma_layer_bf16_acc
+template <int K, int LDX, int NJ, int NCB, typename XT>
+__device__ __forceinline__ void seg_mma(const XT* X, const void* W, int ldw, int wave, int lane, f32x16 (&acc)[2][NJ]) {
+    if constexpr (std::is_same_v<XT, float>) mfma_layer_acc<K, LDX, NJ, NCB>(X, static_cast<const float*>(W), ldw, wave, lane, acc);
+    else mfma_layer_bf16_acc<K, LDX, NJ, NCB>(X, static_cast<const __bf16*>(W), ldw, wave, lane, acc);
+}
+
+// One layer of a 64-row tile: z = act(scale * (X W^T) + shift) in fp32, or z = X W^T (IDENT: no scale, shift or activation), from
+// X (LDS, row stride LDX; W of X's element type) into Y (LDS, row stride LDY) as YT(z) and, when G is not null, its rows < nrows
+// into G (global, row stride ldg) unrounded as well.  INPLACE: Y may lie over X -- every wave has finished reading X before any
+// writes Y.
+template <int K, int LDX, int CO, int LDY, bool INPLACE, bool IDENT = false, typename XT, typename YT>
+__device__ __forceinline__ void seg_layer(const XT* X, const void* W, const float* __restrict__ scl, const float* __restrict__ shf,
+                                          float slope, YT* Y, float* __restrict__ G, int ldg, int nrows, int wave, int lane) {
     constexpr int NCB = CO / 32, NJ = (NCB + 3) / 4;
     const int lr = lane & 31, lh = lane >> 5;
     f32x16 acc[2][NJ];
-    mfma_layer<K, LDX, NJ, NCB>(X, W, wave, lane, acc);
+    acc_clear(acc);
+    seg_mma<K, LDX, NJ, NCB>(X, W, K, wave, lane, acc);
     if (INPLACE) __syncthreads();
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int cb = wave + 4 * j;
         if (cb < NCB) {
             const int col = cb * 32 + lr;
-            const float sc = scl ? scl[col] : 1.f, sh = scl ? shf[col] : 0.f;
+            const float sc = IDENT ? 1.f : scl[col], sh = IDENT ? 0.f : shf[col];
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = acc_row(rb, r, lh);
-                    const float z = scl ? act(sc * acc[rb][j][r] + sh, slope) : acc[rb][j][r];
-                    Y[row * LDY + col] = z;
+                    const float z = IDENT ? acc[rb][j][r] : act(sc * acc[rb][j][r] + sh, slope);
+                    Y[row * LDY + col] = (YT)z;
                     if (G && row < nrows) G[(size_t)row * ldg + col] = z;
                 }
         }
@@ -137,13 +157,15 @@ __global__ __launch_bounds__(NT, 2) void seg_front_kernel(const SegFrontArgs a) 
                                  lane);
 }
 
-// columns [k0, k0 + kw) of the tile's rows of F -> buf [RT][LD128]
-__device__ __forceinline__ void seg_stage(const float* __restrict__ Fb, int ldf, int N, int row0, int k0, int kw, float* buf, int tid) {
+// columns [k0, k0 + kw) of the tile's rows of F -> buf [RT][SG_LD128<XT>]: a 16-byte copy (float) or rounded to bf16
+template <typename XT>
+__device__ __forceinline__ void seg_stage(const float* __restrict__ Fb, int ldf, int N, int row0, int k0, int kw, XT* buf, int tid) {
     const int per = kw / 4;
     for (int i = tid; i < RT * per; i += NT) {
         const int r = i / per, c4 = (i - r * per) * 4;
-        const float* src = Fb + (size_t)min(row0 + r, N - 1) * ldf + k0 + c4;
-        *reinterpret_cast<float4*>(buf + r * LD128 + c4) = *reinterpret_cast<const float4*>(src);
+        const float4 v = *reinterpret_cast<const float4*>(Fb + (size_t)min(row0 + r, N - 1) * ldf + k0 + c4);
+        const float z[4] = {v.x, v.y, v.z, v.w};
+        tile_store4(buf + r * SG_LD128<XT> + c4, z);
     }
 }
 
@@ -152,16 +174,17 @@ struct SegGlobalArgs {
     float* F; int ldf;
     const int32_t* n_valid; int B, N, tpc;
     const float* TT;                               // [B][128][128]: TT[b][j][k] = T128[b][k][j]
-    const float* W[2]; const float* scl[2]; const float* shf[2];
+    const float* W[2]; const float* scl[2]; const float* shf[2];       // W[l] point at XT
     float slope;
     float* part;                                   // [B * tpc][2048]
 };
 
-__global__ __launch_bounds__(NT, 1) void seg_global_kernel(const SegGlobalArgs a) {
+template <typename XT>
+__global__ __launch_bounds__(NT, SG_WGS_GLOBAL<XT>) void seg_global_kernel(const SegGlobalArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* X4 = smem;                              // [RT][LD4]: out4; before it exists, out3 and its transform lie inside
-    float* X1 = smem;                              // [RT][LD128]
-    float* X2 = X1 + RT * LD128;                   // [RT][LD128]
+    XT* X4 = reinterpret_cast<XT*>(smem);          // [RT][LD4]: out4; before it exists, out3 and its transform lie inside
+    float* X1 = smem;                              // [RT][LD128] fp32: out3
+    XT* X2 = reinterpret_cast<XT*>(smem + RT * LD128);      // [RT][SG_LD128<XT>]: x2
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
     if (tile.empty()) return;
@@ -169,14 +192,16 @@ __global__ __launch_bounds__(NT, 1) void seg_global_kernel(const SegGlobalArgs a
     const float* Fb = a.F + (size_t)b * a.N * a.ldf;
     seg_stage(Fb, a.ldf, a.N, row0, SG_F3, SG_C3, X1, tid);
     __syncthreads();
-    seg_layer<SG_C3, LD128, SG_C3, LD128, false>(X1, a.TT + (size_t)b * SG_C3 * SG_C3, nullptr, nullptr, a.slope, X2, nullptr, 0, nrows, wave,
-                                                 lane);
+    // x2 = out3 . T128[b] on the fp32 step under both precisions, stored as XT
+    seg_layer<SG_C3, LD128, SG_C3, SG_LD128<XT>, false, true>(X1, a.TT + (size_t)b * SG_C3 * SG_C3, nullptr, nullptr, a.slope, X2, nullptr, 0,
+                                                              nrows, wave, lane);
     __syncthreads();
     float* Fr = a.F + ((size_t)b * a.N + row0) * a.ldf;
-    seg_layer<SG_C3, LD128, SG_C4, SG_LD4, true>(X2, a.W[0], a.scl[0], a.shf[0], a.slope, X4, Fr + SG_F4, a.ldf, nrows, wave, lane);
+    seg_layer<SG_C3, SG_LD128<XT>, SG_C4, SG_LD4<XT>, true>(X2, a.W[0], a.scl[0], a.shf[0], a.slope, X4, Fr + SG_F4, a.ldf, nrows, wave, lane);
     __syncthreads();
-    max_passes<SG_C4, SG_LD4, false>(X4, a.W[1], a.scl[1], a.shf[1], a.slope, nrows, a.part + ((size_t)b * a.tpc + t) * SG_C5, 0, SG_C5, wave,
-                                     lane);
+    // conv5 under the max: 8 k-blocks per trip of the bf16 step (infer::max_passes on why)
+    max_passes<SG_C4, SG_LD4<XT>, false, 8>(X4, reinterpret_cast<const XT*>(a.W[1]), a.scl[1], a.shf[1], a.slope, nrows,
+                                            a.part + ((size_t)b * a.tpc + t) * SG_C5, 0, SG_C5, wave, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------- head
@@ -184,15 +209,19 @@ struct SegHeadArgs {
     const float* F; int ldf;
     const int32_t* n_valid; int B, N, tpc;
     const float* bias; int ldb;                    // [B][256] per-cloud bias of layer 1 (added before its scale / shift)
-    const float* W[4]; const float* scl[3]; const float* shf[3];
+    const float* W[4]; const float* scl[3]; const float* shf[3];       // W[l] point at XT
     const float* bout; int part_num;
     float slope;
     float* out; size_t ob, oc, on;
 };
 
+template <typename XT>
 __global__ __launch_bounds__(NT, 2) void seg_head_kernel(const SegHeadArgs a) {
+    constexpr int LDC = SG_LD128<XT>, LDH = SG_LDH<XT>, LDO = SG_LDO<XT>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Y = smem;                               // [RT][LDH], over the two chunk buffers once layer 1 has read them
+    XT* S = reinterpret_cast<XT*>(smem);           // the two chunk buffers [RT][LDC]
+    XT* Y = S;                                     // [RT][LDH], over them once layer 1 has read them
+    float* Yo = smem;                              // [RT][LDO] fp32: the logits on their way to the transposed store
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
     const int b = tile.b, row0 = tile.row0, nrows = tile.nrows;
@@ -203,22 +232,23 @@ __global__ __launch_bounds__(NT, 2) void seg_head_kernel(const SegHeadArgs a) {
         return;
     }
     const float* Fb = a.F + (size_t)b * a.N * a.ldf;
+    const XT* W1 = reinterpret_cast<const XT*>(a.W[0]);
     // layer 1: 832 -> 256 over K-chunks of 128 (the last one 64), the next chunk staged while this one is multiplied
     constexpr int NFULL = SG_FK / SG_CHUNK, REST = SG_FK - NFULL * SG_CHUNK;
     static_assert(REST == 64 && NFULL % 2 == 0, "the chunk schedule below");
     constexpr int NJ = SG_H1 / 32 / 4;
     f32x16 acc[2][NJ];
     acc_clear(acc);
-    seg_stage(Fb, a.ldf, a.N, row0, 0, SG_CHUNK, smem, tid);
+    seg_stage(Fb, a.ldf, a.N, row0, 0, SG_CHUNK, S, tid);
     __syncthreads();
     for (int c = 0; c < NFULL; ++c) {
-        const float* cur = smem + (c & 1) * RT * LD128;
-        float* nxt = smem + ((c + 1) & 1) * RT * LD128;
+        const XT* cur = S + (c & 1) * RT * LDC;
+        XT* nxt = S + ((c + 1) & 1) * RT * LDC;
         seg_stage(Fb, a.ldf, a.N, row0, (c + 1) * SG_CHUNK, c + 1 < NFULL ? SG_CHUNK : REST, nxt, tid);
-        mfma_layer_acc<SG_CHUNK, LD128, NJ, SG_H1 / 32>(cur, a.W[0] + c * SG_CHUNK, SG_FK, wave, lane, acc);
+        seg_mma<SG_CHUNK, LDC, NJ, SG_H1 / 32>(cur, W1 + c * SG_CHUNK, SG_FK, wave, lane, acc);
         __syncthreads();
     }
-    mfma_layer_acc<REST, LD128, NJ, SG_H1 / 32>(smem, a.W[0] + NFULL * SG_CHUNK, SG_FK, wave, lane, acc);
+    seg_mma<REST, LDC, NJ, SG_H1 / 32>(S, W1 + NFULL * SG_CHUNK, SG_FK, wave, lane, acc);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -227,17 +257,20 @@ __global__ __launch_bounds__(NT, 2) void seg_head_kernel(const SegHeadArgs a) {
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) Y[acc_row(rb, r, lh) * SG_LDH + col] = act(sc * (acc[rb][j][r] + cb) + sh, a.slope);
+            for (int r = 0; r < 16; ++r) Y[acc_row(rb, r, lh) * LDH + col] = (XT)act(sc * (acc[rb][j][r] + cb) + sh, a.slope);
     }
     __syncthreads();
-    seg_layer<SG_H1, SG_LDH, SG_H2, SG_LDH, true>(Y, a.W[1], a.scl[1], a.shf[1], a.slope, Y, nullptr, 0, nrows, wave, lane);
+    seg_layer<SG_H1, LDH, SG_H2, LDH, true>(Y, a.W[1], a.scl[1], a.shf[1], a.slope, Y, nullptr, 0, nrows, wave, lane);
     __syncthreads();
-    seg_layer<SG_H2, SG_LDH, SG_H3, SG_LDH, true>(Y, a.W[2], a.scl[2], a.shf[2], a.slope, Y, nullptr, 0, nrows, wave, lane);
+    seg_layer<SG_H2, LDH, SG_H3, LDH, true>(Y, a.W[2], a.scl[2], a.shf[2], a.slope, Y, nullptr, 0, nrows, wave, lane);
     __syncthreads();
-    // layer 4: linear + bias on the column blocks that hold a part; W[3] has whole blocks of rows (the launcher checks)
+    // layer 4: linear + bias in fp32 on the column blocks that hold a part; W[3] has whole blocks of rows (the launcher checks)
     const int ncb = (a.part_num + 31) / 32;
     f32x16 lo[2][1];
-    if (wave < ncb) mfma_layer<SG_H3, SG_LDH, 1, 4>(Y, a.W[3], wave, lane, lo);
+    if (wave < ncb) {
+        acc_clear(lo);
+        seg_mma<SG_H3, LDH, 1, 4>(Y, a.W[3], SG_H3, wave, lane, lo);
+    }
     __syncthreads();
     if (wave < ncb) {
         const int col = wave * 32 + lr;
@@ -245,183 +278,13 @@ __global__ __launch_bounds__(NT, 2) void seg_head_kernel(const SegHeadArgs a) {
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) Y[acc_row(rb, r, lh) * SG_LDH + col] = lo[rb][0][r] + bo;
+            for (int r = 0; r < 16; ++r) Yo[acc_row(rb, r, lh) * LDO + col] = lo[rb][0][r] + bo;
     }
     __syncthreads();
     // the output's own layout [B, part_num, N]: a wave stores 64 consecutive points of one part; pad points are zeros
     if (row0 + lane < a.N)
         for (int c = wave; c < a.part_num; c += 4)
-            ob[(size_t)c * a.oc + (size_t)(row0 + lane) * a.on] = lane < nrows ? Y[lane * SG_LDH + c] : 0.f;
-}
-
-// ------------------------------------------------------------------------------------------------------- the bf16 kernels
-// pcl_pointnet_seg_global_infer_bf16_f32 and pcl_pointnet_seg_head_infer_bf16_f32 (header comment): the geometry of the fp32
-// kernels above -- one workgroup per 64-row tile of one cloud, tile-major, the early exit, partials in the never-cleared workspace,
-// the same second launch -- on infer::mfma_layer_bf16, with [64][K + 8] bf16 tiles.
-constexpr int SG16_LD128 = 128 + row_pad<__bf16>;  // row stride of a 128-wide bf16 tile (x2, the head's K-chunks)
-constexpr int SG16_LD4 = 512 + row_pad<__bf16>;    // ... of the 512-wide out4 tile
-constexpr int SG16_LDH = 256 + row_pad<__bf16>;    // ... of the head's 256-wide tile
-constexpr size_t SG16_LDS_GLOBAL = 2 * (size_t)RT * SG16_LD4;            // 66 560 B: two workgroups per CU
-constexpr size_t SG16_LDS_HEAD = 2 * (size_t)2 * RT * SG16_LD128;        // 34 816 B: the two chunk buffers; the tiles lie over them
-static_assert(4 * (size_t)RT * LD128 + 2 * (size_t)RT * SG16_LD128 <= SG16_LDS_GLOBAL, "fp32 out3 and bf16 x2 lie inside the out4 tile");
-static_assert(2 * (size_t)RT * SG16_LDH <= SG16_LDS_HEAD && 4 * (size_t)RT * LD128 <= SG16_LDS_HEAD,
-              "the head's bf16 tile and its fp32 logits lie over the chunk buffers");
-
-// seg_layer on bf16 operands: Y = bf16(z), z = act(scale * (X W^T) + shift) in fp32; G takes z itself, unrounded
-template <int K, int LDX, int CO, int LDY, bool INPLACE>
-__device__ __forceinline__ void seg_layer_bf16(const __bf16* X, const __bf16* __restrict__ W, const float* __restrict__ scl,
-                                               const float* __restrict__ shf, float slope, __bf16* Y, float* __restrict__ G, int ldg,
-                                               int nrows, int wave, int lane) {
-    constexpr int NCB = CO / 32, NJ = (NCB + 3) / 4;
-    const int lr = lane & 31, lh = lane >> 5;
-    f32x16 acc[2][NJ];
-    mfma_layer_bf16<K, LDX, NJ, NCB>(X, W, wave, lane, acc);
-    if (INPLACE) __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int cb = wave + 4 * j;
-        if (cb < NCB) {
-            const int col = cb * 32 + lr;
-            const float sc = scl[col], sh = shf[col];
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = acc_row(rb, r, lh);
-                    const float z = act(sc * acc[rb][j][r] + sh, slope);
-                    Y[row * LDY + col] = (__bf16)z;
-                    if (G && row < nrows) G[(size_t)row * ldg + col] = z;
-                }
-        }
-    }
-}
-
-// columns [k0, k0 + kw) of the tile's rows of F, rounded to bf16 -> buf [RT][SG16_LD128]
-__device__ __forceinline__ void seg_stage_bf16(const float* __restrict__ Fb, int ldf, int N, int row0, int k0, int kw, __bf16* buf, int tid) {
-    const int per = kw / 4;
-    for (int i = tid; i < RT * per; i += NT) {
-        const int r = i / per, c4 = (i - r * per) * 4;
-        const float4 v = *reinterpret_cast<const float4*>(Fb + (size_t)min(row0 + r, N - 1) * ldf + k0 + c4);
-        const float z[4] = {v.x, v.y, v.z, v.w};
-        tile_store4(buf + r * SG16_LD128 + c4, z);
-    }
-}
-
-// a.W[l] point at bf16
-__global__ __launch_bounds__(NT, 2) void seg_global_bf16_kernel(const SegGlobalArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __bf16* X4 = reinterpret_cast<__bf16*>(smem);  // [RT][SG16_LD4]: out4; before it exists, out3 (fp32) and x2 lie inside
-    float* X1 = smem;                              // [RT][LD128] fp32
-    __bf16* X2 = reinterpret_cast<__bf16*>(smem + RT * LD128);      // [RT][SG16_LD128]
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
-    const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
-    if (tile.empty()) return;
-    const int b = tile.b, t = tile.t, row0 = tile.row0, nrows = tile.nrows;
-    const float* Fb = a.F + (size_t)b * a.N * a.ldf;
-    seg_stage(Fb, a.ldf, a.N, row0, SG_F3, SG_C3, X1, tid);
-    __syncthreads();
-    {   // x2 = out3 . T128[b]: the fp32 kernel's step and chain, rounded into X2
-        f32x16 acc[2][1];
-        mfma_layer<SG_C3, LD128, 1, SG_C3 / 32>(X1, a.TT + (size_t)b * SG_C3 * SG_C3, wave, lane, acc);
-        const int col = wave * 32 + lr;
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) X2[acc_row(rb, r, lh) * SG16_LD128 + col] = (__bf16)acc[rb][0][r];
-    }
-    __syncthreads();
-    float* Fr = a.F + ((size_t)b * a.N + row0) * a.ldf;
-    seg_layer_bf16<SG_C3, SG16_LD128, SG_C4, SG16_LD4, true>(X2, reinterpret_cast<const __bf16*>(a.W[0]), a.scl[0], a.shf[0], a.slope, X4,
-                                                             Fr + SG_F4, a.ldf, nrows, wave, lane);
-    __syncthreads();
-    // conv5 under the max, as infer::max_passes without the activation
-    const __bf16* W5 = reinterpret_cast<const __bf16*>(a.W[1]);
-    float* part = a.part + ((size_t)b * a.tpc + t) * SG_C5;
-    for (int c0 = 0; c0 < SG_C5; c0 += MAX_PASS) {
-        f32x16 acc[2][MAX_NJ];
-        mfma_layer_bf16<SG_C4, SG16_LD4, MAX_NJ, 4 * MAX_NJ, 2, 8>(X4, W5 + (size_t)c0 * SG_C4, wave, lane, acc);
-#pragma unroll
-        for (int j = 0; j < MAX_NJ; ++j) {
-            const int col = c0 + (wave + 4 * j) * 32 + lr;
-            const float sc = a.scl[1][col], sh = a.shf[1][col];
-            float mx = -INFINITY;
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, acc_row(rb, r, lh) < nrows ? sc * acc[rb][j][r] + sh : -INFINITY);
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            if (lh == 0) part[col] = mx;
-        }
-    }
-}
-
-// a.W[l] point at bf16
-__global__ __launch_bounds__(NT, 2) void seg_head_bf16_kernel(const SegHeadArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __bf16* S = reinterpret_cast<__bf16*>(smem);   // the two chunk buffers [RT][SG16_LD128]
-    __bf16* Y = S;                                 // [RT][SG16_LDH], over them once layer 1 has read them
-    float* Yf = smem;                              // [RT][LD128] fp32: the logits on their way to the transposed store
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
-    const CloudTile tile = cloud_tile<RT>(a.B, a.N, a.n_valid);
-    const int b = tile.b, row0 = tile.row0, nrows = tile.nrows;
-    float* ob = a.out + (size_t)b * a.ob;
-    if (tile.empty()) {                               // a tile of pad rows only: its logits are zeros; nothing is loaded
-        if (row0 + lane < a.N)
-            for (int c = wave; c < a.part_num; c += 4) ob[(size_t)c * a.oc + (size_t)(row0 + lane) * a.on] = 0.f;
-        return;
-    }
-    const float* Fb = a.F + (size_t)b * a.N * a.ldf;
-    const __bf16* W1 = reinterpret_cast<const __bf16*>(a.W[0]);
-    // layer 1: the fp32 kernel's chunk schedule; every element of F is rounded as it enters LDS
-    constexpr int NFULL = SG_FK / SG_CHUNK, REST = SG_FK - NFULL * SG_CHUNK;
-    static_assert(REST == 64 && NFULL % 2 == 0, "the chunk schedule below");
-    constexpr int NJ = SG_H1 / 32 / 4;
-    f32x16 acc[2][NJ];
-    acc_clear(acc);
-    seg_stage_bf16(Fb, a.ldf, a.N, row0, 0, SG_CHUNK, S, tid);
-    __syncthreads();
-    for (int c = 0; c < NFULL; ++c) {
-        const __bf16* cur = S + (c & 1) * RT * SG16_LD128;
-        __bf16* nxt = S + ((c + 1) & 1) * RT * SG16_LD128;
-        seg_stage_bf16(Fb, a.ldf, a.N, row0, (c + 1) * SG_CHUNK, c + 1 < NFULL ? SG_CHUNK : REST, nxt, tid);
-        mfma_layer_bf16_acc<SG_CHUNK, SG16_LD128, NJ, SG_H1 / 32>(cur, W1 + c * SG_CHUNK, SG_FK, wave, lane, acc);
-        __syncthreads();
-    }
-    mfma_layer_bf16_acc<REST, SG16_LD128, NJ, SG_H1 / 32>(S, W1 + NFULL * SG_CHUNK, SG_FK, wave, lane, acc);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int col = (wave + 4 * j) * 32 + lr;
-        const float sc = a.scl[0][col], sh = a.shf[0][col], cb = a.bias[(size_t)b * a.ldb + col];
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Y[acc_row(rb, r, lh) * SG16_LDH + col] = (__bf16)act(sc * (acc[rb][j][r] + cb) + sh, a.slope);
-    }
-    __syncthreads();
-    seg_layer_bf16<SG_H1, SG16_LDH, SG_H2, SG16_LDH, true>(Y, reinterpret_cast<const __bf16*>(a.W[1]), a.scl[1], a.shf[1], a.slope, Y, nullptr,
-                                                           0, nrows, wave, lane);
-    __syncthreads();
-    seg_layer_bf16<SG_H2, SG16_LDH, SG_H3, SG16_LDH, true>(Y, reinterpret_cast<const __bf16*>(a.W[2]), a.scl[2], a.shf[2], a.slope, Y, nullptr,
-                                                           0, nrows, wave, lane);
-    __syncthreads();
-    // layer 4: linear + bias in fp32 on the column blocks that hold a part; the logits are never rounded
-    const int ncb = (a.part_num + 31) / 32;
-    f32x16 lo[2][1];
-    if (wave < ncb) mfma_layer_bf16<SG_H3, SG16_LDH, 1, 4>(Y, reinterpret_cast<const __bf16*>(a.W[3]), wave, lane, lo);
-    __syncthreads();
-    if (wave < ncb) {
-        const int col = wave * 32 + lr;
-        const float bo = col < a.part_num ? a.bout[col] : 0.f;
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Yf[acc_row(rb, r, lh) * LD128 + col] = lo[rb][0][r] + bo;
-    }
-    __syncthreads();
-    if (row0 + lane < a.N)
-        for (int c = wave; c < a.part_num; c += 4)
-            ob[(size_t)c * a.oc + (size_t)(row0 + lane) * a.on] = lane < nrows ? Yf[lane * LD128 + c] : 0.f;
+            ob[(size_t)c * a.oc + (size_t)(row0 + lane) * a.on] = lane < nrows ? Yo[lane * LDO + c] : 0.f;
 }
 
 // ------------------------------------------------------------------------------------------------------- B-row tails
@@ -531,79 +394,57 @@ extern "C" size_t pcl_pointnet_seg_rows_workspace_bytes(int B, int N, int ldf) {
     return 4 * (size_t)B * N * ldf;
 }
 
-extern "C" int pcl_pointnet_seg_stn_infer_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid,
-                                              int B, int N, int L, const int32_t* widths, const float* W0, int ldw0, const float* const* W,
-                                              const float* const* scale, const float* const* shift, float slope, void* workspace,
-                                              size_t workspace_bytes, float* out, int ldo, void* stream) {
-    const char* who = "pcl_pointnet_seg_stn_infer_f32";
-    PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", who);
-    PCL_REQUIRE(seg_shape_ok(PCL_SEG_STN, 3, L, widths), "%s: no kernel for these widths (pcl_pointnet_seg_infer_supported)", who);
-    PCL_REQUIRE(x && W0 && out, "%s: null pointer (x, W0 or out)", who);
+namespace {
+
+// One launcher body per kernel body; every check runs before any HIP call.
+// stn (TRUNK false: one stack, the T-Net's, whose first layer is the K = 3 layer) and trunk (conv1-3, then fstn's stack *_s on
+// out3; T3, F and the second stack are read and checked only when TRUNK)
+template <bool TRUNK>
+int seg_front_infer(const char* who, const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid, int B, int N,
+                    const float* T3, int L, const int32_t* widths, const float* W0, int ldw0, const float* const* W,
+                    const float* const* scale, const float* const* shift, int Ls, const int32_t* widths_s, const float* const* Ws,
+                    const float* const* scale_s, const float* const* shift_s, float slope, float* F, int ldf, size_t f_bytes,
+                    void* workspace, size_t workspace_bytes, float* out, int ldo, void* stream) {
+    PCL_REQUIRE(widths && W && scale && shift && (!TRUNK || (widths_s && Ws && scale_s && shift_s)), "%s: null host array", who);
+    PCL_REQUIRE(seg_shape_ok(TRUNK ? PCL_SEG_TRUNK : PCL_SEG_STN, 3, L, widths) && (!TRUNK || seg_shape_ok(PCL_SEG_FSTN, SG_C3, Ls, widths_s)),
+                "%s: no kernel for these widths (pcl_pointnet_seg_infer_supported)", who);
+    PCL_REQUIRE(x && (!TRUNK || T3) && W0 && out, "%s: null pointer (%s or out)", who, TRUNK ? "x, T3, W0" : "x, W0");
     if (int rc = seg_sizes_ok(who, B, N)) return rc;
     PCL_REQUIRE(ldw0 >= 3 && ldo >= SG_CT, "%s: ldw0=%d ldo=%d", who, ldw0, ldo);
-    for (int l = 0; l < 3; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", who, l);
+    for (int l = 0; l < 3; ++l)
+        PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]) && (!TRUNK || (scale_s[l] && shift_s[l] && Ws[l])), "%s: layer %d: null pointer",
+                    who, l);
+    if (TRUNK)
+        if (int rc = seg_rows_ok(who, F, ldf, f_bytes, B, N)) return rc;
     if (int rc = seg_part_ok(who, workspace, workspace_bytes, B, N, SG_CT)) return rc;
-    PCL_REQUIRE(al16(W[1], W[2]), "%s: the weights of layers 2-3 must be 16-byte aligned", who);
+    bool aligned = al16(W[1], W[2]);
+    if (TRUNK) aligned = aligned && al16(Ws[0], Ws[1], Ws[2]);
+    PCL_REQUIRE(aligned, "%s: the weights of %s must be 16-byte aligned", who, TRUNK ? "the MFMA layers" : "layers 2-3");
     SegFrontArgs a = {};
     a.x = x; a.sb = stride_b; a.sn = stride_n; a.sc = stride_c;
     a.n_valid = n_valid; a.B = B; a.N = N; a.tpc = tiles_of(N);
     a.W0 = W0; a.ldw0 = ldw0;
-    for (int l = 0; l < 3; ++l) { a.sW[l] = W[l]; a.sscl[l] = scale[l]; a.sshf[l] = shift[l]; }
-    a.slope = slope;
-    a.part = static_cast<float*>(workspace);
-    hipStream_t st = as_stream(stream);
-    if (int rc = lds_opt_in(seg_front_kernel<false>, SG_LDS_FRONT, who)) return rc;
-    hipLaunchKernelGGL(seg_front_kernel<false>, dim3(B * a.tpc), dim3(NT), SG_LDS_FRONT, st, a);
-    if (int rc = check_launch(who)) return rc;
-    hipLaunchKernelGGL(tile_max_kernel<SG_CT>, dim3(B, SG_CT / NT), dim3(NT), 0, st, a.part, n_valid, N, a.tpc, out, ldo);
-    return check_launch(who);
-}
-
-extern "C" int pcl_pointnet_seg_trunk_infer_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid,
-                                                int B, int N, const float* T3, int L, const int32_t* widths, const float* W0, int ldw0,
-                                                const float* const* W, const float* const* scale, const float* const* shift, int Ls,
-                                                const int32_t* widths_s, const float* const* Ws, const float* const* scale_s,
-                                                const float* const* shift_s, float slope, float* F, int ldf, size_t f_bytes,
-                                                void* workspace, size_t workspace_bytes, float* out, int ldo, void* stream) {
-    const char* who = "pcl_pointnet_seg_trunk_infer_f32";
-    PCL_REQUIRE(widths && W && scale && shift && widths_s && Ws && scale_s && shift_s, "%s: null host array", who);
-    PCL_REQUIRE(seg_shape_ok(PCL_SEG_TRUNK, 3, L, widths) && seg_shape_ok(PCL_SEG_FSTN, SG_C3, Ls, widths_s),
-                "%s: no kernel for these widths (pcl_pointnet_seg_infer_supported)", who);
-    PCL_REQUIRE(x && T3 && W0 && out, "%s: null pointer (x, T3, W0 or out)", who);
-    if (int rc = seg_sizes_ok(who, B, N)) return rc;
-    PCL_REQUIRE(ldw0 >= 3 && ldo >= SG_CT, "%s: ldw0=%d ldo=%d", who, ldw0, ldo);
-    for (int l = 0; l < 3; ++l)
-        PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]) && scale_s[l] && shift_s[l] && Ws[l], "%s: layer %d: null pointer", who, l);
-    if (int rc = seg_rows_ok(who, F, ldf, f_bytes, B, N)) return rc;
-    if (int rc = seg_part_ok(who, workspace, workspace_bytes, B, N, SG_CT)) return rc;
-    PCL_REQUIRE(al16(W[1], W[2], Ws[0], Ws[1], Ws[2]), "%s: the weights of the MFMA layers must be 16-byte aligned", who);
-    SegFrontArgs a = {};
-    a.x = x; a.sb = stride_b; a.sn = stride_n; a.sc = stride_c;
-    a.n_valid = n_valid; a.B = B; a.N = N; a.tpc = tiles_of(N);
-    a.T3 = T3; a.W0 = W0; a.ldw0 = ldw0;
     for (int l = 0; l < 3; ++l) {
-        a.cW[l] = W[l]; a.cscl[l] = scale[l]; a.cshf[l] = shift[l];
-        a.sW[l] = Ws[l]; a.sscl[l] = scale_s[l]; a.sshf[l] = shift_s[l];
+        if (TRUNK) { a.cW[l] = W[l]; a.cscl[l] = scale[l]; a.cshf[l] = shift[l]; }
+        a.sW[l] = TRUNK ? Ws[l] : W[l]; a.sscl[l] = TRUNK ? scale_s[l] : scale[l]; a.sshf[l] = TRUNK ? shift_s[l] : shift[l];
     }
     a.slope = slope;
-    a.F = F; a.ldf = ldf;
+    if (TRUNK) { a.T3 = T3; a.F = F; a.ldf = ldf; }
     a.part = static_cast<float*>(workspace);
     hipStream_t st = as_stream(stream);
-    if (int rc = lds_opt_in(seg_front_kernel<true>, SG_LDS_FRONT, who)) return rc;
-    hipLaunchKernelGGL(seg_front_kernel<true>, dim3(B * a.tpc), dim3(NT), SG_LDS_FRONT, st, a);
+    if (int rc = lds_opt_in(seg_front_kernel<TRUNK>, SG_LDS_FRONT, who)) return rc;
+    hipLaunchKernelGGL(seg_front_kernel<TRUNK>, dim3(B * a.tpc), dim3(NT), SG_LDS_FRONT, st, a);
     if (int rc = check_launch(who)) return rc;
     hipLaunchKernelGGL(tile_max_kernel<SG_CT>, dim3(B, SG_CT / NT), dim3(NT), 0, st, a.part, n_valid, N, a.tpc, out, ldo);
     return check_launch(who);
 }
 
-namespace {
-
-// both precisions of a launch: every check runs before any HIP call.  W[l]: fp32 (BF16 false) or bf16 (true) [C_l][C_{l-1}];
-// aligned: the entry's answer to whether every W[l] (and TT) is 16-byte aligned, reported here in its place among the checks
+// global and head at both precisions: W[l] are fp32 (BF16 false) or bf16 (true) [C_l][C_{l-1}]
 template <bool BF16>
 int seg_global_infer(const char* who, float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N, const float* TT, int L,
                      const int32_t* widths, const void* const* W, const float* const* scale, const float* const* shift, float slope,
-                     void* workspace, size_t workspace_bytes, float* out, int ldo, bool aligned, void* stream) {
+                     void* workspace, size_t workspace_bytes, float* out, int ldo, void* stream) {
+    using XT = std::conditional_t<BF16, __bf16, float>;
     PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", who);
     PCL_REQUIRE(seg_shape_ok(PCL_SEG_GLOBAL, SG_C3, L, widths), "%s: no kernel for these widths (pcl_pointnet_seg_infer_supported)", who);
     PCL_REQUIRE(TT && out, "%s: null pointer (TT or out)", who);
@@ -612,6 +453,8 @@ int seg_global_infer(const char* who, float* F, int ldf, size_t f_bytes, const i
     for (int l = 0; l < 2; ++l) PCL_REQUIRE(scale[l] && shift[l] && W[l], "%s: layer %d: null pointer", who, l);
     if (int rc = seg_rows_ok(who, F, ldf, f_bytes, B, N)) return rc;
     if (int rc = seg_part_ok(who, workspace, workspace_bytes, B, N, SG_C5)) return rc;
+    bool aligned = al16(TT);
+    for (int l = 0; l < 2; ++l) aligned = aligned && al16(W[l]);
     PCL_REQUIRE(aligned, "%s: TT and the weights must be 16-byte aligned", who);
     SegGlobalArgs a = {};
     a.F = F; a.ldf = ldf;
@@ -621,10 +464,8 @@ int seg_global_infer(const char* who, float* F, int ldf, size_t f_bytes, const i
     a.slope = slope;
     a.part = static_cast<float*>(workspace);
     hipStream_t st = as_stream(stream);
-    auto kern = BF16 ? seg_global_bf16_kernel : seg_global_kernel;
-    const size_t lds = BF16 ? SG16_LDS_GLOBAL : SG_LDS_GLOBAL;
-    if (int rc = lds_opt_in(kern, lds, who)) return rc;
-    hipLaunchKernelGGL(kern, dim3(B * a.tpc), dim3(NT), lds, st, a);
+    if (int rc = lds_opt_in(seg_global_kernel<XT>, SG_LDS_GLOBAL<XT>, who)) return rc;
+    hipLaunchKernelGGL(seg_global_kernel<XT>, dim3(B * a.tpc), dim3(NT), SG_LDS_GLOBAL<XT>, st, a);
     if (int rc = check_launch(who)) return rc;
     hipLaunchKernelGGL(tile_max_kernel<SG_C5>, dim3(B, SG_C5 / NT), dim3(NT), 0, st, a.part, n_valid, N, a.tpc, out, ldo);
     return check_launch(who);
@@ -634,7 +475,8 @@ template <bool BF16>
 int seg_head_infer(const char* who, const float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N, const float* cloud_bias,
                    int ldb, int L, const int32_t* widths, const void* const* W, int w_out_rows, const float* const* scale,
                    const float* const* shift, const float* bias_out, float slope, float* out, size_t stride_b, size_t stride_c,
-                   size_t stride_n, bool aligned, void* stream) {
+                   size_t stride_n, void* stream) {
+    using XT = std::conditional_t<BF16, __bf16, float>;
     PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", who);
     PCL_REQUIRE(seg_shape_ok(PCL_SEG_HEAD, SG_FK, L, widths), "%s: no kernel for these widths (pcl_pointnet_seg_infer_supported)", who);
     const int part_num = widths[3];
@@ -645,6 +487,8 @@ int seg_head_infer(const char* who, const float* F, int ldf, size_t f_bytes, con
                 (part_num + 31) / 32 * 32, w_out_rows);
     for (int l = 0; l < 4; ++l) PCL_REQUIRE(W[l] && (l == 3 || (scale[l] && shift[l])), "%s: layer %d: null pointer", who, l);
     if (int rc = seg_rows_ok(who, F, ldf, f_bytes, B, N)) return rc;
+    bool aligned = true;
+    for (int l = 0; l < 4; ++l) aligned = aligned && al16(W[l]);
     PCL_REQUIRE(aligned, "%s: the weights must be 16-byte aligned", who);
     SegHeadArgs a = {};
     a.F = F; a.ldf = ldf;
@@ -656,22 +500,39 @@ int seg_head_infer(const char* who, const float* F, int ldf, size_t f_bytes, con
     a.slope = slope;
     a.out = out; a.ob = stride_b; a.oc = stride_c; a.on = stride_n;
     hipStream_t st = as_stream(stream);
-    auto kern = BF16 ? seg_head_bf16_kernel : seg_head_kernel;
-    const size_t lds = BF16 ? SG16_LDS_HEAD : SG_LDS_HEAD;
-    if (int rc = lds_opt_in(kern, lds, who)) return rc;
-    hipLaunchKernelGGL(kern, dim3(B * a.tpc), dim3(NT), lds, st, a);
+    if (int rc = lds_opt_in(seg_head_kernel<XT>, SG_LDS_HEAD<XT>, who)) return rc;
+    hipLaunchKernelGGL(seg_head_kernel<XT>, dim3(B * a.tpc), dim3(NT), SG_LDS_HEAD<XT>, st, a);
     return check_launch(who);
 }
 
 }  // namespace
+
+extern "C" int pcl_pointnet_seg_stn_infer_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid,
+                                              int B, int N, int L, const int32_t* widths, const float* W0, int ldw0, const float* const* W,
+                                              const float* const* scale, const float* const* shift, float slope, void* workspace,
+                                              size_t workspace_bytes, float* out, int ldo, void* stream) {
+    return seg_front_infer<false>("pcl_pointnet_seg_stn_infer_f32", x, stride_b, stride_n, stride_c, n_valid, B, N, nullptr, L, widths, W0, ldw0,
+                                  W, scale, shift, 0, nullptr, nullptr, nullptr, nullptr, slope, nullptr, 0, 0, workspace, workspace_bytes, out,
+                                  ldo, stream);
+}
+
+extern "C" int pcl_pointnet_seg_trunk_infer_f32(const float* x, size_t stride_b, size_t stride_n, size_t stride_c, const int32_t* n_valid,
+                                                int B, int N, const float* T3, int L, const int32_t* widths, const float* W0, int ldw0,
+                                                const float* const* W, const float* const* scale, const float* const* shift, int Ls,
+                                                const int32_t* widths_s, const float* const* Ws, const float* const* scale_s,
+                                                const float* const* shift_s, float slope, float* F, int ldf, size_t f_bytes,
+                                                void* workspace, size_t workspace_bytes, float* out, int ldo, void* stream) {
+    return seg_front_infer<true>("pcl_pointnet_seg_trunk_infer_f32", x, stride_b, stride_n, stride_c, n_valid, B, N, T3, L, widths, W0, ldw0, W,
+                                 scale, shift, Ls, widths_s, Ws, scale_s, shift_s, slope, F, ldf, f_bytes, workspace, workspace_bytes, out, ldo,
+                                 stream);
+}
 
 extern "C" int pcl_pointnet_seg_global_infer_f32(float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N, const float* TT,
                                                  int L, const int32_t* widths, const float* const* W, const float* const* scale,
                                                  const float* const* shift, float slope, void* workspace, size_t workspace_bytes,
                                                  float* out, int ldo, void* stream) {
     return seg_global_infer<false>("pcl_pointnet_seg_global_infer_f32", F, ldf, f_bytes, n_valid, B, N, TT, L, widths,
-                                   reinterpret_cast<const void* const*>(W), scale, shift, slope, workspace, workspace_bytes, out, ldo,
-                                   W && L == 2 && al16(TT, W[0], W[1]), stream);
+                                   reinterpret_cast<const void* const*>(W), scale, shift, slope, workspace, workspace_bytes, out, ldo, stream);
 }
 
 extern "C" int pcl_pointnet_seg_global_infer_bf16_f32(float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N,
@@ -679,7 +540,7 @@ extern "C" int pcl_pointnet_seg_global_infer_bf16_f32(float* F, int ldf, size_t 
                                                       const float* const* scale, const float* const* shift, float slope, void* workspace,
                                                       size_t workspace_bytes, float* out, int ldo, void* stream) {
     return seg_global_infer<true>("pcl_pointnet_seg_global_infer_bf16_f32", F, ldf, f_bytes, n_valid, B, N, TT, L, widths, W, scale, shift,
-                                  slope, workspace, workspace_bytes, out, ldo, L == 2 && all16(W, 2, TT), stream);
+                                  slope, workspace, workspace_bytes, out, ldo, stream);
 }
 
 extern "C" int pcl_pointnet_seg_head_infer_f32(const float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N,
@@ -688,7 +549,7 @@ extern "C" int pcl_pointnet_seg_head_infer_f32(const float* F, int ldf, size_t f
                                                float slope, float* out, size_t stride_b, size_t stride_c, size_t stride_n, void* stream) {
     return seg_head_infer<false>("pcl_pointnet_seg_head_infer_f32", F, ldf, f_bytes, n_valid, B, N, cloud_bias, ldb, L, widths,
                                  reinterpret_cast<const void* const*>(W), w_out_rows, scale, shift, bias_out, slope, out, stride_b, stride_c,
-                                 stride_n, W && L == 4 && al16(W[0], W[1], W[2], W[3]), stream);
+                                 stride_n, stream);
 }
 
 extern "C" int pcl_pointnet_seg_head_infer_bf16_f32(const float* F, int ldf, size_t f_bytes, const int32_t* n_valid, int B, int N,
@@ -697,7 +558,7 @@ extern "C" int pcl_pointnet_seg_head_infer_bf16_f32(const float* F, int ldf, siz
                                                     const float* bias_out, float slope, float* out, size_t stride_b, size_t stride_c,
                                                     size_t stride_n, void* stream) {
     return seg_head_infer<true>("pcl_pointnet_seg_head_infer_bf16_f32", F, ldf, f_bytes, n_valid, B, N, cloud_bias, ldb, L, widths, W,
-                                w_out_rows, scale, shift, bias_out, slope, out, stride_b, stride_c, stride_n, L == 4 && all16(W, 4), stream);
+                                w_out_rows, scale, shift, bias_out, slope, out, stride_b, stride_c, stride_n, stream);
 }
 
 extern "C" int pcl_pointnet_seg_rows_f32(const float* x, int ldx, int R, int K, const float* W, int C, const float* scale,

@@ -105,10 +105,9 @@ INVENTORY = {
     ("infer_pointnet.hip", "pn_stack_infer"): dict(entry=["pcl_pointnet_stack_infer_f32", "pcl_pointnet_stack_infer_bf16"], external=_FROZEN, misaligned="error", case="none"),
     ("infer_pointnet_seg.hip", "seg_part_ok"): dict(entry=["pcl_pointnet_seg_*_infer_f32"], external=_FROZEN, misaligned="error", case="none"),
     ("infer_pointnet_seg.hip", "seg_rows_ok"): dict(entry=["pcl_pointnet_seg_*_infer_f32"], external=_FROZEN, misaligned="error", case="none"),
-    ("infer_pointnet_seg.hip", "pcl_pointnet_seg_stn_infer_f32"): dict(entry=["pcl_pointnet_seg_stn_infer_f32"], external=_FROZEN, misaligned="error", case="none"),
-    ("infer_pointnet_seg.hip", "pcl_pointnet_seg_trunk_infer_f32"): dict(entry=["pcl_pointnet_seg_trunk_infer_f32"], external=_FROZEN, misaligned="error", case="none"),
-    ("infer_pointnet_seg.hip", "pcl_pointnet_seg_global_infer_f32"): dict(entry=["pcl_pointnet_seg_global_infer_f32"], external=_FROZEN, misaligned="error", case="none"),
-    ("infer_pointnet_seg.hip", "pcl_pointnet_seg_head_infer_f32"): dict(entry=["pcl_pointnet_seg_head_infer_f32"], external=_FROZEN, misaligned="error", case="none"),
+    ("infer_pointnet_seg.hip", "seg_front_infer"): dict(entry=["pcl_pointnet_seg_stn_infer_f32", "pcl_pointnet_seg_trunk_infer_f32"], external=_FROZEN, misaligned="error", case="none"),
+    ("infer_pointnet_seg.hip", "seg_global_infer"): dict(entry=["pcl_pointnet_seg_global_infer_f32", "pcl_pointnet_seg_global_infer_bf16_f32"], external=_FROZEN, misaligned="error", case="none"),
+    ("infer_pointnet_seg.hip", "seg_head_infer"): dict(entry=["pcl_pointnet_seg_head_infer_f32", "pcl_pointnet_seg_head_infer_bf16_f32"], external=_FROZEN, misaligned="error", case="none"),
     ("infer_pointnet_seg.hip", "pcl_pointnet_seg_rows_f32"): dict(entry=["pcl_pointnet_seg_rows_f32"], external=_FROZEN, misaligned="error", case="none"),
 }
 
