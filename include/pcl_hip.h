@@ -845,6 +845,42 @@ int pcl_sa_level_infer_bf16_f32(const float* xyz, const float* new_xyz, const fl
                                 int ns, int L, const int32_t* widths, const void* const* W, const float* const* scale,
                                 const float* const* shift, float slope, float* out, int ldo, int col0, void* stream);
 
+/* ---- Frozen inference: one k-NN PointConv level in evaluation mode, up to and including the contraction, as ONE launch -----
+ * misc/pointconv_utils.py:361-394 (PointConvDensitySetAbstraction.execute: sample_and_group :133-170, the feature MLP :384-389, the
+ * WeightNet :220-250 / :391-392, the DensityNet :186-218 / :376-377, the density multiply and per-point matmul :393-394) as evaluated
+ * by net.eval().  Per group g (centre new_xyz[g], neighbours idx[g, :]: k-NN lists, every slot a real row, no counts) and row s:
+ *     src    = b*N + idx[g, s],  b = g / m,   d = xyz[src] - new_xyz[g]
+ *     y1     = Wx d + Uf[src]   (Uf NULL: a level without point features),   z_l = act(scale_l * y_l + shift_l),  y_l = W_l z_{l-1}
+ *     w[s,:] = WeightNet(d): 3 -> 8 -> 8 -> 16,  rho[s] = DensityNet(density[src]): 1 -> 8 -> 8 -> 1, each layer
+ *              relu(scale * (W x) + shift) with the dot product an fp32 fmaf chain in ascending k from the first product
+ *     out[g * ldo + c*16 + m] = sum_s z_3[s, c] * (rho[s] * w[s, m])
+ * xyz [B*N,3], new_xyz [B*m,3], idx [B,m,ns] int32 with every entry in [0, N) (a precondition: the kernel clamps an entry outside it
+ * to the nearest end so that no load leaves the cloud, and reports nothing), density [B*N] (the raw output of pcl_density_f32), Wx [C1,3] (row stride ldw),
+ * Uf [B*N, C1] or NULL.  Host arrays of L entries as for pcl_sa_level_infer_f32: widths, W (W[0] ignored), scale, shift (eval
+ * BatchNorm with the conv bias folded into the shift); act = leaky ReLU with `slope`.  `nets`: PCL_POINTCONV_NETS_FLOATS floats on
+ * the device, the two small nets' dense weights [out][in] and folded eval scale / shift per layer at these offsets:
+ *     WeightNet  W1 0 [8][3]   s1 24   t1 32   W2 40 [8][8]    s2 104  t2 112  W3 120 [16][8]  s3 248  t3 264
+ *     DensityNet W1 280 [8][1] s1 288  t1 296  W2 304 [8][8]   s2 368  t2 376  W3 384 [1][8]   s3 392  t3 393     (394 .. 399 unused)
+ * out [B*m, ldo], ldo >= 16 * C3 and a multiple of 4.  Uf, W_l (l >= 1) and out MUST be 16-byte aligned: the kernel moves them in
+ * 16-byte pieces and has no other form, so this is the caller's precondition (pointcloudlib_amd/inference.py raises before the call).
+ * Activations stay in LDS / registers; layers 2
+ * and 3 on v_mfma_f32_32x32x2_f32, the contraction on v_mfma_f32_16x16x4_f32 with s ascending.  A group's result depends only on
+ * its own rows (not on B, on the group's place in the launch or on how many groups a workgroup owns); no atomics, two calls give
+ * identical bits; out is fully defined for every group.  Kernels exist for (ns, C1/C2/C3) = (32, 64/64/128) and (64, 128/128/256)
+ * with L = 3, M = 16: pcl_pointconv_level_infer_supported answers for any query; any other shape returns PCL_EINVAL ("no kernel")
+ * before any launch. */
+#define PCL_POINTCONV_NETS_FLOATS 400
+int pcl_pointconv_level_infer_supported(int ns, int L, int C1, int C2, int C3, int M);
+/* How many consecutive groups one workgroup of a launch over G groups owns (whole 64-row tiles: a multiple of 64 / ns; 0 for an ns
+ * without a kernel).  It depends on the device's compute-unit count; no result depends on it -- the tests ask so as to know that
+ * they walk several tiles per workgroup. */
+int pcl_pointconv_level_infer_group_tile(int ns, int G);
+/* reference: misc/pointconv_utils.py:361-394 in eval mode (sample_and_group :133-170, WeightNet :220-250, DensityNet :186-218) */
+int pcl_pointconv_level_infer_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
+                                  const float* density, const int32_t* idx, int B, int N, int m, int ns, int L, const int32_t* widths,
+                                  const float* const* W, const float* const* scale, const float* const* shift, float slope,
+                                  const float* nets, int M, float* out, int ldo, void* stream);
+
 /* ---- Frozen inference: one PointNet++ feature-propagation level in evaluation mode as ONE launch ------------------------
  * misc/ops.py:54-107 (PointNetFeaturePropagation.execute: 3-NN inverse-distance interpolation, concat with the skip features,
  * conv/bn/relu x L) as evaluated by net.eval(), optionally followed by the part-seg head of networks/seg/pointnet2_partseg.py:151-176

@@ -33,7 +33,15 @@ DESIGN.md section 20): ``conv5`` has no activation, so the head's 4944-wide firs
 stored.  ``FrozenPointNetPartseg(net, precision="bf16")`` runs the two wide launches as ``pcl_pointnet_seg_global_infer_bf16_f32``
 and ``pcl_pointnet_seg_head_infer_bf16_f32``: conv4, conv5 and the head's four layers take bf16 operands (activations rounded to
 nearest even, every weight snapshot as bf16 in ``refresh()``) and accumulate in fp32; the T-Nets, the trunk, the product with
-``T128``, the row buffer, the epilogues, the max, the per-cloud bias and the logits stay fp32."""
+``T128``, the row buffer, the epilogues, the max, the per-cloud bias and the logits stay fp32.
+
+``FrozenPointConv(net)`` is the same for ``networks.cls.pointconv.PointConvDensityClsSsg`` (csrc/infer_pointconv.hip, DESIGN.md
+section 24): per k-NN level the per-point product ``Uf = points W0[:, 3:]^T`` (stats-free library GEMM), then ONE
+``pcl_pointconv_level_infer_f32`` launch that runs the feature MLP, the WeightNet and the DensityNet of every row and the
+density-weighted contraction with its activations in LDS -- the ``[B*S, 16 C]`` contraction output is the only large tensor a
+level writes -- then the level's ``Linear(16 C -> C)`` as a stats-free GEMM of the family ``net.eval()`` selects, with the eval
+constants.  The ``group_all`` level runs the stats-free GEMMs and ``pcl_pointconv_contract_bn_f32``; the head runs the eval-mode
+head kernels.  fp32 only; constructed directly."""
 import copy
 import ctypes
 
@@ -44,12 +52,15 @@ from .misc.head import MAX_ROWS, fc_head
 from .misc.layers import PointwiseMLP
 from .misc.ops import (_lengths, _p, _stream, group_all, group_points, mlp_segment_max, pack_rows, packed_layout, three_interpolate,
                        three_nn, unpack_rows)
+from .misc.pointconv_utils import (DensityNet, PointConvDensitySetAbstraction, WeightNet, _linear_flush, _pointconv_linear, compute_density,
+                                   sample_level)
+from .networks.cls.pointconv import PointConvDensityClsSsg
 from .networks.cls.pointnet import PointNet
-from .networks.cls.pointnet2 import PointNet2_cls
+from .networks.cls.pointnet2 import PointNet2_cls, SamplingPrefetch
 from .networks.seg.pointnet2_partseg import PointNet2_partseg
 from .networks.seg.pointnet_partseg import PointNet_partseg
 
-__all__ = ["frozen", "FrozenPointNet", "FrozenPointNet2", "FrozenPointNet2Partseg", "FrozenPointNetPartseg"]
+__all__ = ["frozen", "FrozenPointConv", "FrozenPointNet", "FrozenPointNet2", "FrozenPointNet2Partseg", "FrozenPointNetPartseg"]
 
 
 PRECISIONS = ("fp32", "bf16")
@@ -72,10 +83,11 @@ def frozen(net, precision="fp32"):
                     f"(PointNet++ part segmentation), got {type(net).__name__}; PointNet has FrozenPointNet(net)")
 
 
-def _eval_consts(mlp, l):
-    """(scale, shift) of layer ``l`` of a PointwiseMLP in evaluation mode, conv bias folded into the shift (fp32, on the device)."""
+def _eval_consts(mlp, l, fold_bias=True):
+    """(scale, shift) of layer ``l`` of a PointwiseMLP in evaluation mode, conv bias folded into the shift (fp32, on the device).
+    ``fold_bias=False``: the constants behind a GEMM that adds the bias itself."""
     W = mlp.weights[l]
-    bias = None if mlp.biases is None else mlp.biases[l].detach()
+    bias = None if mlp.biases is None or not fold_bias else mlp.biases[l].detach()
     if mlp.bn:
         rm, rv = getattr(mlp, f"running_mean_{l}"), getattr(mlp, f"running_var_{l}")
         scale = mlp.gammas[l].detach() * torch.rsqrt(rv + mlp.eps)
@@ -757,3 +769,248 @@ class FrozenPointNetPartseg:
                   self.head_widths, self.head_W, self.Wout.shape[0], h.c_scale, h.c_shift, _p(self.bias_out), self.slope, _p(out),
                   out.stride(0), out.stride(1), out.stride(2), st)
         return T3.view(B, 3, 3), TT.view(B, 128, 128).transpose(1, 2), glob[:, :2048], out
+
+
+# ---------------------------------------------------------------------------------------------- PointConv classification
+POINTCONV_M = 16                                         # WeightNet(3, 16)
+
+
+def pack_small_nets(weightnet, densitynet):
+    """The eval constants of a level's WeightNet (3 -> 8 -> 8 -> 16) and DensityNet (1 -> 8 -> 8 -> 1) as the one packed buffer of
+    ``PCL_POINTCONV_NETS_FLOATS`` floats ``pcl_pointconv_level_infer_f32`` takes: per net and layer the dense weight ``[out][in]``,
+    then the folded ``scale`` and ``shift`` (``_eval_consts``), at the offsets include/pcl_hip.h lists.  Plain torch, any device."""
+    parts = []
+    for mlp in (weightnet.mlp, densitynet.mlp):
+        for l in range(mlp.n_layers):
+            parts += [mlp.weights[l].detach().float().reshape(-1), *_eval_consts(mlp, l)]
+    flat = torch.cat(parts)
+    out = torch.zeros(_lib.define("PCL_POINTCONV_NETS_FLOATS"), dtype=torch.float32, device=flat.device)
+    out[:flat.numel()] = flat
+    return out
+
+
+class _LevelLinear:
+    """Snapshot of a level's ``Linear(16 C -> C)`` + BatchNorm1d + ReLU (a one-layer PointwiseMLP): the stats-free GEMM of the family
+    ``_linear_flush`` selects for the call's shape under ``net.eval()`` (bias in the GEMM, as there), then ``pcl_bn_act_f32`` with the
+    eval constants."""
+
+    def __init__(self, mlp):
+        self.W = mlp.weights[0].detach().float().contiguous().clone()
+        self.bias = None if mlp.biases is None else mlp.biases[0].detach().float().contiguous().clone()
+        self.scale, self.shift = _eval_consts(mlp, 0, fold_bias=False)
+        self.slope = float(mlp.slope) if mlp.last_act else 1.0
+
+    def run(self, X):
+        P, K = X.shape
+        C = self.W.shape[0]
+        st = _stream()
+        Y = torch.empty((P, C), dtype=torch.float32, device=X.device)
+        flush = _linear_flush(K, P)
+        if flush:
+            _lib.call("pcl_frag_linear_fwd_f32", _p(X), K, _p(self.W), K, _p(self.bias), None, None, 0.0, P, K, C, _p(Y), C, None, None,
+                      flush, st, tag=f"fwd{K}x{C}")
+        else:
+            _lib.call("pcl_linear_fwd_rows_f32", _p(X), _p(self.W), _p(self.bias), None, None, 0.0, P, K, C, _p(Y), None, None, None, st,
+                      tag=f"fwd{K}x{C}")
+        out = torch.empty_like(Y)
+        _lib.call("pcl_bn_act_f32", _p(Y), _p(self.scale), _p(self.shift), self.slope, P, C, _p(out), st)
+        return out
+
+
+def _small_nets_ok(sa):
+    wn, dn = sa.weightnet, sa.densitynet
+    return (isinstance(wn, WeightNet) and isinstance(dn, DensityNet) and wn.mlp.spec == [3, 8, 8, POINTCONV_M] and dn.mlp.spec == [1, 8, 8, 1]
+            and all(m.bn and m.last_act and m.slope == 0.0 for m in (wn.mlp, dn.mlp))
+            and sa.linear.n_layers == 1 and sa.linear.bn)
+
+
+def _pointconv_fusable(sa, D):
+    mlp = sa.mlp
+    if sa.group_all or not (mlp.n_layers == 3 and mlp.bn and mlp.last_act and mlp.spec[0] == 3 + D and _small_nets_ok(sa)):
+        return False
+    return bool(_lib.size_query("pcl_pointconv_level_infer_supported", int(sa.nsample), 3, *[int(c) for c in mlp.spec[1:]], POINTCONV_M))
+
+
+class _FusedPointConv(_SegStack):
+    """Snapshot of one k-NN PointConv level for pcl_pointconv_level_infer_f32: the feature MLP (first layer folded), the packed small
+    nets and the level's Linear."""
+
+    def __init__(self, sa, D):
+        mlp = sa.mlp
+        super().__init__([(mlp, l) for l in range(mlp.n_layers)], first=None)
+        W0 = mlp.weights[0].detach().float().contiguous().clone()
+        self.D, self.slope = D, float(mlp.slope)
+        self.W0, self.ldw = W0, W0.shape[1]                            # Wx = W0[:, :3]: the kernel reads it with the row stride ldw
+        self.Wf = W0[:, 3:].contiguous() if D else None
+        self.nets = pack_small_nets(sa.weightnet, sa.densitynet)
+        self.linear = _LevelLinear(sa.linear)
+
+    def contract(self, xyz, new_xyz, points, idx, density):
+        """-> the contraction output [B*S, 16 C3] (the level up to misc/pointconv_utils.py:394)."""
+        B, N, _ = xyz.shape
+        S, ns = idx.shape[1], idx.shape[2]
+        C1, C3 = self.widths[0], self.widths[-1]
+        st = _stream()
+        Uf = None
+        if self.D:
+            Uf = torch.empty((B * N, C1), dtype=torch.float32, device=xyz.device)
+            _lib.call("pcl_linear_fwd_rows_f32", _p(points.reshape(B * N, self.D)), _p(self.Wf), None, None, None, 0.0, B * N, self.D, C1, _p(Uf),
+                      None, None, None, st, tag=f"pt{self.D}x{C1}")
+        out = torch.empty((B * S, POINTCONV_M * C3), dtype=torch.float32, device=xyz.device)
+        if any(t is not None and t.data_ptr() % 16 for t in (Uf, out, *self.Ws[1:])):      # the entry point's precondition (pcl_hip.h)
+            raise ValueError("pcl_pointconv_level_infer_f32: Uf, the weights and out must be 16-byte aligned")
+        rows = B * S * ns
+        _lib.call("pcl_pointconv_level_infer_f32", _p(xyz), _p(new_xyz), _p(Uf), _p(self.W0), self.ldw, _p(density), _p(idx), B, N, S, ns, self.L,
+                  self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(self.nets), POINTCONV_M, _p(out), out.shape[1], st,
+                  algo_flops=2 * rows * (3 * C1 + C1 * self.widths[1] + self.widths[1] * C3 + POINTCONV_M * C3 + 296),
+                  tag=f"pointconv{ns}x{C3}")
+        return out
+
+    def run(self, xyz, new_xyz, points, idx, density):
+        B, S = idx.shape[0], idx.shape[1]
+        return self.linear.run(self.contract(xyz, new_xyz, points, idx, density)).view(B, S, -1)
+
+
+class _RowsStack:
+    """Snapshot of a PointwiseMLP for the stats-free library GEMMs: dense weights and eval constants (conv bias folded into the
+    shift).  ``run(x [P, C0])`` chains ``pcl_linear_fwd_rows_f32`` with the BatchNorm + activation of each layer folded into the
+    next GEMM's operand load -> (pre-BatchNorm output of the last layer, its scale, its shift); ``run_act`` applies them too."""
+
+    def __init__(self, mlp):
+        self.slope = float(mlp.slope)
+        self.out_slope = self.slope if mlp.last_act else 1.0
+        self.Ws = [w.detach().float().contiguous().clone() for w in mlp.weights]
+        consts = [_eval_consts(mlp, l) for l in range(len(self.Ws))]
+        self.scales, self.shifts = [c[0] for c in consts], [c[1] for c in consts]
+
+    def run(self, cur):
+        P, st = cur.shape[0], _stream()
+        sc = sh = None
+        for W, scale, shift in zip(self.Ws, self.scales, self.shifts):
+            cout, cin = W.shape
+            Y = torch.empty((P, cout), dtype=torch.float32, device=cur.device)
+            _lib.call("pcl_linear_fwd_rows_f32", _p(cur), _p(W), None, _p(sc), _p(sh), self.slope, P, cin, cout, _p(Y), None, None, None, st,
+                      tag=f"fwd{cin}x{cout}")
+            cur, sc, sh = Y, scale, shift
+        return cur, sc, sh
+
+    def run_act(self, x):
+        Y, sc, sh = self.run(x)
+        out = torch.empty_like(Y)
+        _lib.call("pcl_bn_act_f32", _p(Y), _p(sc), _p(sh), self.out_slope, Y.shape[0], Y.shape[1], _p(out), _stream())
+        return out
+
+
+class _PointConvGroupAll:
+    """Snapshot of the ``group_all`` level: the feature MLP, the WeightNet and the DensityNet as stats-free GEMM chains
+    (``_RowsStack``), ``pcl_pointconv_contract_bn_f32`` with the feature MLP's last eval constants, and an eval-mode copy of the
+    level's Linear (16384 -> 1024 on B rows: the wide head kernels ``net.eval()`` uses)."""
+
+    def __init__(self, sa, linear):
+        self.feat, self.weightnet, self.densitynet = _RowsStack(sa.mlp), _RowsStack(sa.weightnet.mlp), _RowsStack(sa.densitynet.mlp)
+        self.linear = linear
+
+    def run(self, xyz, points, density):
+        B, N, _ = xyz.shape
+        P = B * N
+        local = xyz - xyz.mean(dim=1, keepdim=True)                    # sample_and_group_all: relative to the centroid
+        rows = (torch.cat([local, points], dim=-1) if points is not None else local).reshape(P, -1).contiguous()
+        Y, sc, sh = self.feat.run(rows)
+        C = Y.shape[1]
+        weights = self.weightnet.run_act(local.reshape(P, 3))
+        rho = self.densitynet.run_act(density.reshape(P, 1))
+        out = torch.empty((B, C * POINTCONV_M), dtype=torch.float32, device=xyz.device)
+        _lib.call("pcl_pointconv_contract_bn_f32", _p(Y), _p(sc), _p(sh), self.feat.out_slope, _p(rho), _p(weights), B, N, C, POINTCONV_M,
+                  _p(out), _stream())
+        return _pointconv_linear(self.linear, out.view(B, 1, -1))
+
+
+class FrozenPointConv:
+    """Frozen evaluator of ``networks.cls.pointconv.PointConvDensityClsSsg``: ``fnet(xyz [B,3,N], start_idx=None, knn_lists=None,
+    sampling=None) -> [B, n_classes]``, the signature of ``net.forward``; ``fnet.run(...)`` also returns the three level features
+    (channel-last: ``[B, S, C]``).  Index lists and densities come from the network's own ``sa.sample`` (or a handle of
+    ``net.precompute_sampling``).
+
+    ``fnet.levels`` names the plan per level: ``"fused"`` for a k-NN level whose shape has a kernel
+    (``pcl_pointconv_level_infer_supported``; module docstring), ``"all"`` for a ``group_all`` level of the usual small nets,
+    ``"module"`` otherwise -- an eval-mode copy of the level's own module runs.  ``refresh()`` re-reads weights and running
+    statistics; ``net`` itself is never modified (parameters, buffers, ``training`` flags).  fp32 only."""
+
+    def __init__(self, net):
+        if not isinstance(net, PointConvDensityClsSsg):
+            raise TypeError(f"FrozenPointConv takes networks.cls.pointconv.PointConvDensityClsSsg, got {type(net).__name__}")
+        self.net = net
+        self._copies = {}
+        self.refresh()
+
+    def _copy(self, key, module):
+        c = self._copies.get(key)
+        if c is None:
+            c = self._copies[key] = copy.deepcopy(module).eval()
+        else:
+            c.load_state_dict(module.state_dict())        # same objects: the head kernels' plan cache keys on them
+        return c
+
+    @torch.no_grad()
+    def refresh(self):
+        net = self.net
+        self.plans = []
+        D = 0
+        for name in ("sa1", "sa2", "sa3"):
+            sa = getattr(net, name)
+            if isinstance(sa, PointConvDensitySetAbstraction) and _pointconv_fusable(sa, D):
+                self.plans.append(("fused", _FusedPointConv(sa, D)))
+            elif (isinstance(sa, PointConvDensitySetAbstraction) and sa.group_all and sa.mlp.bn and sa.mlp.last_act and sa.mlp.spec[0] == 3 + D
+                  and _small_nets_ok(sa)):
+                self.plans.append(("all", _PointConvGroupAll(sa, self._copy((name, "linear"), sa.linear))))
+            else:
+                self.plans.append(("module", self._copy(name, sa)))
+            D = sa.linear.spec[-1]
+        self.levels = [k for k, _ in self.plans]
+        self._head = self._copy("head", torch.nn.Sequential(net.fc1, net.bn1, net.relu, net.drop1, net.fc2, net.bn2, net.relu, net.drop2, net.fc3))
+        self.head = list(self._head)
+        return self
+
+    def __call__(self, xyz, start_idx=None, knn_lists=None, sampling=None):
+        return self.run(xyz, start_idx, knn_lists, sampling)[1]
+
+    @staticmethod
+    def _sample(sa, xyz, start_idx, knn_idx):
+        if knn_idx is None or sa.group_all:
+            return sa.sample(xyz, start_idx)
+        new_xyz, idx = sample_level(sa.npoint, sa.nsample, xyz, start_idx, knn_idx)
+        return new_xyz, [(idx, compute_density(xyz, sa.bandwidth))]
+
+    @torch.no_grad()
+    def run(self, xyz, start_idx=None, knn_lists=None, sampling=None):
+        """-> ([feature of sa1, sa2, sa3: [B, S, C]], logits [B, n_classes])."""
+        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[1] != 3:
+            raise ValueError(f"FrozenPointConv: xyz must be [B,3,N], got {tuple(getattr(xyz, 'shape', ()))}")
+        if not xyz.is_cuda or xyz.dtype != torch.float32:
+            raise TypeError(f"FrozenPointConv: expected a float32 tensor on the GPU, got {xyz.dtype} on {xyz.device}")
+        net = self.net
+        B = xyz.shape[0]
+        SamplingPrefetch.adopt_sampling(sampling)
+        knn = (None, None, None) if knn_lists is None else (*knn_lists, None)
+        starts = (None, None, None) if start_idx is None else (start_idx[0], start_idx[1], None)
+        pts = xyz.permute(0, 2, 1).contiguous()
+        points = None
+        feats = []
+        for i, (name, (kind, plan)) in enumerate(zip(("sa1", "sa2", "sa3"), self.plans)):
+            sa = getattr(net, name)
+            lv = sampling["levels"][i] if sampling is not None else self._sample(sa, pts, starts[i], knn[i])
+            new_xyz, ((idx, density),) = lv
+            if kind == "fused":
+                points = plan.run(pts, new_xyz.contiguous(), points, idx.contiguous(), density.contiguous())
+            elif kind == "all":
+                points = plan.run(pts, points, density.contiguous())
+            else:
+                nx, f = plan(pts.permute(0, 2, 1), None if points is None else points.permute(0, 2, 1), sampling=lv)
+                points = f.permute(0, 2, 1).contiguous()
+                if new_xyz is None:
+                    new_xyz = nx.permute(0, 2, 1)
+            feats.append(points)
+            pts = new_xyz.contiguous() if new_xyz is not None else None
+        feature = feats[-1].reshape(B, -1)
+        logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, B, MAX_ROWS)]
+        return feats, logits[0] if len(logits) == 1 else torch.cat(logits)

@@ -1,0 +1,161 @@
+"""Evaluation-mode restatement of PointConv (misc/pointconv_utils.py) in plain torch, fp64 by default: one k-NN level up to the
+contraction, a level's Linear, the group_all level, the whole classifier.  Index lists, centres and densities are arguments, so
+sampling is not part of what is compared.  A "stack" is a list of layers ``(W [out, in], scale [out], shift [out])``: a layer is
+``act(scale * (x W^T) + shift)``; ``stack_of(mlp)`` reads one from a PointwiseMLP's parameters and running statistics in fp64 (conv
+bias folded into the shift).  Not a test file."""
+import torch
+
+
+def act(x, slope):
+    return torch.where(x > 0, x, x * slope)
+
+
+def consts64(mlp, l):
+    W = mlp.weights[l].detach().double()
+    bias = None if mlp.biases is None else mlp.biases[l].detach().double()
+    if mlp.bn:
+        rm, rv = getattr(mlp, f"running_mean_{l}").double(), getattr(mlp, f"running_var_{l}").double()
+        scale = mlp.gammas[l].detach().double() / torch.sqrt(rv + mlp.eps)
+        shift = mlp.betas[l].detach().double() - scale * rm
+        if bias is not None:
+            shift = shift + scale * bias
+    else:
+        scale = torch.ones_like(W[:, 0])
+        shift = torch.zeros_like(W[:, 0]) if bias is None else bias
+    return W, scale, shift
+
+
+def stack_of(mlp):
+    return [consts64(mlp, l) for l in range(mlp.n_layers)]
+
+
+def granule(t):
+    """The largest power of two that divides every entry of ``t`` (as a float; 1.0 for an all-zero tensor)."""
+    t = t.double()
+    for k in range(-8, 60):
+        s = t * 2.0 ** k
+        if bool((s == s.round()).all()):
+            return 2.0 ** -k
+    raise ValueError("entries are not on a binary grid")
+
+
+def run_stack(layers, x, slope, dtype, audit=None):
+    """``audit`` (a list): per layer, (largest sum of |products| of any dot product) / (granule of the products) -- below 2^24 every
+    partial sum of the layer, in any order, is an fp32 number."""
+    for W, scale, shift in layers:
+        W, scale, shift = W.to(dtype), scale.to(dtype), shift.to(dtype)
+        if audit is not None:
+            audit.append(float((x.abs().double() @ W.abs().double().t()).max()) / (granule(x) * granule(W)))
+        x = act(scale * (x @ W.t()) + shift, slope)
+    return x
+
+
+def level(feat, wn, dn, xyz, new_xyz, points, idx, density, slope=0.0, dtype=torch.float64, audit=None):
+    """One k-NN level up to and including the contraction (misc/pointconv_utils.py:361-394 under net.eval()): xyz [B,N,3], new_xyz
+    [B,S,3], points [B,N,D] or None, idx [B,S,ns], density [B,N] (raw) -> [B, S, C3 * 16] with column c*16 + m."""
+    B, S, ns = idx.shape
+    bidx = torch.arange(B, device=idx.device).view(B, 1, 1)
+    il = idx.long()
+    d = xyz.to(dtype)[bidx, il] - new_xyz.to(dtype).unsqueeze(2)
+    x = d if points is None else torch.cat([d, points.to(dtype)[bidx, il]], dim=-1)
+    z = run_stack(feat, x, slope, dtype, audit)
+    w = run_stack(wn, d, 0.0, dtype, audit)
+    rho = run_stack(dn, density.to(dtype)[bidx, il].unsqueeze(-1), 0.0, dtype, audit)          # [B,S,ns,1]
+    rw = rho * w
+    if audit is not None:
+        audit.append(float(torch.matmul(z.abs().double().transpose(2, 3), rw.abs().double()).max()) / (granule(z) * granule(rw)))
+    return torch.matmul(z.transpose(2, 3), rw).reshape(B, S, -1)
+
+
+def group_all_level(feat, wn, dn, xyz, points, density, slope=0.0, dtype=torch.float64):
+    """The group_all level up to the contraction: one group of all N points, coordinates relative to the centroid -> [B, 1, C3 * 16]."""
+    B, N, _ = xyz.shape
+    local = xyz.to(dtype) - xyz.to(dtype).mean(dim=1, keepdim=True)
+    x = local if points is None else torch.cat([local, points.to(dtype)], dim=-1)
+    z = run_stack(feat, x, slope, dtype)
+    rw = run_stack(dn, density.to(dtype).unsqueeze(-1), 0.0, dtype) * run_stack(wn, local, 0.0, dtype)
+    return torch.matmul(z.transpose(1, 2), rw).reshape(B, 1, -1)
+
+
+def head(seq, x):
+    x = x.double()
+    for mod in seq:
+        if isinstance(mod, torch.nn.Linear):
+            x = x @ mod.weight.double().t() + (0 if mod.bias is None else mod.bias.double())
+        elif isinstance(mod, torch.nn.BatchNorm1d):
+            x = (x - mod.running_mean.double()) / torch.sqrt(mod.running_var.double() + mod.eps) * mod.weight.double() + mod.bias.double()
+        elif isinstance(mod, torch.nn.ReLU):
+            x = x.clamp(min=0)
+    return x
+
+
+def network(net, xyz, levels):
+    """fp64 evaluation of PointConvDensityClsSsg on ``levels`` = [(new_xyz | None, [(idx | None, density)])] (what
+    ``net.precompute_sampling(...)["levels"]`` holds); xyz [B,N,3] -> ([sa1, sa2, sa3 features, channel-last], logits)."""
+    pts, points, feats = xyz, None, []
+    for sa, (new_xyz, ((idx, density),)) in zip((net.sa1, net.sa2, net.sa3), levels):
+        stacks = (stack_of(sa.mlp), stack_of(sa.weightnet.mlp), stack_of(sa.densitynet.mlp))
+        if sa.group_all:
+            out = group_all_level(*stacks, pts, points, density, sa.mlp.slope)
+        else:
+            out = level(*stacks, pts, new_xyz, points, idx, density, sa.mlp.slope)
+        points = run_stack(stack_of(sa.linear), out, sa.linear.slope, torch.float64)
+        feats.append(points)
+        pts = new_xyz
+    mods = [net.fc1, net.bn1, net.relu, net.drop1, net.fc2, net.bn2, net.relu, net.drop2, net.fc3]
+    return feats, head(mods, points.reshape(points.shape[0], -1))
+
+
+# ------------------------------------------------------------------------------------------------- cases of the level kernel
+def knn_lists(B, N, m, ns, g):
+    """Random neighbour lists from [0, N) with 0 and N - 1 forced in."""
+    idx = torch.randint(0, N, (B, m, ns), generator=g, dtype=torch.int32)
+    idx[0, 0, 0], idx[-1, -1, -1] = 0, N - 1
+    return idx
+
+
+def _sparse_weight(cout, cin, values, g, nnz=2):
+    """[cout, cin] with ``nnz`` nonzeros per row drawn from ``values``."""
+    W = torch.zeros(cout, cin, dtype=torch.float64)
+    vals = torch.tensor(values, dtype=torch.float64)
+    for r in range(cout):
+        cols = torch.randperm(cin, generator=g)[:min(nnz, cin)]
+        W[r, cols] = vals[torch.randint(0, len(values), (len(cols),), generator=g)]
+    return W
+
+
+def exact_case(ns, widths, D, B, N, m, seed):
+    """Exactly representable data for one level: coordinates and densities on a 1/8 grid (densities in (0, 3]), weights in
+    {-1, -1/2, 1/2, 1} (the last layer of every net: {-1, 1}) with two nonzeros per row, scale = 1, shifts on the 1/8 grid, point
+    features on a 1/2 grid.  Every product and partial sum of the level is then an fp32 number (``level(..., audit=)`` measures
+    the margin), so fp32 arithmetic in any order gives the fp64 result.  -> dict of CPU fp64 tensors and stacks."""
+    g = torch.Generator().manual_seed(seed)
+    half, unit = [-1.0, -0.5, 0.5, 1.0], [-1.0, 1.0]
+
+    def stack(spec):
+        layers = []
+        for i in range(1, len(spec)):
+            W = _sparse_weight(spec[i], spec[i - 1], unit if i == len(spec) - 1 else half, g)
+            if i == 1 and spec[0] > 3:                       # the feature MLP's first layer: two nonzeros on xyz, two on the features
+                W = torch.cat([_sparse_weight(spec[1], 3, half, g), _sparse_weight(spec[1], spec[0] - 3, half, g)], dim=1)
+            shift = torch.randint(-2, 5, (spec[i],), generator=g).double() / 8
+            if spec[i] == 1:                                 # the DensityNet's one output: kept alive (rho = 0 would erase the level)
+                W, shift = W.abs(), shift.abs() + 0.125
+            layers.append((W, torch.ones(spec[i], dtype=torch.float64), shift))
+        return layers
+
+    c = {"xyz": torch.randint(0, 9, (B, N, 3), generator=g).double() / 8,
+         "new_xyz": torch.randint(0, 9, (B, m, 3), generator=g).double() / 8,
+         "points": None if D == 0 else torch.randint(-2, 3, (B, N, D), generator=g).double() / 2,
+         "density": torch.randint(1, 25, (B, N), generator=g).double() / 8,
+         "idx": knn_lists(B, N, m, ns, g),
+         "feat": stack([3 + D] + list(widths)), "wn": stack([3, 8, 8, 16]), "dn": stack([1, 8, 8, 1])}
+    return c
+
+
+def pack_nets(wn, dn, size):
+    """The two small nets' stacks as the packed buffer of pcl_pointconv_level_infer_f32 (fp32, CPU)."""
+    flat = torch.cat([t.reshape(-1) for layers in (wn, dn) for layer in layers for t in layer]).float()
+    out = torch.zeros(size)
+    out[:flat.numel()] = flat
+    return out

@@ -29,6 +29,11 @@ to profiles/infer_pointnet_partseg_bench_line.json; with ``--ragged`` the four f
 distance and the per-point top-1 agreement of the two precisions); the line goes to
 profiles/infer_pointnet_partseg_bf16_bench_line.json instead.
 
+``--nets pointconv`` compares ``net.eval()`` under ``no_grad`` with ``FrozenPointConv(net)`` (B in {32, 256}, N = 1024; both forms read the
+same dense [B,3,N] tensor and the SAME ``net.precompute_sampling`` handle, so the index-producing kernels are in neither), with the
+peak memory of both and, per fused level, the time of the ``pcl_pointconv_level_infer_f32`` call between two device events
+(``level_kernel_ms``, with its flops: TF/s against the fp32 MFMA peak); the line goes to profiles/infer_pointconv_bench_line.json.
+
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
 (a) ``dense`` frozen at N, (b) ``ragged_full`` with every length = N, (c) ``ragged`` with the drawn lengths, (d) ``loop``: B calls
@@ -93,6 +98,25 @@ def _pointnet_fp64(net, x_cf, chunk=16):
     return feat, linear(net.linear2, h.clamp(min=0.0))
 
 
+def _pointconv_level_times(fwd, repeats=5):
+    """Per fused level of a FrozenPointConv forward: the pcl_pointconv_level_infer_f32 call between two device events (average of
+    ``repeats`` forwards; the events' own dispatch gaps are inside), its flops and the TF/s they give."""
+    from pointcloudlib_amd import _lib
+    timer = _lib.KernelTimer(names=["pcl_pointconv_level_infer_f32"])
+    _lib.PROFILER = timer
+    try:
+        for _ in range(repeats):
+            fwd()
+        torch.cuda.synchronize()
+    finally:
+        _lib.PROFILER = None
+    out = {}
+    for (_, tag), r in timer.summary().items():
+        out[tag] = {"ms": round(r["avg_ms"], 4), "gflop": round(r["algo_flops"] / 1e9, 2),
+                    "tflops": round(r["algo_flops"] / (r["avg_ms"] * 1e-3) / 1e12, 1)}
+    return out
+
+
 def _ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16=None):
     """The four forms of --ragged for one net and batch (same window estimator as the dense rows)."""
     import numpy as np
@@ -140,7 +164,7 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, nargs="+", default=None, help="default: 32 256 (cls), 16 64 (part-seg, pointnet_partseg), 8 32 256 (pointnet)")
-    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg", "pointnet", "pointnet_partseg"])
+    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg", "pointnet", "pointnet_partseg", "pointconv"])
     ap.add_argument("--points", type=int, default=None, help="default: 1024 (cls), 2048 (part-seg)")
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
     ap.add_argument("--precision", nargs="+", default=["fp32"], choices=["fp32", "bf16"],
@@ -153,9 +177,12 @@ def main():
     from pointcloudlib_amd.inference import frozen
     from pointcloudlib_amd.networks.cls.pointnet2 import PointNet2_cls, PointNetMSG
     dev = torch.device("cuda")
-    cls_only = all(k in ("ssg", "msg", "pointnet") for k in a.nets)
+    cls_only = all(k in ("ssg", "msg", "pointnet", "pointconv") for k in a.nets)
     pointnet_only = all(k == "pointnet" for k in a.nets)
     pn_partseg_only = all(k == "pointnet_partseg" for k in a.nets)
+    pointconv_only = all(k == "pointconv" for k in a.nets)
+    if a.ragged and "pointconv" in a.nets:
+        raise SystemExit("bench_infer.py: PointConv's sampling has no ragged form")
     res = {"N": (a.points or 1024) if cls_only else (a.points or 2048), "windows": a.windows, "iters": a.iters, "cases": []}
     if a.ragged:
         del res["N"]                 # every --ragged case carries its own N (classifiers and part-seg nets share one line)
@@ -173,6 +200,10 @@ def main():
             from pointcloudlib_amd.inference import FrozenPointNet
             from pointcloudlib_amd.networks.cls.pointnet import PointNet
             net = PointNet().to(dev).eval()
+        elif kind == "pointconv":
+            from pointcloudlib_amd.inference import FrozenPointConv
+            from pointcloudlib_amd.networks.cls.pointconv import PointConvDensityClsSsg
+            net = PointConvDensityClsSsg().to(dev).eval()
         elif pn_seg:
             from pointcloudlib_amd.inference import FrozenPointNetPartseg
             from pointcloudlib_amd.networks.seg.pointnet_partseg import PointNet_partseg
@@ -190,6 +221,9 @@ def main():
 
                 def fnet_bf16(xyz, nrm, lengths=None):
                     return fpn16(xyz.transpose(1, 2), lengths)
+        elif kind == "pointconv":
+            fpc = FrozenPointConv(net)
+            fnet_bf16 = None                                  # (fp32 only)
         elif pn_seg:
             fps = FrozenPointNetPartseg(net)
 
@@ -236,6 +270,17 @@ def main():
                 def frozen_bf16_fwd():
                     return fpn16(x_cf)
 
+            if kind == "pointconv":
+                x_cf = xyz.transpose(1, 2).contiguous()       # the network's input layout, made once: both forms read it
+                samp = net.precompute_sampling(x_cf)          # ... and one sampling handle
+
+                def eval_fwd(net=net):
+                    with torch.no_grad():
+                        return net(x_cf, sampling=samp)
+
+                def frozen_fwd():
+                    return fpc(x_cf, sampling=samp)
+
             if pn_seg:
                 x_cf = xyz.transpose(1, 2).contiguous()       # the network's input layout, made once: both forms read it
 
@@ -278,7 +323,7 @@ def main():
                 case["speedup"] = round(case["eval_ms"] / case["frozen_ms"], 3)
                 if seg:
                     case["speedup_vs_acc0"] = round(case["eval_acc0_ms"] / case["frozen_ms"], 3)
-                if seg or pn_seg:
+                if seg or pn_seg or kind == "pointconv":
                     case["mem_ratio"] = round(case["eval_peak_mib"] / max(case["frozen_peak_mib"], 0.1), 1)
                 with torch.no_grad():
                     case["max_abs_logit_diff"] = float((eval_fwd() - frozen_fwd()).abs().max())
@@ -295,6 +340,8 @@ def main():
                         case[f"feature_err_fp64_{tag}"] = float((feat.double() - f64).abs().max())
                         case[f"logit_err_fp64_{tag}"] = float((logits.double() - l64).abs().max())
                     case["top1_agreement_bf16_fp64"] = float((lb.argmax(1) == l64.argmax(1)).float().mean())
+            if kind == "pointconv":
+                case["level_kernel_ms"] = _pointconv_level_times(frozen_fwd)
             res["cases"].append(case)
     print(json.dumps(res))
     if "bf16" in a.precision and not a.ragged and not ((pointnet_only or pn_partseg_only) and a.frozen_only):
@@ -306,6 +353,10 @@ def main():
     elif pointnet_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "infer_pointnet_ragged_bench_line.json" if a.ragged else "infer_pointnet_bench_line.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
+    elif pointconv_only and not a.frozen_only:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "infer_pointconv_bench_line.json"), "w") as f:
             f.write(json.dumps(res) + "\n")
     elif pn_partseg_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
