@@ -880,6 +880,20 @@ int pcl_pointconv_level_infer_f32(const float* xyz, const float* new_xyz, const 
                                   const float* density, const int32_t* idx, int B, int N, int m, int ns, int L, const int32_t* widths,
                                   const float* const* W, const float* const* scale, const float* const* shift, float slope,
                                   const float* nets, int M, float* out, int ldo, void* stream);
+/* No reference counterpart: the same level with bf16 matrix operands (FrozenPointConv(net, precision="bf16")).  Arguments, host
+ * checks, preconditions and the "no kernel" error of pcl_pointconv_level_infer_f32, except that W[1] and W[2] are bf16
+ * [C_l, C_{l-1}] dense, 16-byte aligned; Wx, Uf, scale, shift and nets stay fp32.  Numerics: the row records, layer 1 (the fp32
+ * fmaf chain plus Uf) and its epilogue, the WeightNet, the DensityNet and rw = rho * w are exactly the expressions of
+ * pcl_pointconv_level_infer_f32; z_1 is rounded to nearest even to bf16; y_2 and y_3 are bf16 x bf16 products accumulated in fp32
+ * (v_mfma_f32_32x32x16_bf16, k-blocks of 16 ascending); the epilogues act(scale * y + shift) run in fp32; z_2 is rounded to bf16;
+ * z_3 is never rounded: it goes to the contraction as fp32, and the contraction is the fp32 v_mfma_f32_16x16x4_f32 form of
+ * pcl_pointconv_level_infer_f32 with s ascending.  A group's result depends only on its own rows (not on B, on the group's place in
+ * the launch or on how many groups a workgroup owns); no atomics, two calls give identical bits; all 16 * C3 outputs of every group
+ * are written, in fp32.  pcl_pointconv_level_infer_supported and pcl_pointconv_level_infer_group_tile answer for both precisions. */
+int pcl_pointconv_level_infer_bf16_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
+                                       const float* density, const int32_t* idx, int B, int N, int m, int ns, int L,
+                                       const int32_t* widths, const void* const* W, const float* const* scale, const float* const* shift,
+                                       float slope, const float* nets, int M, float* out, int ldo, void* stream);
 
 /* ---- Frozen inference: one PointNet++ feature-propagation level in evaluation mode as ONE launch ------------------------
  * misc/ops.py:54-107 (PointNetFeaturePropagation.execute: 3-NN inverse-distance interpolation, concat with the skip features,

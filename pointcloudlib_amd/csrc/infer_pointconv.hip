@@ -27,9 +27,13 @@
 // Numeric contract (include/pcl_hip.h): a group's result depends only on its own rows (not on B, on the group's place in the
 // launch or on GT); no atomics, two calls give identical bits; out is fully defined for every group.
 //
-// The kernel is templated on the tile's element type as infer.hip's is (BF16: X1 / X2 as bf16, layers 2 and 3 on
-// v_mfma_f32_32x32x16_bf16); only the fp32 form is instantiated and has an entry point.  The BF16 branches have never been compiled:
-// the overlay of Z on a bf16 X1 | X2 (tile_bytes with sizeof(XT) == 2) and the bf16 tiles' stores are unchecked text until then.
+// The kernel is templated on the tile's element type as infer.hip's is.  The bf16 instantiation (pcl_pointconv_level_infer_bf16_f32)
+// holds X1 / X2 as bf16 (rows of C + 8 elements: an odd number of 16-byte pieces, infer_mfma.h) and runs layers 2 and 3 on
+// v_mfma_f32_32x32x16_bf16, k-blocks of 16 ascending: z1 and z2 are rounded to nearest even when they are stored, W[1] and W[2] are
+// bf16; row records, layer 1, the small nets, rw, every epilogue, Z (z3, never rounded) and the contraction are the fp32 text
+// above.  Z is larger than X1 | X2 of either element type, so tile_bytes, the place of RW and the LDS totals are those of the fp32
+// form, and the barrier in front of the deposit guards the same overlay.
+// Layer 1 of this form is written in single-lane steps (lone(), below).
 #include <type_traits>
 
 #include "common.h"
@@ -74,6 +78,16 @@ struct PointConvShape {
 };
 
 __device__ __forceinline__ float relu_bn(float y, float sc, float sh) { return fmaxf(sc * y + sh, 0.f); }
+
+// Keeps a value out of the packed two-channel fp32 instructions (v_pk_fma_f32, v_pk_mul_f32, v_pk_add_f32) that the compiler
+// otherwise forms from a thread's four layer-1 channels.  In the 128/128/256 bf16 kernel, with two workgroups on a compute unit, a
+// chain of such instructions two apart now and then lost one step in the low channel of lanes 48 - 63 (dumps of X1: the y term of
+// layer 1 missing from channels 4k or 4k + 2 >= 64 of one odd row, 2 to 9 groups of 4101 in a launch).  The
+// value is the same; only the instruction that computes it differs.
+__device__ __forceinline__ float lone(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
 
 // one row of the two small nets: the four outputs m0 .. m0 + 3 of the WeightNet times rho.  cn: the packed constants in LDS.
 __device__ __forceinline__ void small_nets(const float* cn, float dx, float dy, float dz, float dens, int m0, float (&rw)[4]) {
@@ -180,8 +194,17 @@ __global__ __launch_bounds__(NT, 2) void pointconv_level_infer_kernel(const Poin
             float z[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float y = fmaf(wx[i][2], L.z, fmaf(wx[i][1], L.y, fmaf(wx[i][0], L.x, u[i])));
-                z[i] = act(sc1[i] * y + sh1[i], a.slope);
+                if constexpr (BF16) {              // the same chain, every step a single-lane instruction (lone(), above)
+                    float y = lone(fmaf(wx[i][0], L.x, u[i]));
+                    y = lone(fmaf(wx[i][1], L.y, y));
+                    y = lone(fmaf(wx[i][2], L.z, y));
+                    const float v = lone(lone(sc1[i] * y) + sh1[i]);
+                    const float n = lone(v * a.slope);
+                    z[i] = v > 0.f ? v : n;
+                } else {
+                    const float y = fmaf(wx[i][2], L.z, fmaf(wx[i][1], L.y, fmaf(wx[i][0], L.x, u[i])));
+                    z[i] = act(sc1[i] * y + sh1[i], a.slope);
+                }
             }
             tile_store4(X1 + (size_t)r * LD1 + c4, z);
         }
@@ -255,11 +278,11 @@ int pointconv_group_tile(int ns, int G) {
     return tiles * gpt;
 }
 
-template <int NS, int C1, int C2, int C3>
+template <int NS, int C1, int C2, int C3, bool BF16>
 int launch_pointconv(const char* fn, PointConvArgs a, hipStream_t st) {
-    using S = PointConvShape<C1, C2, C3, false>;
+    using S = PointConvShape<C1, C2, C3, BF16>;
     a.GT = pointconv_group_tile(NS, a.G);
-    auto kern = pointconv_level_infer_kernel<NS, C1, C2, C3, false>;
+    auto kern = pointconv_level_infer_kernel<NS, C1, C2, C3, BF16>;
     if (int rc = lds_opt_in(kern, S::lds_bytes, fn)) return rc;
     const int blocks = (a.G + a.GT - 1) / a.GT;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(NT), S::lds_bytes, st, a);
@@ -272,6 +295,36 @@ int pointconv_shape_id(int ns, int L, int C1, int C2, int C3, int M) {
     if (ns == 32 && C1 == 64 && C2 == 64 && C3 == 128) return 0;
     if (ns == 64 && C1 == 128 && C2 == 128 && C3 == 256) return 1;
     return -1;
+}
+
+// both precisions: every check runs before any HIP call.  W[1], W[2]: fp32 (BF16 false) or bf16 (true) [C_l][C_{l-1}]
+template <bool BF16>
+int pointconv_level_infer(const char* fn, const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
+                          const float* density, const int32_t* idx, int B, int N, int m, int ns, int L, const int32_t* widths,
+                          const void* const* W, const float* const* scale, const float* const* shift, float slope, const float* nets,
+                          int M, float* out, int ldo, void* stream) {
+    PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", fn);
+    PCL_REQUIRE(L >= 1 && L <= 4, "%s: L=%d", fn, L);
+    const int sid = L == 3 ? pointconv_shape_id(ns, L, widths[0], widths[1], widths[2], M) : -1;
+    PCL_REQUIRE(sid >= 0, "%s: no kernel for ns=%d L=%d widths %d/%d/%d M=%d (pcl_pointconv_level_infer_supported)", fn, ns, L, widths[0],
+                L > 1 ? widths[1] : 0, L > 2 ? widths[2] : 0, M);
+    PCL_REQUIRE(xyz && new_xyz && Wx && density && idx && nets && out, "%s: null pointer", fn);
+    PCL_REQUIRE(ldw >= 3, "%s: ldw=%d", fn, ldw);
+    PCL_REQUIRE(B >= 1 && N >= 1 && m >= 1, "%s: bad sizes B=%d N=%d m=%d", fn, B, N, m);
+    PCL_REQUIRE((size_t)B * m < (1u << 31) && (size_t)B * N < (1u << 31), "%s: too many groups / points", fn);
+    for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", fn, l);
+    PCL_REQUIRE(ldo >= widths[2] * M && ldo % 4 == 0, "%s: ldo=%d for %d columns (a multiple of 4)", fn, ldo, widths[2] * M);
+    // Uf, W[1], W[2] and out are moved in 16-byte pieces: their alignment is the caller's precondition (include/pcl_hip.h), held by
+    // pointcloudlib_amd/inference.py before the call; there is no other path to choose here
+    PointConvArgs a = {};
+    a.xyz = xyz; a.new_xyz = new_xyz; a.Uf = Uf; a.Wx = Wx; a.ldw = ldw; a.density = density; a.idx = idx;
+    a.G = B * m; a.N = N; a.m = m;
+    a.W2 = static_cast<const float*>(W[1]); a.W3 = static_cast<const float*>(W[2]);
+    a.sc1 = scale[0]; a.sh1 = shift[0]; a.sc2 = scale[1]; a.sh2 = shift[1]; a.sc3 = scale[2]; a.sh3 = shift[2];
+    a.slope = slope; a.nets = nets; a.out = out; a.ldo = ldo;
+    hipStream_t st = as_stream(stream);
+    if (sid == 0) return launch_pointconv<32, 64, 64, 128, BF16>(fn, a, st);
+    return launch_pointconv<64, 128, 128, 256, BF16>(fn, a, st);
 }
 
 }  // namespace
@@ -291,27 +344,15 @@ extern "C" int pcl_pointconv_level_infer_f32(const float* xyz, const float* new_
                                              const int32_t* widths, const float* const* W, const float* const* scale,
                                              const float* const* shift, float slope, const float* nets, int M, float* out, int ldo,
                                              void* stream) {
-    const char* fn = "pcl_pointconv_level_infer_f32";
-    PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", fn);
-    PCL_REQUIRE(L >= 1 && L <= 4, "%s: L=%d", fn, L);
-    const int sid = L == 3 ? pointconv_shape_id(ns, L, widths[0], widths[1], widths[2], M) : -1;
-    PCL_REQUIRE(sid >= 0, "%s: no kernel for ns=%d L=%d widths %d/%d/%d M=%d (pcl_pointconv_level_infer_supported)", fn, ns, L, widths[0],
-                L > 1 ? widths[1] : 0, L > 2 ? widths[2] : 0, M);
-    PCL_REQUIRE(xyz && new_xyz && Wx && density && idx && nets && out, "%s: null pointer", fn);
-    PCL_REQUIRE(ldw >= 3, "%s: ldw=%d", fn, ldw);
-    PCL_REQUIRE(B >= 1 && N >= 1 && m >= 1, "%s: bad sizes B=%d N=%d m=%d", fn, B, N, m);
-    PCL_REQUIRE((size_t)B * m < (1u << 31) && (size_t)B * N < (1u << 31), "%s: too many groups / points", fn);
-    for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", fn, l);
-    PCL_REQUIRE(ldo >= widths[2] * M && ldo % 4 == 0, "%s: ldo=%d for %d columns (a multiple of 4)", fn, ldo, widths[2] * M);
-    // Uf, W[1], W[2] and out are moved in 16-byte pieces: their alignment is the caller's precondition (include/pcl_hip.h), held by
-    // pointcloudlib_amd/inference.py before the call; there is no other path to choose here
-    PointConvArgs a = {};
-    a.xyz = xyz; a.new_xyz = new_xyz; a.Uf = Uf; a.Wx = Wx; a.ldw = ldw; a.density = density; a.idx = idx;
-    a.G = B * m; a.N = N; a.m = m;
-    a.W2 = W[1]; a.W3 = W[2];
-    a.sc1 = scale[0]; a.sh1 = shift[0]; a.sc2 = scale[1]; a.sh2 = shift[1]; a.sc3 = scale[2]; a.sh3 = shift[2];
-    a.slope = slope; a.nets = nets; a.out = out; a.ldo = ldo;
-    hipStream_t st = as_stream(stream);
-    if (sid == 0) return launch_pointconv<32, 64, 64, 128>(fn, a, st);
-    return launch_pointconv<64, 128, 128, 256>(fn, a, st);
+    return pointconv_level_infer<false>("pcl_pointconv_level_infer_f32", xyz, new_xyz, Uf, Wx, ldw, density, idx, B, N, m, ns, L, widths,
+                                        reinterpret_cast<const void* const*>(W), scale, shift, slope, nets, M, out, ldo, stream);
+}
+
+extern "C" int pcl_pointconv_level_infer_bf16_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
+                                                  const float* density, const int32_t* idx, int B, int N, int m, int ns, int L,
+                                                  const int32_t* widths, const void* const* W, const float* const* scale,
+                                                  const float* const* shift, float slope, const float* nets, int M, float* out, int ldo,
+                                                  void* stream) {
+    return pointconv_level_infer<true>("pcl_pointconv_level_infer_bf16_f32", xyz, new_xyz, Uf, Wx, ldw, density, idx, B, N, m, ns, L,
+                                       widths, W, scale, shift, slope, nets, M, out, ldo, stream);
 }

@@ -41,7 +41,11 @@ section 24): per k-NN level the per-point product ``Uf = points W0[:, 3:]^T`` (s
 density-weighted contraction with its activations in LDS -- the ``[B*S, 16 C]`` contraction output is the only large tensor a
 level writes -- then the level's ``Linear(16 C -> C)`` as a stats-free GEMM of the family ``net.eval()`` selects, with the eval
 constants.  The ``group_all`` level runs the stats-free GEMMs and ``pcl_pointconv_contract_bn_f32``; the head runs the eval-mode
-head kernels.  fp32 only; constructed directly."""
+head kernels.  Constructed directly.  ``FrozenPointConv(net, precision="bf16")`` runs every fused level launch as
+``pcl_pointconv_level_infer_bf16_f32``: layers 2 and 3 of the feature MLP take bf16 operands (activations rounded to nearest even,
+weights snapshot as bf16 in ``refresh()``) and accumulate in fp32; ``Uf``, layer 1, the WeightNet, the DensityNet, the epilogues,
+``z3``, the contraction and its output stay fp32, and so do the level's Linear, the ``group_all`` level, ``"module"`` fallbacks
+and the head."""
 import copy
 import ctypes
 
@@ -832,12 +836,15 @@ def _pointconv_fusable(sa, D):
 
 
 class _FusedPointConv(_SegStack):
-    """Snapshot of one k-NN PointConv level for pcl_pointconv_level_infer_f32: the feature MLP (first layer folded), the packed small
-    nets and the level's Linear."""
+    """Snapshot of one k-NN PointConv level for pcl_pointconv_level_infer_f32 (or, ``precision="bf16"``,
+    pcl_pointconv_level_infer_bf16_f32): the feature MLP (first layer folded), the packed small nets and the level's Linear."""
 
-    def __init__(self, sa, D):
+    def __init__(self, sa, D, precision="fp32"):
         mlp = sa.mlp
-        super().__init__([(mlp, l) for l in range(mlp.n_layers)], first=None)
+        super().__init__([(mlp, l) for l in range(mlp.n_layers)], first=None, bf16=precision == "bf16")
+        self.precision = precision
+        self.entry = "pcl_pointconv_level_infer_bf16_f32" if precision == "bf16" else "pcl_pointconv_level_infer_f32"
+        self.operands = self.Ws_bf16 if precision == "bf16" else self.Ws           # what c_W points at
         W0 = mlp.weights[0].detach().float().contiguous().clone()
         self.D, self.slope = D, float(mlp.slope)
         self.W0, self.ldw = W0, W0.shape[1]                            # Wx = W0[:, :3]: the kernel reads it with the row stride ldw
@@ -857,10 +864,10 @@ class _FusedPointConv(_SegStack):
             _lib.call("pcl_linear_fwd_rows_f32", _p(points.reshape(B * N, self.D)), _p(self.Wf), None, None, None, 0.0, B * N, self.D, C1, _p(Uf),
                       None, None, None, st, tag=f"pt{self.D}x{C1}")
         out = torch.empty((B * S, POINTCONV_M * C3), dtype=torch.float32, device=xyz.device)
-        if any(t is not None and t.data_ptr() % 16 for t in (Uf, out, *self.Ws[1:])):      # the entry point's precondition (pcl_hip.h)
-            raise ValueError("pcl_pointconv_level_infer_f32: Uf, the weights and out must be 16-byte aligned")
+        if any(t is not None and t.data_ptr() % 16 for t in (Uf, out, *self.operands[1:])):      # the entry point's precondition (pcl_hip.h)
+            raise ValueError(f"{self.entry}: Uf, the weights and out must be 16-byte aligned")
         rows = B * S * ns
-        _lib.call("pcl_pointconv_level_infer_f32", _p(xyz), _p(new_xyz), _p(Uf), _p(self.W0), self.ldw, _p(density), _p(idx), B, N, S, ns, self.L,
+        _lib.call(self.entry, _p(xyz), _p(new_xyz), _p(Uf), _p(self.W0), self.ldw, _p(density), _p(idx), B, N, S, ns, self.L,
                   self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(self.nets), POINTCONV_M, _p(out), out.shape[1], st,
                   algo_flops=2 * rows * (3 * C1 + C1 * self.widths[1] + self.widths[1] * C3 + POINTCONV_M * C3 + 296),
                   tag=f"pointconv{ns}x{C3}")
@@ -934,12 +941,17 @@ class FrozenPointConv:
     ``fnet.levels`` names the plan per level: ``"fused"`` for a k-NN level whose shape has a kernel
     (``pcl_pointconv_level_infer_supported``; module docstring), ``"all"`` for a ``group_all`` level of the usual small nets,
     ``"module"`` otherwise -- an eval-mode copy of the level's own module runs.  ``refresh()`` re-reads weights and running
-    statistics; ``net`` itself is never modified (parameters, buffers, ``training`` flags).  fp32 only."""
+    statistics; ``net`` itself is never modified (parameters, buffers, ``training`` flags).  ``precision``: "fp32", or "bf16" for
+    bf16 matrix operands in layers 2 and 3 of the fused level launches (module docstring); ``fnet.precision`` tells which.
+    ``levels`` does not depend on it, and everything but the fused launches is the same code on the same types."""
 
-    def __init__(self, net):
+    def __init__(self, net, precision="fp32"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"FrozenPointConv: precision must be one of {PRECISIONS}, got {precision!r}")
         if not isinstance(net, PointConvDensityClsSsg):
             raise TypeError(f"FrozenPointConv takes networks.cls.pointconv.PointConvDensityClsSsg, got {type(net).__name__}")
         self.net = net
+        self.precision = precision
         self._copies = {}
         self.refresh()
 
@@ -959,7 +971,7 @@ class FrozenPointConv:
         for name in ("sa1", "sa2", "sa3"):
             sa = getattr(net, name)
             if isinstance(sa, PointConvDensitySetAbstraction) and _pointconv_fusable(sa, D):
-                self.plans.append(("fused", _FusedPointConv(sa, D)))
+                self.plans.append(("fused", _FusedPointConv(sa, D, self.precision)))
             elif (isinstance(sa, PointConvDensitySetAbstraction) and sa.group_all and sa.mlp.bn and sa.mlp.last_act and sa.mlp.spec[0] == 3 + D
                   and _small_nets_ok(sa)):
                 self.plans.append(("all", _PointConvGroupAll(sa, self._copy((name, "linear"), sa.linear))))

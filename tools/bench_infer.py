@@ -33,6 +33,11 @@ profiles/infer_pointnet_partseg_bf16_bench_line.json instead.
 same dense [B,3,N] tensor and the SAME ``net.precompute_sampling`` handle, so the index-producing kernels are in neither), with the
 peak memory of both and, per fused level, the time of the ``pcl_pointconv_level_infer_f32`` call between two device events
 (``level_kernel_ms``, with its flops: TF/s against the fp32 MFMA peak); the line goes to profiles/infer_pointconv_bench_line.json.
+With ``--precision fp32 bf16`` every row also carries ``FrozenPointConv(net, precision="bf16")`` in the same windows
+(``frozen_bf16_ms`` with its window minimum, ``bf16_vs_fp32``, ``bf16_below_fp32_min``, the max-abs logit distance and the top-1
+agreement of the two precisions, recorded and not asserted) and ``level_kernel_ms_bf16``, the same per-level times of the
+``pcl_pointconv_level_infer_bf16_f32`` calls; the line goes to profiles/infer_pointconv_bf16_bench_line.json instead.
+``--frozen_only --precision bf16`` runs the bf16 form alone (for a kernel trace) and writes no file.
 
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
@@ -98,11 +103,11 @@ def _pointnet_fp64(net, x_cf, chunk=16):
     return feat, linear(net.linear2, h.clamp(min=0.0))
 
 
-def _pointconv_level_times(fwd, repeats=5):
-    """Per fused level of a FrozenPointConv forward: the pcl_pointconv_level_infer_f32 call between two device events (average of
-    ``repeats`` forwards; the events' own dispatch gaps are inside), its flops and the TF/s they give."""
+def _pointconv_level_times(fwd, entry="pcl_pointconv_level_infer_f32", repeats=5):
+    """Per fused level of a FrozenPointConv forward: the ``entry`` call between two device events (average of ``repeats`` forwards;
+    the events' own dispatch gaps are inside), its flops and the TF/s they give."""
     from pointcloudlib_amd import _lib
-    timer = _lib.KernelTimer(names=["pcl_pointconv_level_infer_f32"])
+    timer = _lib.KernelTimer(names=[entry])
     _lib.PROFILER = timer
     try:
         for _ in range(repeats):
@@ -223,7 +228,7 @@ def main():
                     return fpn16(xyz.transpose(1, 2), lengths)
         elif kind == "pointconv":
             fpc = FrozenPointConv(net)
-            fnet_bf16 = None                                  # (fp32 only)
+            fnet_bf16 = fpc16 = FrozenPointConv(net, precision="bf16") if "bf16" in a.precision else None
         elif pn_seg:
             fps = FrozenPointNetPartseg(net)
 
@@ -281,6 +286,9 @@ def main():
                 def frozen_fwd():
                     return fpc(x_cf, sampling=samp)
 
+                def frozen_bf16_fwd():
+                    return fpc16(x_cf, sampling=samp)
+
             if pn_seg:
                 x_cf = xyz.transpose(1, 2).contiguous()       # the network's input layout, made once: both forms read it
 
@@ -298,7 +306,7 @@ def main():
                 res["cases"].append(_ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16))
                 continue
             if a.frozen_only:
-                forms = [("frozen", frozen_fwd)]
+                forms = [("frozen", frozen_fwd)] if "fp32" in a.precision or kind != "pointconv" else []
             elif seg:
                 forms = [("eval", eval_fwd), ("eval_acc0", lambda: eval_fwd(net0)), ("frozen", frozen_fwd)]
             else:
@@ -327,7 +335,7 @@ def main():
                     case["mem_ratio"] = round(case["eval_peak_mib"] / max(case["frozen_peak_mib"], 0.1), 1)
                 with torch.no_grad():
                     case["max_abs_logit_diff"] = float((eval_fwd() - frozen_fwd()).abs().max())
-            if fnet_bf16 is not None:
+            if fnet_bf16 is not None and "frozen" in times:
                 case["bf16_vs_fp32"] = round(case["frozen_bf16_ms"] / case["frozen_ms"], 4)
                 case["bf16_below_fp32_min"] = case["frozen_bf16_ms"] < case["frozen_ms_min"]
                 lf, lb = frozen_fwd(), frozen_bf16_fwd()
@@ -340,14 +348,17 @@ def main():
                         case[f"feature_err_fp64_{tag}"] = float((feat.double() - f64).abs().max())
                         case[f"logit_err_fp64_{tag}"] = float((logits.double() - l64).abs().max())
                     case["top1_agreement_bf16_fp64"] = float((lb.argmax(1) == l64.argmax(1)).float().mean())
-            if kind == "pointconv":
+            if kind == "pointconv" and "frozen" in times:
                 case["level_kernel_ms"] = _pointconv_level_times(frozen_fwd)
+            if kind == "pointconv" and fnet_bf16 is not None:
+                case["level_kernel_ms_bf16"] = _pointconv_level_times(frozen_bf16_fwd, "pcl_pointconv_level_infer_bf16_f32")
             res["cases"].append(case)
     print(json.dumps(res))
-    if "bf16" in a.precision and not a.ragged and not ((pointnet_only or pn_partseg_only) and a.frozen_only):
+    if "bf16" in a.precision and not a.ragged and not ((pointnet_only or pn_partseg_only or pointconv_only) and a.frozen_only):
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         name = ("infer_pointnet_bf16_bench_line.json" if pointnet_only else
-                "infer_pointnet_partseg_bf16_bench_line.json" if pn_partseg_only else "infer_bf16_bench_line.json")
+                "infer_pointnet_partseg_bf16_bench_line.json" if pn_partseg_only else
+                "infer_pointconv_bf16_bench_line.json" if pointconv_only else "infer_bf16_bench_line.json")
         with open(os.path.join(ROOT, "profiles", name), "w") as f:
             f.write(json.dumps(res) + "\n")
     elif pointnet_only and not a.frozen_only:
