@@ -880,6 +880,27 @@ int pcl_pointconv_level_infer_f32(const float* xyz, const float* new_xyz, const 
                                   const float* density, const int32_t* idx, int B, int N, int m, int ns, int L, const int32_t* widths,
                                   const float* const* W, const float* const* scale, const float* const* shift, float slope,
                                   const float* nets, int M, float* out, int ldo, void* stream);
+/* The same launch for the k-NN levels of networks/seg/pointconv_partseg.py (FrozenPointConvPartseg): a feature MLP of L = 2 or 3
+ * layers, 16, 32 or 64 neighbours.  Arguments, host checks (all before any HIP call), preconditions (Uf, W_l with l >= 1 and out
+ * 16-byte aligned; idx in [0, N)) and the numeric contract of pcl_pointconv_level_infer_f32: z_L takes the place of z_3,
+ *     out[g * ldo + c*16 + m] = sum_s z_L[s, c] * (rho[s] * w[s, m]),   c < widths[L-1],
+ * all 16 * widths[L-1] outputs of every group are written and none beyond them; a group's result depends only on its own rows;
+ * no atomics, two calls give identical bits.  An interpolation level (PointConvDensitySetInterpolation) is this launch with
+ * xyz = xyz1, new_xyz = xyz1[fps_idx], m = N and Uf formed from the interpolated features.
+ * In the queries C1 = widths[0], C2 = widths[1] and C3 = widths[L-1] (so C2 = C3 at L = 2).  Kernels exist, with M = 16, for
+ *     ns = 32, L = 3: 32/32/64, 64/64/128, 128/128/256        ns = 64, L = 3: 128/128/256
+ *     ns = 16, L = 2: 256/256, 128/128                        ns = 16, L = 3: 128/128/128
+ * and for nothing else (256/256/512 at ns = 32 and 512/512 at ns = 16 do not fit the tile's LDS); any other shape returns
+ * PCL_EINVAL ("no kernel") before any launch.  (32, 64/64/128) and (64, 128/128/256) launch the very kernels of
+ * pcl_pointconv_level_infer_f32.  pcl_pointconv_seg_level_infer_group_tile: as pcl_pointconv_level_infer_group_tile, for ns in
+ * {16, 32, 64} (a multiple of 64 / ns, at most 8 tiles). */
+int pcl_pointconv_seg_level_infer_supported(int ns, int L, int C1, int C2, int C3, int M);
+int pcl_pointconv_seg_level_infer_group_tile(int ns, int G);
+int pcl_pointconv_seg_level_infer_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
+                                      const float* density, const int32_t* idx, int B, int N, int m, int ns, int L,
+                                      const int32_t* widths, const float* const* W, const float* const* scale,
+                                      const float* const* shift, float slope, const float* nets, int M, float* out, int ldo,
+                                      void* stream);
 /* No reference counterpart: the same level with bf16 matrix operands (FrozenPointConv(net, precision="bf16")).  Arguments, host
  * checks, preconditions and the "no kernel" error of pcl_pointconv_level_infer_f32, except that W[1] and W[2] are bf16
  * [C_l, C_{l-1}] dense, 16-byte aligned; Wx, Uf, scale, shift and nets stay fp32.  Numerics: the row records, layer 1 (the fp32

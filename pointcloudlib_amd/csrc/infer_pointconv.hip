@@ -34,6 +34,12 @@
 // above.  Z is larger than X1 | X2 of either element type, so tile_bytes, the place of RW and the LDS totals are those of the fp32
 // form, and the barrier in front of the deposit guards the same overlay.
 // Layer 1 of this form is written in single-lane steps (lone(), below).
+//
+// The kernel is also templated on the feature MLP's layer count L (pcl_pointconv_seg_level_infer_f32: the levels of
+// networks/seg/pointconv_partseg.py).  L = 2 has no step 3: the last layer reads X1, and Z lies over X1 behind the same barrier.
+// At ns = 16 a tile holds four groups and a wave owns all C3 / 16 column blocks of one of them in step 5 (8 or 16 accumulators);
+// a tile with 1, 2 or 3 live groups leaves the other waves out of step 5 (gi < ngt).  A layer of 32 columns is one column block:
+// waves 1 - 3 idle in it.
 #include <type_traits>
 
 #include "common.h"
@@ -66,12 +72,14 @@ struct PointConvArgs {
     float* out; int ldo;
 };
 
-template <int C1, int C2, int C3, bool BF16>
+// L: layers of the feature MLP (3: C1 -> C2 -> C3; 2: C1 -> C3, C2 is not used and there is no X2)
+template <int L, int C1, int C2, int C3, bool BF16>
 struct PointConvShape {
+    static_assert(L == 2 || L == 3, "layers of the feature MLP");
     using XT = std::conditional_t<BF16, __bf16, float>;                    // element of X1 / X2
     static constexpr int LD1 = C1 + row_pad<XT>, LD2 = C2 + row_pad<XT>, LDZ = C3 + 16;
-    static constexpr size_t tile_bytes = sizeof(XT) * ((size_t)RT * LD1 + RT * LD2) > 4 * (size_t)RT * LDZ
-                                             ? sizeof(XT) * ((size_t)RT * LD1 + RT * LD2) : 4 * (size_t)RT * LDZ;
+    static constexpr size_t x_bytes = sizeof(XT) * ((size_t)RT * LD1 + (L == 3 ? RT * LD2 : 0));
+    static constexpr size_t tile_bytes = x_bytes > 4 * (size_t)RT * LDZ ? x_bytes : 4 * (size_t)RT * LDZ;
     // X1 | X2 under Z, RW, row records (d, src, density), the small nets' constants
     static constexpr size_t lds_bytes = tile_bytes + 4 * (size_t)RT * PC_M + 16 * RT + 4 * RT + 4 * RT + 4 * PC_NETS;
     static_assert(lds_bytes <= PC_LDS_CAP, "two workgroups per CU");
@@ -130,9 +138,9 @@ __device__ __forceinline__ void small_nets(const float* cn, float dx, float dy, 
     }
 }
 
-template <int NS, int C1, int C2, int C3, bool BF16>
+template <int NS, int NL, int C1, int C2, int C3, bool BF16>
 __global__ __launch_bounds__(NT, 2) void pointconv_level_infer_kernel(const PointConvArgs a) {
-    using S = PointConvShape<C1, C2, C3, BF16>;
+    using S = PointConvShape<NL, C1, C2, C3, BF16>;
     using XT = typename S::XT;
     constexpr int LD1 = S::LD1, LD2 = S::LD2, LDZ = S::LDZ;
     constexpr int NCB3 = C3 / 32, NJ3 = (NCB3 + 3) / 4;
@@ -142,8 +150,10 @@ __global__ __launch_bounds__(NT, 2) void pointconv_level_infer_kernel(const Poin
     static_assert(RT % NS == 0 && 4 % GPT == 0 && (C3 / 16) % WPG == 0 && NS % 4 == 0, "contraction split");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     XT* X1 = reinterpret_cast<XT*>(smem);                                   // [RT][LD1]
-    XT* X2 = X1 + RT * LD1;                                                 // [RT][LD2]
+    XT* X2 = X1 + RT * LD1;                                                 // [RT][LD2] (L = 3)
     float* Z = smem;                                                        // [RT][LDZ], over X1 | X2
+    constexpr int KL = NL == 3 ? C2 : C1, LDL = NL == 3 ? LD2 : LD1;        // the last layer's input: X2, or X1 at L = 2
+    const XT* XL = NL == 3 ? X2 : X1;
     float* RW = smem + S::tile_bytes / 4;                                   // [RT][16]
     float4* rloc = reinterpret_cast<float4*>(RW + RT * PC_M);               // [RT]
     int* rsrc = reinterpret_cast<int*>(rloc + RT);                          // [RT]
@@ -216,14 +226,16 @@ __global__ __launch_bounds__(NT, 2) void pointconv_level_infer_kernel(const Poin
             *reinterpret_cast<float4*>(RW + r * PC_M + m0) = make_float4(rw[0], rw[1], rw[2], rw[3]);
         }
         __syncthreads();
-        // 3. layer 2
-        tile_layer<C1, LD1, C2, LD2>(X1, a.W2, a.sc2, a.sh2, a.slope, X2, wave, lane);
-        __syncthreads();
-        // 4. layer 3 -> Z (over X1 | X2: the barrier keeps the deposit behind every wave's last read of X2)
+        // 3. layer 2 (L = 3)
+        if constexpr (NL == 3) {
+            tile_layer<C1, LD1, C2, LD2>(X1, a.W2, a.sc2, a.sh2, a.slope, X2, wave, lane);
+            __syncthreads();
+        }
+        // 4. the last layer -> Z (over X1 | X2: the barrier keeps the deposit behind every wave's last read of its input)
         {
             f32x16 acc[2][NJ3];
-            if constexpr (BF16) mfma_layer_bf16<C2, LD2, NJ3, NCB3>(X2, reinterpret_cast<const __bf16*>(a.W3), wave, lane, acc);
-            else mfma_layer<C2, LD2, NJ3, NCB3>(X2, a.W3, wave, lane, acc);
+            if constexpr (BF16) mfma_layer_bf16<KL, LDL, NJ3, NCB3>(XL, reinterpret_cast<const __bf16*>(a.W3), wave, lane, acc);
+            else mfma_layer<KL, LDL, NJ3, NCB3>(XL, a.W3, wave, lane, acc);
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < NJ3; ++j) {
@@ -278,11 +290,11 @@ int pointconv_group_tile(int ns, int G) {
     return tiles * gpt;
 }
 
-template <int NS, int C1, int C2, int C3, bool BF16>
+template <int NS, int L, int C1, int C2, int C3, bool BF16>
 int launch_pointconv(const char* fn, PointConvArgs a, hipStream_t st) {
-    using S = PointConvShape<C1, C2, C3, BF16>;
+    using S = PointConvShape<L, C1, C2, C3, BF16>;
     a.GT = pointconv_group_tile(NS, a.G);
-    auto kern = pointconv_level_infer_kernel<NS, C1, C2, C3, BF16>;
+    auto kern = pointconv_level_infer_kernel<NS, L, C1, C2, C3, BF16>;
     if (int rc = lds_opt_in(kern, S::lds_bytes, fn)) return rc;
     const int blocks = (a.G + a.GT - 1) / a.GT;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(NT), S::lds_bytes, st, a);
@@ -297,34 +309,63 @@ int pointconv_shape_id(int ns, int L, int C1, int C2, int C3, int M) {
     return -1;
 }
 
-// both precisions: every check runs before any HIP call.  W[1], W[2]: fp32 (BF16 false) or bf16 (true) [C_l][C_{l-1}]
-template <bool BF16>
+// every instantiation (the fp32 ones of pcl_pointconv_seg_level_infer_f32): the two above keep their ids, then the levels of
+// networks/seg/pointconv_partseg.py that fit the tile -- sa0, sa2 at ns = 32; in1, in2 (two layers: C2 = C3 = widths[1]) and in3 at
+// ns = 16.  sa3 (256/256/512) and in0 (512/512) need about 133 KB of LDS and have no kernel.
+int pointconv_seg_shape_id(int ns, int L, int C1, int C2, int C3, int M) {
+    const int sid = pointconv_shape_id(ns, L, C1, C2, C3, M);
+    if (sid >= 0 || M != PC_M) return sid;
+    if (L == 3 && ns == 32 && C1 == 32 && C2 == 32 && C3 == 64) return 2;
+    if (L == 3 && ns == 32 && C1 == 128 && C2 == 128 && C3 == 256) return 3;
+    if (L == 2 && ns == 16 && C1 == 256 && C2 == 256 && C3 == 256) return 4;
+    if (L == 2 && ns == 16 && C1 == 128 && C2 == 128 && C3 == 128) return 5;
+    if (L == 3 && ns == 16 && C1 == 128 && C2 == 128 && C3 == 128) return 6;
+    return -1;
+}
+
+// both precisions and both shape tables (SEG: pointconv_seg_shape_id, fp32 only): every check runs before any HIP call.  W[1],
+// W[2]: fp32 (BF16 false) or bf16 (true) [C_l][C_{l-1}]
+template <bool BF16, bool SEG = false>
 int pointconv_level_infer(const char* fn, const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
                           const float* density, const int32_t* idx, int B, int N, int m, int ns, int L, const int32_t* widths,
                           const void* const* W, const float* const* scale, const float* const* shift, float slope, const float* nets,
                           int M, float* out, int ldo, void* stream) {
+    static_assert(!(BF16 && SEG), "the part-seg shapes are fp32");
     PCL_REQUIRE(widths && W && scale && shift, "%s: null host array", fn);
     PCL_REQUIRE(L >= 1 && L <= 4, "%s: L=%d", fn, L);
-    const int sid = L == 3 ? pointconv_shape_id(ns, L, widths[0], widths[1], widths[2], M) : -1;
-    PCL_REQUIRE(sid >= 0, "%s: no kernel for ns=%d L=%d widths %d/%d/%d M=%d (pcl_pointconv_level_infer_supported)", fn, ns, L, widths[0],
-                L > 1 ? widths[1] : 0, L > 2 ? widths[2] : 0, M);
+    int sid = -1;
+    if (SEG && (L == 2 || L == 3)) sid = pointconv_seg_shape_id(ns, L, widths[0], widths[1], widths[L - 1], M);
+    else if (L == 3) sid = pointconv_shape_id(ns, L, widths[0], widths[1], widths[2], M);
+    PCL_REQUIRE(sid >= 0, "%s: no kernel for ns=%d L=%d widths %d/%d/%d M=%d (%s)", fn, ns, L, widths[0], L > 1 ? widths[1] : 0,
+                L > 2 ? widths[2] : 0, M, SEG ? "pcl_pointconv_seg_level_infer_supported" : "pcl_pointconv_level_infer_supported");
+    const int C3 = widths[L - 1];
     PCL_REQUIRE(xyz && new_xyz && Wx && density && idx && nets && out, "%s: null pointer", fn);
     PCL_REQUIRE(ldw >= 3, "%s: ldw=%d", fn, ldw);
     PCL_REQUIRE(B >= 1 && N >= 1 && m >= 1, "%s: bad sizes B=%d N=%d m=%d", fn, B, N, m);
     PCL_REQUIRE((size_t)B * m < (1u << 31) && (size_t)B * N < (1u << 31), "%s: too many groups / points", fn);
     for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", fn, l);
-    PCL_REQUIRE(ldo >= widths[2] * M && ldo % 4 == 0, "%s: ldo=%d for %d columns (a multiple of 4)", fn, ldo, widths[2] * M);
+    PCL_REQUIRE(ldo >= C3 * M && ldo % 4 == 0, "%s: ldo=%d for %d columns (a multiple of 4)", fn, ldo, C3 * M);
     // Uf, W[1], W[2] and out are moved in 16-byte pieces: their alignment is the caller's precondition (include/pcl_hip.h), held by
     // pointcloudlib_amd/inference.py before the call; there is no other path to choose here
     PointConvArgs a = {};
     a.xyz = xyz; a.new_xyz = new_xyz; a.Uf = Uf; a.Wx = Wx; a.ldw = ldw; a.density = density; a.idx = idx;
     a.G = B * m; a.N = N; a.m = m;
-    a.W2 = static_cast<const float*>(W[1]); a.W3 = static_cast<const float*>(W[2]);
-    a.sc1 = scale[0]; a.sh1 = shift[0]; a.sc2 = scale[1]; a.sh2 = shift[1]; a.sc3 = scale[2]; a.sh3 = shift[2];
+    // W3 / sc3 / sh3 are the last layer's whatever L is; W2 / sc2 / sh2 the middle layer's of L = 3
+    if (L == 3) { a.W2 = static_cast<const float*>(W[1]); a.sc2 = scale[1]; a.sh2 = shift[1]; }
+    a.W3 = static_cast<const float*>(W[L - 1]);
+    a.sc1 = scale[0]; a.sh1 = shift[0]; a.sc3 = scale[L - 1]; a.sh3 = shift[L - 1];
     a.slope = slope; a.nets = nets; a.out = out; a.ldo = ldo;
     hipStream_t st = as_stream(stream);
-    if (sid == 0) return launch_pointconv<32, 64, 64, 128, BF16>(fn, a, st);
-    return launch_pointconv<64, 128, 128, 256, BF16>(fn, a, st);
+    if (sid == 0) return launch_pointconv<32, 3, 64, 64, 128, BF16>(fn, a, st);
+    if (sid == 1) return launch_pointconv<64, 3, 128, 128, 256, BF16>(fn, a, st);
+    if constexpr (SEG) {
+        if (sid == 2) return launch_pointconv<32, 3, 32, 32, 64, false>(fn, a, st);
+        if (sid == 3) return launch_pointconv<32, 3, 128, 128, 256, false>(fn, a, st);
+        if (sid == 4) return launch_pointconv<16, 2, 256, 256, 256, false>(fn, a, st);
+        if (sid == 5) return launch_pointconv<16, 2, 128, 128, 128, false>(fn, a, st);
+        if (sid == 6) return launch_pointconv<16, 3, 128, 128, 128, false>(fn, a, st);
+    }
+    return ::pcl::fail(PCL_EINVAL, "%s: shape id %d has no launch", fn, sid);
 }
 
 }  // namespace
@@ -346,6 +387,24 @@ extern "C" int pcl_pointconv_level_infer_f32(const float* xyz, const float* new_
                                              void* stream) {
     return pointconv_level_infer<false>("pcl_pointconv_level_infer_f32", xyz, new_xyz, Uf, Wx, ldw, density, idx, B, N, m, ns, L, widths,
                                         reinterpret_cast<const void* const*>(W), scale, shift, slope, nets, M, out, ldo, stream);
+}
+
+extern "C" int pcl_pointconv_seg_level_infer_supported(int ns, int L, int C1, int C2, int C3, int M) {
+    return pointconv_seg_shape_id(ns, L, C1, C2, C3, M) >= 0;
+}
+
+extern "C" int pcl_pointconv_seg_level_infer_group_tile(int ns, int G) {
+    return (ns == 16 || ns == 32 || ns == 64) && G >= 1 ? pointconv_group_tile(ns, G) : 0;
+}
+
+extern "C" int pcl_pointconv_seg_level_infer_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
+                                                 const float* density, const int32_t* idx, int B, int N, int m, int ns, int L,
+                                                 const int32_t* widths, const float* const* W, const float* const* scale,
+                                                 const float* const* shift, float slope, const float* nets, int M, float* out, int ldo,
+                                                 void* stream) {
+    return pointconv_level_infer<false, true>("pcl_pointconv_seg_level_infer_f32", xyz, new_xyz, Uf, Wx, ldw, density, idx, B, N, m, ns, L,
+                                              widths, reinterpret_cast<const void* const*>(W), scale, shift, slope, nets, M, out, ldo,
+                                              stream);
 }
 
 extern "C" int pcl_pointconv_level_infer_bf16_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,

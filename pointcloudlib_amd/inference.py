@@ -45,7 +45,15 @@ head kernels.  Constructed directly.  ``FrozenPointConv(net, precision="bf16")``
 ``pcl_pointconv_level_infer_bf16_f32``: layers 2 and 3 of the feature MLP take bf16 operands (activations rounded to nearest even,
 weights snapshot as bf16 in ``refresh()``) and accumulate in fp32; ``Uf``, layer 1, the WeightNet, the DensityNet, the epilogues,
 ``z3``, the contraction and its output stay fp32, and so do the level's Linear, the ``group_all`` level, ``"module"`` fallbacks
-and the head."""
+and the head.
+
+``FrozenPointConvPartseg(net)`` is the same for ``networks.seg.pointconv_partseg.PointConvDensity_partseg``:
+its eight levels are k-NN levels, and each one whose (neighbours, widths) have a kernel (``pcl_pointconv_seg_level_infer_supported``:
+feature MLPs of two or three layers, 16 or 32 neighbours) runs as ONE ``pcl_pointconv_seg_level_infer_f32`` launch plus its Linear,
+as above.  An interpolation level first runs the 3-NN interpolation and ``Uf = interpolated W0[:, 3:]^T`` over its N points, then
+that launch over N groups of 16 (the centres are the level's own points in FPS visiting order, as upstream), so no ``[B,N,16,C]``
+tensor exists.  The two 512-wide levels (``sa3``, ``in0``) have no kernel and run eval-mode copies of their modules; the head runs
+the stats-free GEMMs on the ``B N`` rows.  fp32 only."""
 import copy
 import ctypes
 
@@ -56,15 +64,16 @@ from .misc.head import MAX_ROWS, fc_head
 from .misc.layers import PointwiseMLP
 from .misc.ops import (_lengths, _p, _stream, group_all, group_points, mlp_segment_max, pack_rows, packed_layout, three_interpolate,
                        three_nn, unpack_rows)
-from .misc.pointconv_utils import (DensityNet, PointConvDensitySetAbstraction, WeightNet, _linear_flush, _pointconv_linear, compute_density,
-                                   sample_level)
+from .misc.pointconv_utils import (DensityNet, PointConvDensitySetAbstraction, PointConvDensitySetInterpolation, WeightNet, _linear_flush,
+                                   _pointconv_linear, compute_density, sample_level)
 from .networks.cls.pointconv import PointConvDensityClsSsg
 from .networks.cls.pointnet import PointNet
 from .networks.cls.pointnet2 import PointNet2_cls, SamplingPrefetch
+from .networks.seg.pointconv_partseg import PointConvDensity_partseg
 from .networks.seg.pointnet2_partseg import PointNet2_partseg
 from .networks.seg.pointnet_partseg import PointNet_partseg
 
-__all__ = ["frozen", "FrozenPointConv", "FrozenPointNet", "FrozenPointNet2", "FrozenPointNet2Partseg", "FrozenPointNetPartseg"]
+__all__ = ["frozen", "FrozenPointConv", "FrozenPointConvPartseg", "FrozenPointNet", "FrozenPointNet2", "FrozenPointNet2Partseg", "FrozenPointNetPartseg"]
 
 
 PRECISIONS = ("fp32", "bf16")
@@ -837,13 +846,14 @@ def _pointconv_fusable(sa, D):
 
 class _FusedPointConv(_SegStack):
     """Snapshot of one k-NN PointConv level for pcl_pointconv_level_infer_f32 (or, ``precision="bf16"``,
-    pcl_pointconv_level_infer_bf16_f32): the feature MLP (first layer folded), the packed small nets and the level's Linear."""
+    pcl_pointconv_level_infer_bf16_f32): the feature MLP (first layer folded), the packed small nets and the level's Linear.
+    ``entry``: another fp32 entry point of the same argument list (pcl_pointconv_seg_level_infer_f32: feature MLPs of 2 or 3 layers)."""
 
-    def __init__(self, sa, D, precision="fp32"):
+    def __init__(self, sa, D, precision="fp32", entry=None):
         mlp = sa.mlp
         super().__init__([(mlp, l) for l in range(mlp.n_layers)], first=None, bf16=precision == "bf16")
         self.precision = precision
-        self.entry = "pcl_pointconv_level_infer_bf16_f32" if precision == "bf16" else "pcl_pointconv_level_infer_f32"
+        self.entry = entry or ("pcl_pointconv_level_infer_bf16_f32" if precision == "bf16" else "pcl_pointconv_level_infer_f32")
         self.operands = self.Ws_bf16 if precision == "bf16" else self.Ws           # what c_W points at
         W0 = mlp.weights[0].detach().float().contiguous().clone()
         self.D, self.slope = D, float(mlp.slope)
@@ -869,8 +879,8 @@ class _FusedPointConv(_SegStack):
         rows = B * S * ns
         _lib.call(self.entry, _p(xyz), _p(new_xyz), _p(Uf), _p(self.W0), self.ldw, _p(density), _p(idx), B, N, S, ns, self.L,
                   self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(self.nets), POINTCONV_M, _p(out), out.shape[1], st,
-                  algo_flops=2 * rows * (3 * C1 + C1 * self.widths[1] + self.widths[1] * C3 + POINTCONV_M * C3 + 296),
-                  tag=f"pointconv{ns}x{C3}")
+                  algo_flops=2 * rows * (3 * C1 + sum(a * b for a, b in zip(self.widths, self.widths[1:])) + POINTCONV_M * C3 + 296),
+                  tag=f"pointconv{ns}x{C3}" if self.L == 3 else f"pointconv{ns}x{C3}L{self.L}")
         return out
 
     def run(self, xyz, new_xyz, points, idx, density):
@@ -1026,3 +1036,111 @@ class FrozenPointConv:
         feature = feats[-1].reshape(B, -1)
         logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, B, MAX_ROWS)]
         return feats, logits[0] if len(logits) == 1 else torch.cat(logits)
+
+
+# ---------------------------------------------------------------------------------------------- PointConv part segmentation
+POINTCONV_SEG_ENTRY = "pcl_pointconv_seg_level_infer_f32"
+
+
+def _pointconv_seg_fusable(level, D):
+    """A k-NN level (set abstraction or interpolation) of the usual small nets whose shape ``pcl_pointconv_seg_level_infer_f32``
+    has a kernel for.  In the query C2 = widths[1] and C3 = widths[L-1] (include/pcl_hip.h)."""
+    mlp = level.mlp
+    if getattr(level, "group_all", False) or not (mlp.n_layers in (2, 3) and mlp.bn and mlp.last_act and mlp.spec[0] == 3 + D
+                                                   and _small_nets_ok(level)):
+        return False
+    w = [int(c) for c in mlp.spec[1:]]
+    return bool(_lib.size_query("pcl_pointconv_seg_level_infer_supported", int(level.nsample), len(w), w[0], w[1], w[-1], POINTCONV_M))
+
+
+class FrozenPointConvPartseg:
+    """Frozen evaluator of ``networks.seg.pointconv_partseg.PointConvDensity_partseg``: ``fnet(xyz [B,N,3], cls_label=None,
+    sampling=None, start_idx=None) -> [B, N, part_num]``, the signature and layout of ``net.forward`` (``cls_label`` is accepted
+    and unused, as there); ``fnet.run(...)`` also returns the eight level outputs (channel-last ``[B, S, C]``, in call order
+    ``sa0..sa3, in0..in3``; an interpolation level's rows are in its FPS visiting order, as upstream).  ``sampling``: a handle of
+    ``net.precompute_sampling(xyz)``; without one the evaluator calls it with ``start_idx`` (eight [B] int32 FPS starts, or None
+    for random ones).
+
+    ``fnet.levels`` names the plan per level: ``"fused"`` for a level whose shape has a kernel
+    (``pcl_pointconv_seg_level_infer_supported``; module docstring), ``"module"`` otherwise -- an eval-mode copy of the level's own
+    module runs on the same sampling entry.  ``refresh()`` re-reads weights and running statistics; ``net`` itself is never
+    modified (parameters, buffers, ``training`` flags)."""
+
+    def __init__(self, net):
+        if not isinstance(net, PointConvDensity_partseg):
+            raise TypeError(f"FrozenPointConvPartseg takes networks.seg.pointconv_partseg.PointConvDensity_partseg, got {type(net).__name__}")
+        self.net = net
+        self._copies = {}
+        self.refresh()
+
+    _copy = FrozenPointConv._copy
+
+    @torch.no_grad()
+    def refresh(self):
+        net = self.net
+        self.plans = []
+        D = 0
+        for name in net.LEVELS:
+            level = getattr(net, name)
+            kinds = (PointConvDensitySetAbstraction, PointConvDensitySetInterpolation)
+            if isinstance(level, kinds[1]):
+                D = level.mlp.spec[0] - 3                              # the interpolated features of the level below
+            if isinstance(level, kinds) and _pointconv_seg_fusable(level, D):
+                self.plans.append(("fused", _FusedPointConv(level, D, entry=POINTCONV_SEG_ENTRY)))
+            else:
+                self.plans.append(("module", self._copy(name, level)))
+            D = level.linear.spec[-1]
+        self.levels = [k for k, _ in self.plans]
+        fc1, fc3 = net.fc1, net.fc3
+        self.fc1 = _RowsStack(fc1)
+        self.W3 = fc3.weight.detach().float().contiguous().clone()
+        self.b3 = None if fc3.bias is None else fc3.bias.detach().float().contiguous().clone()
+        return self
+
+    def __call__(self, xyz, cls_label=None, sampling=None, start_idx=None):
+        return self.run(xyz, cls_label, sampling, start_idx)[1]
+
+    def _head(self, rows):
+        """fc1 + bn1 + relu (Dropout = identity), fc3: fc1's BatchNorm + activation ride in fc3's operand load."""
+        Y, sc, sh = self.fc1.run(rows)
+        P, K = Y.shape
+        out = torch.empty((P, self.W3.shape[0]), dtype=torch.float32, device=rows.device)
+        _lib.call("pcl_linear_fwd_rows_f32", _p(Y), _p(self.W3), _p(self.b3), _p(sc), _p(sh), self.fc1.out_slope, P, K, out.shape[1], _p(out),
+                  None, None, None, _stream(), tag=f"fwd{K}x{out.shape[1]}")
+        return out
+
+    @torch.no_grad()
+    def run(self, xyz, cls_label=None, sampling=None, start_idx=None):
+        """-> ([output of sa0..sa3, in0..in3: [B, S, C]], logits [B, N, part_num])."""
+        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
+            raise ValueError(f"FrozenPointConvPartseg: xyz must be [B,N,3], got {tuple(getattr(xyz, 'shape', ()))}")
+        if not xyz.is_cuda or xyz.dtype != torch.float32:
+            raise TypeError(f"FrozenPointConvPartseg: expected a float32 tensor on the GPU, got {xyz.dtype} on {xyz.device}")
+        B, N, _ = xyz.shape
+        if sampling is None:
+            sampling = self.net.precompute_sampling(xyz, start_idx)
+        levels = sampling["levels"]
+        pts, feats, points = [xyz.contiguous()], [], None
+        for i in range(4):
+            points = self._level(i, pts[-1], None, points, levels[i])
+            feats.append(points)
+            pts.append(levels[i][0].contiguous())
+        for k in range(4):                                             # in_k reads the coordinates of levels 3 - k and 4 - k
+            points = self._level(4 + k, pts[3 - k], pts[4 - k], points, levels[4 + k])
+            feats.append(points)
+        return feats, self._head(points.reshape(B * N, -1)).view(B, N, -1)
+
+    def _level(self, i, xyz1, xyz2, points, lv):
+        """Level ``i`` (call order) on its sampling entry ``lv``, channel-last: a set-abstraction level on (xyz1, points), an
+        interpolation level on (xyz1, xyz2, points of xyz2) -> the level's output [B, S, C]."""
+        kind, plan = self.plans[i]
+        cf = lambda t: t.permute(0, 2, 1)                              # channel-last <-> channel-first, for the module copies
+        if i < 4:
+            new_xyz, ((idx, density),) = lv
+            if kind == "fused":
+                return plan.run(xyz1, new_xyz.contiguous(), points, idx.contiguous(), density.contiguous())
+            return cf(plan(cf(xyz1), None if points is None else cf(points), sampling=lv)[1]).contiguous()
+        if kind == "fused":
+            interpolated = three_interpolate(points.contiguous(), lv["idx3"], lv["w3"])
+            return plan.run(xyz1, lv["new_xyz"].contiguous(), interpolated, lv["idx"].contiguous(), lv["density"].contiguous())
+        return cf(plan(cf(xyz1), cf(xyz2), None, cf(points), sampling=lv)).contiguous()

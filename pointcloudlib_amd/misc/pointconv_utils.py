@@ -327,20 +327,36 @@ class PointConvDensitySetInterpolation(nn.Module):
         self.densitynet = DensityNet()
         self.linear = PointwiseMLP([16 * mlp[-1], mlp[-1]], bias=True)
 
-    def forward(self, xyz1, xyz2, points1, points2, start_idx=None):
+    def sample(self, xyz1, xyz2, start_idx=None):
+        """Everything of this level that depends on the coordinates only (xyz1 [B,N,3], xyz2 [B,S,3], no gradients), for
+        ``forward(sampling=...)``: ``idx3, w3`` of the 3-NN interpolation (:293-299), the raw kernel ``density`` of xyz1 (:304),
+        ``fps_idx`` -- FPS over all N points, the order of the level's output rows (:307) -- ``new_xyz = xyz1[fps_idx]`` and their
+        k-NN lists ``idx`` [B,N,nsample]."""
+        idx3, w3 = three_nn(xyz1, xyz2)
+        density = compute_density(xyz1, self.bandwidth)
+        fps_idx = farthest_point_sample(xyz1, xyz1.shape[1], start_idx)
+        new_xyz = index_points(xyz1, fps_idx)
+        return {"fps_idx": fps_idx, "new_xyz": new_xyz, "idx": knn_point(self.nsample, xyz1, new_xyz), "density": density,
+                "idx3": idx3, "w3": w3}
+
+    def forward(self, xyz1, xyz2, points1, points2, start_idx=None, sampling=None):
         xyz1 = xyz1.permute(0, 2, 1).contiguous()
         xyz2 = xyz2.permute(0, 2, 1).contiguous()
         points2 = points2.permute(0, 2, 1).contiguous()
         B, N, _ = xyz1.shape
-        idx3, w3 = three_nn(xyz1, xyz2)                                                   # :293-299
+        s = sampling                                                                      # produced ahead by ``sample``
+        idx3, w3 = (s["idx3"], s["w3"]) if s is not None else three_nn(xyz1, xyz2)        # :293-299
         interpolated = three_interpolate(points2, idx3, w3)                               # :300
-        density_scale = self.densitynet(compute_density(xyz1, self.bandwidth))            # :304-305
+        density_scale = self.densitynet(s["density"] if s is not None else compute_density(xyz1, self.bandwidth))   # :304-305
         if xyz1.is_cuda:
             # sample_and_group(N, nsample, ...) :307 without the [B,N,ns,3+D] tensor, as in PointConvDensitySetAbstraction.forward:
             # the feature MLP's first conv runs folded into the grouping (K = 3+D GEMM over the N points, not over N*ns rows)
-            fps_idx = farthest_point_sample(xyz1, N, start_idx)
-            new_xyz = index_points(xyz1, fps_idx)
-            idx = knn_point(self.nsample, xyz1, new_xyz)
+            if s is not None:
+                new_xyz, idx = s["new_xyz"], s["idx"]
+            else:
+                fps_idx = farthest_point_sample(xyz1, N, start_idx)
+                new_xyz = index_points(xyz1, fps_idx)
+                idx = knn_point(self.nsample, xyz1, new_xyz)
             grouped_xyz_norm = index_points(xyz1, idx) - new_xyz.view(B, N, 1, 3)
             grouped_density = index_points(density_scale, idx)
             weights = self.weightnet(grouped_xyz_norm.contiguous())                       # :317-318
@@ -350,7 +366,8 @@ class PointConvDensitySetInterpolation(nn.Module):
                 out = feature_mlp_contract(self.mlp, new_points, grouped_density, weights)
             return _pointconv_linear(self.linear, out).permute(0, 2, 1)                   # :321-323
         _, new_points, grouped_xyz_norm, _, grouped_density = sample_and_group(
-            N, self.nsample, xyz1, interpolated, density_scale, start_idx)                # :307
+            N, self.nsample, xyz1, interpolated, density_scale, start_idx,
+            sampled=None if s is None else (s["new_xyz"], s["idx"]))                      # :307
         weights = self.weightnet(grouped_xyz_norm.contiguous())                           # :317-318
         new_points = feature_mlp_contract(self.mlp, new_points, grouped_density, weights)     # :311-315 + :319-320
         return _pointconv_linear(self.linear, new_points).permute(0, 2, 1)                # :321-323

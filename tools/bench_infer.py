@@ -39,6 +39,13 @@ agreement of the two precisions, recorded and not asserted) and ``level_kernel_m
 ``pcl_pointconv_level_infer_bf16_f32`` calls; the line goes to profiles/infer_pointconv_bf16_bench_line.json instead.
 ``--frozen_only --precision bf16`` runs the bf16 form alone (for a kernel trace) and writes no file.
 
+``--nets pointconv_partseg`` compares ``net.eval()`` under ``no_grad`` with ``FrozenPointConvPartseg(net)`` (B in {16, 64}, N = 2048;
+both forms read the same [B,N,3] tensor and the SAME ``net.precompute_sampling`` handle), with the peak memory of both, the
+per-call times of the ``pcl_pointconv_seg_level_infer_f32`` launches (``level_kernel_ms``) and, between device events around each
+level of a frozen forward (``frozen_level_ms``: sa0..sa3, in0..in3, head; ``in3_contract`` and ``in3_linear`` inside in3), the
+shares of the two ``"module"`` levels and of the launches that write and read in3's ``[B N, 2048]`` contraction output; the line
+goes to profiles/infer_pointconv_partseg_bench_line.json.
+
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
 (a) ``dense`` frozen at N, (b) ``ragged_full`` with every length = N, (c) ``ragged`` with the drawn lengths, (d) ``loop``: B calls
@@ -122,6 +129,42 @@ def _pointconv_level_times(fwd, entry="pcl_pointconv_level_infer_f32", repeats=5
     return out
 
 
+def _partseg_level_times(fpcs, fwd, repeats=5):
+    """Device events around every level, the head, and in3's two halves (the launch that writes the contraction output, the
+    Linear that reads it) of FrozenPointConvPartseg forwards: average ms over ``repeats`` (the events' dispatch gaps are inside)."""
+    marks = []
+
+    def timed(fn, key):
+        def wrapper(*args, **kw):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            out = fn(*args, **kw)
+            b.record()
+            marks.append((key(*args), a, b))
+            return out
+        return wrapper
+
+    names = list(fpcs.net.LEVELS)
+    in3 = fpcs.plans[7][1] if fpcs.levels[7] == "fused" else None
+    saved = [(fpcs, "_level", fpcs._level), (fpcs, "_head", fpcs._head)]
+    fpcs._level, fpcs._head = timed(fpcs._level, lambda i, *r: names[i]), timed(fpcs._head, lambda *r: "head")
+    if in3 is not None:
+        saved += [(in3, "contract", in3.contract), (in3.linear, "run", in3.linear.run)]
+        in3.contract, in3.linear.run = timed(in3.contract, lambda *r: "in3_contract"), timed(in3.linear.run, lambda *r: "in3_linear")
+    try:
+        for _ in range(repeats):
+            fwd()
+        torch.cuda.synchronize()
+    finally:
+        for obj, attr, fn in saved:
+            if attr in obj.__dict__:
+                delattr(obj, attr)
+    out = {}
+    for key, a, b in marks:
+        out[key] = out.get(key, 0.0) + a.elapsed_time(b) / repeats
+    return {k: round(v, 4) for k, v in out.items()}
+
+
 def _ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16=None):
     """The four forms of --ragged for one net and batch (same window estimator as the dense rows)."""
     import numpy as np
@@ -169,7 +212,8 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, nargs="+", default=None, help="default: 32 256 (cls), 16 64 (part-seg, pointnet_partseg), 8 32 256 (pointnet)")
-    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg", "pointnet", "pointnet_partseg", "pointconv"])
+    ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg", "pointnet", "pointnet_partseg", "pointconv",
+                                                                                "pointconv_partseg"])
     ap.add_argument("--points", type=int, default=None, help="default: 1024 (cls), 2048 (part-seg)")
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
     ap.add_argument("--precision", nargs="+", default=["fp32"], choices=["fp32", "bf16"],
@@ -186,7 +230,10 @@ def main():
     pointnet_only = all(k == "pointnet" for k in a.nets)
     pn_partseg_only = all(k == "pointnet_partseg" for k in a.nets)
     pointconv_only = all(k == "pointconv" for k in a.nets)
-    if a.ragged and "pointconv" in a.nets:
+    pc_partseg_only = all(k == "pointconv_partseg" for k in a.nets)
+    if a.precision != ["fp32"] and "pointconv_partseg" in a.nets:
+        raise SystemExit("bench_infer.py: FrozenPointConvPartseg is fp32 only")
+    if a.ragged and ("pointconv" in a.nets or "pointconv_partseg" in a.nets):
         raise SystemExit("bench_infer.py: PointConv's sampling has no ragged form")
     res = {"N": (a.points or 1024) if cls_only else (a.points or 2048), "windows": a.windows, "iters": a.iters, "cases": []}
     if a.ragged:
@@ -194,7 +241,8 @@ def main():
     for kind in a.nets:
         seg = kind.startswith("partseg")
         pn_seg = kind == "pointnet_partseg"
-        N = a.points or (2048 if seg or pn_seg else 1024)
+        pc_seg = kind == "pointconv_partseg"
+        N = a.points or (2048 if seg or pn_seg or pc_seg else 1024)
         torch.manual_seed(0)
         if seg:
             from pointcloudlib_amd.misc.layers import set_accumulation
@@ -213,6 +261,10 @@ def main():
             from pointcloudlib_amd.inference import FrozenPointNetPartseg
             from pointcloudlib_amd.networks.seg.pointnet_partseg import PointNet_partseg
             net = PointNet_partseg().to(dev).eval()
+        elif pc_seg:
+            from pointcloudlib_amd.inference import FrozenPointConvPartseg
+            from pointcloudlib_amd.networks.seg.pointconv_partseg import PointConvDensity_partseg
+            net = PointConvDensity_partseg().to(dev).eval()
         else:
             net = (PointNet2_cls if kind == "ssg" else PointNetMSG)().to(dev).eval()
         if kind == "pointnet":
@@ -229,6 +281,9 @@ def main():
         elif kind == "pointconv":
             fpc = FrozenPointConv(net)
             fnet_bf16 = fpc16 = FrozenPointConv(net, precision="bf16") if "bf16" in a.precision else None
+        elif pc_seg:
+            fpcs = FrozenPointConvPartseg(net)
+            fnet_bf16 = None
         elif pn_seg:
             fps = FrozenPointNetPartseg(net)
 
@@ -243,7 +298,7 @@ def main():
         else:
             fnet = frozen(net)
             fnet_bf16 = frozen(net, precision="bf16") if "bf16" in a.precision else None
-        for B in a.batch or ([16, 64] if seg or pn_seg else [8, 32, 256] if kind == "pointnet" else [32, 256]):
+        for B in a.batch or ([16, 64] if seg or pn_seg or pc_seg else [8, 32, 256] if kind == "pointnet" else [32, 256]):
             xyz = torch.from_numpy(synth.gauss_ball(B, N, 1)).to(dev)
             nrm = torch.from_numpy(synth.unit_normals(B, N, 2)).to(dev)
             extra = ()
@@ -289,6 +344,16 @@ def main():
                 def frozen_bf16_fwd():
                     return fpc16(x_cf, sampling=samp)
 
+            if pc_seg:
+                samp = net.precompute_sampling(xyz)           # one sampling handle feeds both forms
+
+                def eval_fwd(net=net):
+                    with torch.no_grad():
+                        return net(xyz, sampling=samp)
+
+                def frozen_fwd():
+                    return fpcs(xyz, sampling=samp)
+
             if pn_seg:
                 x_cf = xyz.transpose(1, 2).contiguous()       # the network's input layout, made once: both forms read it
 
@@ -320,18 +385,20 @@ def main():
             for w in range(a.windows):
                 for name, fn in (forms if w % 2 == 0 else forms[::-1]):
                     times[name].append(_window(fn, a.iters))
-            case = {"net": kind, "B": B, "N": N} if seg or pn_seg else {"net": kind, "B": B}
+            case = {"net": kind, "B": B, "N": N} if seg or pn_seg or pc_seg else {"net": kind, "B": B}
             for name, fn in forms:
                 case[f"{name}_ms"] = round(statistics.median(times[name]), 4)
                 case[f"{name}_ms_min"] = round(min(times[name]), 4)
-                if fnet_bf16 is not None:
+                if fnet_bf16 is not None or pc_seg:
                     case[f"{name}_ms_max"] = round(max(times[name]), 4)
                 case[f"{name}_peak_mib"] = round(_peak(fn) / 2**20, 1)
             if not a.frozen_only:
                 case["speedup"] = round(case["eval_ms"] / case["frozen_ms"], 3)
                 if seg:
                     case["speedup_vs_acc0"] = round(case["eval_acc0_ms"] / case["frozen_ms"], 3)
-                if seg or pn_seg or kind == "pointconv":
+                if pc_seg:
+                    case["frozen_below_eval_min"] = case["frozen_ms"] < case["eval_ms_min"]
+                if seg or pn_seg or pc_seg or kind == "pointconv":
                     case["mem_ratio"] = round(case["eval_peak_mib"] / max(case["frozen_peak_mib"], 0.1), 1)
                 with torch.no_grad():
                     case["max_abs_logit_diff"] = float((eval_fwd() - frozen_fwd()).abs().max())
@@ -352,6 +419,14 @@ def main():
                 case["level_kernel_ms"] = _pointconv_level_times(frozen_fwd)
             if kind == "pointconv" and fnet_bf16 is not None:
                 case["level_kernel_ms_bf16"] = _pointconv_level_times(frozen_bf16_fwd, "pcl_pointconv_level_infer_bf16_f32")
+            if pc_seg and "frozen" in times:
+                case["levels"] = fpcs.levels
+                case["level_kernel_ms"] = _pointconv_level_times(frozen_fwd, "pcl_pointconv_seg_level_infer_f32")
+                lt = case["frozen_level_ms"] = _partseg_level_times(fpcs, frozen_fwd)
+                total = sum(v for k, v in lt.items() if not k.startswith("in3_"))
+                case["module_levels_share"] = round(sum(lt[n] for n, k in zip(net.LEVELS, fpcs.levels) if k == "module") / total, 4)
+                if "in3_contract" in lt:
+                    case["in3_contraction_output_share"] = round((lt["in3_contract"] + lt["in3_linear"]) / total, 4)
             res["cases"].append(case)
     print(json.dumps(res))
     if "bf16" in a.precision and not a.ragged and not ((pointnet_only or pn_partseg_only or pointconv_only) and a.frozen_only):
@@ -368,6 +443,10 @@ def main():
     elif pointconv_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "infer_pointconv_bench_line.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
+    elif pc_partseg_only and not a.frozen_only:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "infer_pointconv_partseg_bench_line.json"), "w") as f:
             f.write(json.dumps(res) + "\n")
     elif pn_partseg_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
