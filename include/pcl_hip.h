@@ -893,7 +893,8 @@ int pcl_pointconv_level_infer_f32(const float* xyz, const float* new_xyz, const 
  * and for nothing else (256/256/512 at ns = 32 and 512/512 at ns = 16 do not fit the tile's LDS); any other shape returns
  * PCL_EINVAL ("no kernel") before any launch.  (32, 64/64/128) and (64, 128/128/256) launch the very kernels of
  * pcl_pointconv_level_infer_f32.  pcl_pointconv_seg_level_infer_group_tile: as pcl_pointconv_level_infer_group_tile, for ns in
- * {16, 32, 64} (a multiple of 64 / ns, at most 8 tiles). */
+ * {16, 32, 64} (a multiple of 64 / ns, at most 8 tiles).  Both queries answer for both precisions: every shape has its fp32 and its
+ * bf16 kernel (pcl_pointconv_seg_level_infer_bf16_f32), and the group tile does not depend on the precision. */
 int pcl_pointconv_seg_level_infer_supported(int ns, int L, int C1, int C2, int C3, int M);
 int pcl_pointconv_seg_level_infer_group_tile(int ns, int G);
 int pcl_pointconv_seg_level_infer_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
@@ -915,6 +916,23 @@ int pcl_pointconv_level_infer_bf16_f32(const float* xyz, const float* new_xyz, c
                                        const float* density, const int32_t* idx, int B, int N, int m, int ns, int L,
                                        const int32_t* widths, const void* const* W, const float* const* scale, const float* const* shift,
                                        float slope, const float* nets, int M, float* out, int ldo, void* stream);
+/* No reference counterpart: pcl_pointconv_seg_level_infer_f32 with bf16 matrix operands (FrozenPointConvPartseg(net,
+ * precision="bf16")).  Arguments, host checks (all before any HIP call), preconditions, shapes and the "no kernel" error of
+ * pcl_pointconv_seg_level_infer_f32, except that W[1] .. W[L-1] are bf16 [C_l, C_{l-1}] dense, 16-byte aligned; Wx, Uf, scale,
+ * shift and nets stay fp32.  Numerics, for both layer counts: the row records, layer 1 (the fp32 fmaf chain plus Uf) and its
+ * epilogue, the WeightNet, the DensityNet, rw = rho * w, every epilogue act(scale * y + shift), the last activation z_L, Z and the
+ * contraction (v_mfma_f32_16x16x4_f32, s ascending) are exactly the expressions of pcl_pointconv_seg_level_infer_f32.
+ *     L = 3: z_1 and z_2 are rounded to nearest even to bf16; y_2 = W_2 z_1 and y_3 = W_3 z_2 are bf16 x bf16 products accumulated
+ *            in fp32 (v_mfma_f32_32x32x16_bf16, k-blocks of 16 ascending); z_3 is never rounded.
+ *     L = 2: z_1 is rounded to nearest even to bf16; y_2 = W_2 z_1 is the one bf16 x bf16 layer, as above; z_2 is never rounded.
+ * A group's result depends only on its own rows (not on B, on the group's place in the launch or on how many groups a workgroup
+ * owns); no atomics, two calls give identical bits; all 16 * widths[L-1] outputs of every group are written, in fp32, and none
+ * beyond them.  (32, 64/64/128) and (64, 128/128/256) launch the very kernels of pcl_pointconv_level_infer_bf16_f32. */
+int pcl_pointconv_seg_level_infer_bf16_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
+                                           const float* density, const int32_t* idx, int B, int N, int m, int ns, int L,
+                                           const int32_t* widths, const void* const* W, const float* const* scale,
+                                           const float* const* shift, float slope, const float* nets, int M, float* out, int ldo,
+                                           void* stream);
 
 /* ---- Frozen inference: one PointNet++ feature-propagation level in evaluation mode as ONE launch ------------------------
  * misc/ops.py:54-107 (PointNetFeaturePropagation.execute: 3-NN inverse-distance interpolation, concat with the skip features,

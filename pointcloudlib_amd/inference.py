@@ -53,7 +53,11 @@ feature MLPs of two or three layers, 16 or 32 neighbours) runs as ONE ``pcl_poin
 as above.  An interpolation level first runs the 3-NN interpolation and ``Uf = interpolated W0[:, 3:]^T`` over its N points, then
 that launch over N groups of 16 (the centres are the level's own points in FPS visiting order, as upstream), so no ``[B,N,16,C]``
 tensor exists.  The two 512-wide levels (``sa3``, ``in0``) have no kernel and run eval-mode copies of their modules; the head runs
-the stats-free GEMMs on the ``B N`` rows.  fp32 only."""
+the stats-free GEMMs on the ``B N`` rows.  ``FrozenPointConvPartseg(net, precision="bf16")`` runs every fused level launch as
+``pcl_pointconv_seg_level_infer_bf16_f32``: the layers behind the first of the feature MLP (one at two layers, two at three) take
+bf16 operands (activations rounded to nearest even, weights snapshot as bf16 in ``refresh()``) and accumulate in fp32; ``Uf``,
+layer 1, the WeightNet, the DensityNet, the epilogues, the last activation, the contraction and its output stay fp32, and so do the
+3-NN interpolation, the level's Linear, the two ``"module"`` levels and the head."""
 import copy
 import ctypes
 
@@ -847,7 +851,8 @@ def _pointconv_fusable(sa, D):
 class _FusedPointConv(_SegStack):
     """Snapshot of one k-NN PointConv level for pcl_pointconv_level_infer_f32 (or, ``precision="bf16"``,
     pcl_pointconv_level_infer_bf16_f32): the feature MLP (first layer folded), the packed small nets and the level's Linear.
-    ``entry``: another fp32 entry point of the same argument list (pcl_pointconv_seg_level_infer_f32: feature MLPs of 2 or 3 layers)."""
+    ``entry``: another entry point of the same argument list and of that precision (pcl_pointconv_seg_level_infer_f32 /
+    pcl_pointconv_seg_level_infer_bf16_f32: feature MLPs of 2 or 3 layers)."""
 
     def __init__(self, sa, D, precision="fp32", entry=None):
         mlp = sa.mlp
@@ -1040,6 +1045,7 @@ class FrozenPointConv:
 
 # ---------------------------------------------------------------------------------------------- PointConv part segmentation
 POINTCONV_SEG_ENTRY = "pcl_pointconv_seg_level_infer_f32"
+POINTCONV_SEG_ENTRIES = {"fp32": POINTCONV_SEG_ENTRY, "bf16": "pcl_pointconv_seg_level_infer_bf16_f32"}
 
 
 def _pointconv_seg_fusable(level, D):
@@ -1064,12 +1070,18 @@ class FrozenPointConvPartseg:
     ``fnet.levels`` names the plan per level: ``"fused"`` for a level whose shape has a kernel
     (``pcl_pointconv_seg_level_infer_supported``; module docstring), ``"module"`` otherwise -- an eval-mode copy of the level's own
     module runs on the same sampling entry.  ``refresh()`` re-reads weights and running statistics; ``net`` itself is never
-    modified (parameters, buffers, ``training`` flags)."""
+    modified (parameters, buffers, ``training`` flags).  ``precision``: "fp32", or "bf16" for bf16 matrix operands in the layers
+    behind the first of the fused level launches (module docstring); ``fnet.precision`` tells which.  ``levels`` does not depend
+    on it, and everything but the fused launches -- the interpolation, ``Uf``, each level's Linear, the ``"module"`` levels, the
+    head -- is the same code on the same types."""
 
-    def __init__(self, net):
+    def __init__(self, net, precision="fp32"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"FrozenPointConvPartseg: precision must be one of {PRECISIONS}, got {precision!r}")
         if not isinstance(net, PointConvDensity_partseg):
             raise TypeError(f"FrozenPointConvPartseg takes networks.seg.pointconv_partseg.PointConvDensity_partseg, got {type(net).__name__}")
         self.net = net
+        self.precision = precision
         self._copies = {}
         self.refresh()
 
@@ -1086,7 +1098,7 @@ class FrozenPointConvPartseg:
             if isinstance(level, kinds[1]):
                 D = level.mlp.spec[0] - 3                              # the interpolated features of the level below
             if isinstance(level, kinds) and _pointconv_seg_fusable(level, D):
-                self.plans.append(("fused", _FusedPointConv(level, D, entry=POINTCONV_SEG_ENTRY)))
+                self.plans.append(("fused", _FusedPointConv(level, D, self.precision, entry=POINTCONV_SEG_ENTRIES[self.precision])))
             else:
                 self.plans.append(("module", self._copy(name, level)))
             D = level.linear.spec[-1]

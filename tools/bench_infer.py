@@ -44,7 +44,13 @@ both forms read the same [B,N,3] tensor and the SAME ``net.precompute_sampling``
 per-call times of the ``pcl_pointconv_seg_level_infer_f32`` launches (``level_kernel_ms``) and, between device events around each
 level of a frozen forward (``frozen_level_ms``: sa0..sa3, in0..in3, head; ``in3_contract`` and ``in3_linear`` inside in3), the
 shares of the two ``"module"`` levels and of the launches that write and read in3's ``[B N, 2048]`` contraction output; the line
-goes to profiles/infer_pointconv_partseg_bench_line.json.
+goes to profiles/infer_pointconv_partseg_bench_line.json.  With ``--precision fp32 bf16`` every row also carries
+``FrozenPointConvPartseg(net, precision="bf16")`` in the same interleaved windows, on the same tensor and the same sampling handle
+(``frozen_bf16_ms`` with its window minimum and maximum, ``bf16_vs_fp32``, ``bf16_below_fp32_min``, the max-abs logit distance and the
+per-point top-1 agreement of the two precisions, recorded and not asserted), ``level_kernel_ms_bf16`` (the per-call times of the
+``pcl_pointconv_seg_level_infer_bf16_f32`` launches) and ``frozen_level_ms_bf16`` with the shares of the two ``"module"`` levels and
+of in3's Linear in the bf16 forward; the line goes to profiles/infer_pointconv_partseg_bf16_bench_line.json instead.
+``--frozen_only --precision bf16`` runs the bf16 form alone (for a kernel trace) and writes no file.
 
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
@@ -231,8 +237,6 @@ def main():
     pn_partseg_only = all(k == "pointnet_partseg" for k in a.nets)
     pointconv_only = all(k == "pointconv" for k in a.nets)
     pc_partseg_only = all(k == "pointconv_partseg" for k in a.nets)
-    if a.precision != ["fp32"] and "pointconv_partseg" in a.nets:
-        raise SystemExit("bench_infer.py: FrozenPointConvPartseg is fp32 only")
     if a.ragged and ("pointconv" in a.nets or "pointconv_partseg" in a.nets):
         raise SystemExit("bench_infer.py: PointConv's sampling has no ragged form")
     res = {"N": (a.points or 1024) if cls_only else (a.points or 2048), "windows": a.windows, "iters": a.iters, "cases": []}
@@ -283,7 +287,7 @@ def main():
             fnet_bf16 = fpc16 = FrozenPointConv(net, precision="bf16") if "bf16" in a.precision else None
         elif pc_seg:
             fpcs = FrozenPointConvPartseg(net)
-            fnet_bf16 = None
+            fnet_bf16 = fpcs16 = FrozenPointConvPartseg(net, precision="bf16") if "bf16" in a.precision else None
         elif pn_seg:
             fps = FrozenPointNetPartseg(net)
 
@@ -354,6 +358,9 @@ def main():
                 def frozen_fwd():
                     return fpcs(xyz, sampling=samp)
 
+                def frozen_bf16_fwd():
+                    return fpcs16(xyz, sampling=samp)
+
             if pn_seg:
                 x_cf = xyz.transpose(1, 2).contiguous()       # the network's input layout, made once: both forms read it
 
@@ -371,7 +378,7 @@ def main():
                 res["cases"].append(_ragged_case(kind, fnet, xyz, nrm, extra, a, fnet_bf16))
                 continue
             if a.frozen_only:
-                forms = [("frozen", frozen_fwd)] if "fp32" in a.precision or kind != "pointconv" else []
+                forms = [("frozen", frozen_fwd)] if "fp32" in a.precision or kind not in ("pointconv", "pointconv_partseg") else []
             elif seg:
                 forms = [("eval", eval_fwd), ("eval_acc0", lambda: eval_fwd(net0)), ("frozen", frozen_fwd)]
             else:
@@ -407,7 +414,8 @@ def main():
                 case["bf16_below_fp32_min"] = case["frozen_bf16_ms"] < case["frozen_ms_min"]
                 lf, lb = frozen_fwd(), frozen_bf16_fwd()
                 case["max_abs_logit_diff_bf16_fp32"] = float((lf - lb).abs().max())
-                case["top1_agreement_bf16_fp32"] = float((lf.argmax(1) == lb.argmax(1)).float().mean())
+                cdim = -1 if pc_seg else 1                    # FrozenPointConvPartseg's logits are [B, N, parts]: per-point top-1
+                case["top1_agreement_bf16_fp32"] = float((lf.argmax(cdim) == lb.argmax(cdim)).float().mean())
                 if kind == "pointnet" and not a.frozen_only:  # recorded, not asserted: distance from fp64 under both precisions
                     f64, l64 = _pointnet_fp64(net, x_cf)
                     for tag, form in (("fp32", fpn), ("bf16", fpn16)):
@@ -427,13 +435,22 @@ def main():
                 case["module_levels_share"] = round(sum(lt[n] for n, k in zip(net.LEVELS, fpcs.levels) if k == "module") / total, 4)
                 if "in3_contract" in lt:
                     case["in3_contraction_output_share"] = round((lt["in3_contract"] + lt["in3_linear"]) / total, 4)
+            if pc_seg and fnet_bf16 is not None:
+                case["levels"] = fpcs16.levels
+                case["level_kernel_ms_bf16"] = _pointconv_level_times(frozen_bf16_fwd, "pcl_pointconv_seg_level_infer_bf16_f32")
+                lt = case["frozen_level_ms_bf16"] = _partseg_level_times(fpcs16, frozen_bf16_fwd)
+                total = sum(v for k, v in lt.items() if not k.startswith("in3_"))
+                case["module_levels_share_bf16"] = round(sum(lt[n] for n, k in zip(net.LEVELS, fpcs16.levels) if k == "module") / total, 4)
+                if "in3_linear" in lt:
+                    case["in3_linear_share_bf16"] = round(lt["in3_linear"] / total, 4)
             res["cases"].append(case)
     print(json.dumps(res))
-    if "bf16" in a.precision and not a.ragged and not ((pointnet_only or pn_partseg_only or pointconv_only) and a.frozen_only):
+    if "bf16" in a.precision and not a.ragged and not ((pointnet_only or pn_partseg_only or pointconv_only or pc_partseg_only) and a.frozen_only):
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         name = ("infer_pointnet_bf16_bench_line.json" if pointnet_only else
                 "infer_pointnet_partseg_bf16_bench_line.json" if pn_partseg_only else
-                "infer_pointconv_bf16_bench_line.json" if pointconv_only else "infer_bf16_bench_line.json")
+                "infer_pointconv_bf16_bench_line.json" if pointconv_only else
+                "infer_pointconv_partseg_bf16_bench_line.json" if pc_partseg_only else "infer_bf16_bench_line.json")
         with open(os.path.join(ROOT, "profiles", name), "w") as f:
             f.write(json.dumps(res) + "\n")
     elif pointnet_only and not a.frozen_only:
