@@ -1,63 +1,19 @@
-"""Frozen inference for the PointNet++ classifiers: ``frozen(net)`` evaluates a trained ``PointNet2_cls`` / ``PointNetMSG`` the way
-``net.eval()`` under ``torch.no_grad()`` does (the reference's ``evaluate``, train_cls.py:92-124), on kernels made for it.
+"""Frozen inference: evaluators that run a trained network the way ``net.eval()`` under ``torch.no_grad()`` does (the reference's
+``evaluate``, train_cls.py:92-124), on kernels made for it.  Each class states its own plan; this is the index.
 
-The eval constants are snapshot once on the device (per layer ``scale = gamma / sqrt(running_var + eps)``, ``shift = beta -
-scale * running_mean``, folded conv bias; dense weights), so a forward launches no small torch ops and computes no BatchNorm
-statistics.  Per ball-query set-abstraction level and scale: the per-point product ``Uf = feat W0[:, 3:]^T`` of the folded first
-layer (stats-free library GEMM; narrow features such as SA1's normals fold inline instead), then ONE ``pcl_sa_level_infer_f32``
-launch that runs the whole MLP + max of every group with its activations in LDS and writes its column slice of the level's output.
-The GroupAll level runs the library's forward GEMMs stats-free with the snapshot constants, then its max; the head runs the
-eval-mode head kernels on at most 64 rows per call.  A level whose shape has no fused kernel runs an eval-mode copy of its own
-module.  ``net`` itself is never modified (parameters, running statistics, ``training`` flags).
+- ``FrozenPointNet2``: ``PointNet2_cls`` / ``PointNetMSG``, through ``frozen(net)``; csrc/infer.hip; DESIGN.md sections 12, 14
+  (``lengths=``) and 17 (``precision="bf16"``).
+- ``FrozenPointNet2Partseg``: ``PointNet2_partseg`` / its ``PointNetMSG``, through ``frozen(net)``; csrc/infer.hip and
+  csrc/infer_fp.hip; DESIGN.md sections 13, 14 and 17.
+- ``FrozenPointNet``: ``networks.cls.pointnet.PointNet``; csrc/infer_pointnet.hip; DESIGN.md sections 19 and 21 (bf16).
+- ``FrozenPointNetPartseg``: ``networks.seg.pointnet_partseg.PointNet_partseg``; csrc/infer_pointnet_seg.hip; DESIGN.md sections 20
+  and 23 (bf16).
+- ``FrozenPointConv``: ``networks.cls.pointconv.PointConvDensityClsSsg``; csrc/infer_pointconv.hip; DESIGN.md sections 24 and 25
+  (bf16).
+- ``FrozenPointConvPartseg``: ``networks.seg.pointconv_partseg.PointConvDensity_partseg``; csrc/infer_pointconv.hip and
+  csrc/infer_pointconv_seg_bf16.hip; DESIGN.md sections 26 and 27 (bf16).
 
-The part-seg networks (``PointNet2_partseg`` / its ``PointNetMSG``) share that encoder plan; each feature-propagation level runs
-the stats-free GEMMs of its folded first layer (``Uc = coarse W0c^T`` at the coarse resolution, ``Us = skip W0s^T`` per point, or
-the skip inline when it is narrow; the one-hot class label as a per-cloud bias) and then ONE ``pcl_fp_level_infer_f32`` launch.
-The last level carries the head (Conv1d + BN, Dropout = identity, Conv1d) in the same launch, which also stores the level's own
-output (the tap).  FP levels and heads of other widths run eval-mode copies of their own modules.
-
-``frozen(net, precision="bf16")`` runs every fused set-abstraction launch as ``pcl_sa_level_infer_bf16_f32``: layers 2 and up
-take bf16 operands (activations rounded to nearest even, weights snapshot as bf16 once) and accumulate in fp32; the first layer,
-``Uf``, the epilogues, the max and every output stay fp32, and so do the GroupAll level, the FP levels and the heads.
-
-``FrozenPointNet(net)`` is the same for ``networks.cls.pointnet.PointNet``: the five convs and the max over the points run as
-``pcl_pointnet_stack_infer_f32`` (csrc/infer_pointnet.hip: activations in LDS, nothing but per-tile maxima written), then the
-head.  It is constructed directly: ``frozen()`` keeps its PointNet++ dispatch.  ``FrozenPointNet(net, precision="bf16")`` runs the
-stack as ``pcl_pointnet_stack_infer_bf16_f32``: layers 2-5 take bf16 operands (activations rounded to nearest even, weights
-snapshot as bf16 in ``refresh()``) and accumulate in fp32; layer 1, the epilogues, the max, the global feature and the head stay
-fp32.
-
-``FrozenPointNetPartseg(net)`` is the same for ``networks.seg.pointnet_partseg.PointNet_partseg`` (csrc/infer_pointnet_seg.hip,
-DESIGN.md section 20): ``conv5`` has no activation, so the head's 4944-wide first layer folds to 832 columns on a row buffer
-``out1 | out2 | out3 | out4`` plus a per-cloud bias (``fold_partseg_head``); neither the concatenation nor ``out5`` is ever
-stored.  ``FrozenPointNetPartseg(net, precision="bf16")`` runs the two wide launches as ``pcl_pointnet_seg_global_infer_bf16_f32``
-and ``pcl_pointnet_seg_head_infer_bf16_f32``: conv4, conv5 and the head's four layers take bf16 operands (activations rounded to
-nearest even, every weight snapshot as bf16 in ``refresh()``) and accumulate in fp32; the T-Nets, the trunk, the product with
-``T128``, the row buffer, the epilogues, the max, the per-cloud bias and the logits stay fp32.
-
-``FrozenPointConv(net)`` is the same for ``networks.cls.pointconv.PointConvDensityClsSsg`` (csrc/infer_pointconv.hip, DESIGN.md
-section 24): per k-NN level the per-point product ``Uf = points W0[:, 3:]^T`` (stats-free library GEMM), then ONE
-``pcl_pointconv_level_infer_f32`` launch that runs the feature MLP, the WeightNet and the DensityNet of every row and the
-density-weighted contraction with its activations in LDS -- the ``[B*S, 16 C]`` contraction output is the only large tensor a
-level writes -- then the level's ``Linear(16 C -> C)`` as a stats-free GEMM of the family ``net.eval()`` selects, with the eval
-constants.  The ``group_all`` level runs the stats-free GEMMs and ``pcl_pointconv_contract_bn_f32``; the head runs the eval-mode
-head kernels.  Constructed directly.  ``FrozenPointConv(net, precision="bf16")`` runs every fused level launch as
-``pcl_pointconv_level_infer_bf16_f32``: layers 2 and 3 of the feature MLP take bf16 operands (activations rounded to nearest even,
-weights snapshot as bf16 in ``refresh()``) and accumulate in fp32; ``Uf``, layer 1, the WeightNet, the DensityNet, the epilogues,
-``z3``, the contraction and its output stay fp32, and so do the level's Linear, the ``group_all`` level, ``"module"`` fallbacks
-and the head.
-
-``FrozenPointConvPartseg(net)`` is the same for ``networks.seg.pointconv_partseg.PointConvDensity_partseg``:
-its eight levels are k-NN levels, and each one whose (neighbours, widths) have a kernel (``pcl_pointconv_seg_level_infer_supported``:
-feature MLPs of two or three layers, 16 or 32 neighbours) runs as ONE ``pcl_pointconv_seg_level_infer_f32`` launch plus its Linear,
-as above.  An interpolation level first runs the 3-NN interpolation and ``Uf = interpolated W0[:, 3:]^T`` over its N points, then
-that launch over N groups of 16 (the centres are the level's own points in FPS visiting order, as upstream), so no ``[B,N,16,C]``
-tensor exists.  The two 512-wide levels (``sa3``, ``in0``) have no kernel and run eval-mode copies of their modules; the head runs
-the stats-free GEMMs on the ``B N`` rows.  ``FrozenPointConvPartseg(net, precision="bf16")`` runs every fused level launch as
-``pcl_pointconv_seg_level_infer_bf16_f32``: the layers behind the first of the feature MLP (one at two layers, two at three) take
-bf16 operands (activations rounded to nearest even, weights snapshot as bf16 in ``refresh()``) and accumulate in fp32; ``Uf``,
-layer 1, the WeightNet, the DensityNet, the epilogues, the last activation, the contraction and its output stay fp32, and so do the
-3-NN interpolation, the level's Linear, the two ``"module"`` levels and the head."""
+All but the two PointNet++ evaluators are constructed directly: ``frozen()`` keeps its PointNet++ dispatch."""
 import copy
 import ctypes
 
@@ -89,7 +45,7 @@ def frozen(net, precision="fp32"):
     cls_label, sampling=None, lengths=None) -> [B, part_num, N]``.  ``lengths`` [B]: per-cloud point counts of a ragged batch
     (capacity N; rows from lengths[b] on are pad rows, any contents): every cloud's result is that of the cloud alone; the
     part-seg logits and ``fp1`` feature of pad points are exact zeros.  ``precision``: "fp32", or "bf16" for bf16 matrix operands
-    in the fused set-abstraction launches (module docstring); ``fnet.precision`` tells which."""
+    in the fused set-abstraction launches (``_FrozenEncoder``); ``fnet.precision`` tells which."""
     if precision not in PRECISIONS:
         raise ValueError(f"frozen(): precision must be one of {PRECISIONS}, got {precision!r}")
     if isinstance(net, PointNet2_cls):
@@ -126,19 +82,38 @@ def _pad32(t, fill):
     return out
 
 
-_OWN = object()                    # _SegStack(first=_OWN): the first weight is the first layer's own
+def _entry(name, precision):
+    """The entry point ``name`` (``..._f32``) for ``precision``: the bf16-operand form of a launch is named ``..._bf16_f32``."""
+    return name[:-len("f32")] + "bf16_f32" if precision == "bf16" else name
+
+
+def _rows_gemm(X, W, bias=None, in_scale=None, in_shift=None, slope=0.0, tag="fwd"):
+    """``act(in_scale * X + in_shift) W^T + bias`` -> [P, Cout]: the stats-free library GEMM (``pcl_linear_fwd_rows_f32``) on X [P, Cin]
+    and W [Cout, Cin]; without ``in_scale`` X is taken as it is.  ``tag``: the profile key's prefix -- ``"pt"`` for the per-point
+    product of a folded first layer, ``"fwd"`` for a layer of a chain."""
+    P = X.shape[0]
+    Cout, Cin = W.shape
+    Y = torch.empty((P, Cout), dtype=torch.float32, device=X.device)
+    _lib.call("pcl_linear_fwd_rows_f32", _p(X), _p(W), _p(bias), _p(in_scale), _p(in_shift), slope, P, Cin, Cout, _p(Y), None, None, None,
+              _stream(), tag=f"{tag}{Cin}x{Cout}")
+    return Y
+
+
+_OWN = object()                   # _SegStack(first=_OWN): the first weight is the first layer's own
 
 
 class _SegStack:
     """Snapshot of consecutive layers ``[(mlp, l)]`` for a frozen-inference launcher: dense fp32 weights ``Ws``, eval constants
-    ``scales`` / ``shifts``, the layer ``widths``, and the ctypes arrays ``c_widths / c_W / c_scale / c_shift`` over them.
+    ``scales`` / ``shifts``, the layer ``widths``, and the ctypes arrays ``c_widths / c_W / c_scale / c_shift`` over them;
+    ``operands`` is the list ``c_W`` points at.
 
     ``first``: what stands for the first weight -- by default a clone of the layer's own; ``None`` when the first layer is
-    folded and the kernel takes it apart from the arrays; or a tensor that replaces it.  ``bf16``: also ``Ws_bf16``, the weights
-    of layers 2 and up rounded once to bf16 (``[None, ...]``), and ``c_W`` points at those.  ``pad_last``: the last layer's
-    weight, scale and shift padded to a multiple of 32 rows (zero weights); ``widths`` keeps the layer's own.  ``bf16_first``
-    (with ``bf16``): ALL layers as bf16 -- ``_OWN`` rounds the first layer's own weight like the others, a bf16 tensor stands
-    for it (a folded weight its caller rounded straight from fp64); by default the first entry stays ``None``."""
+    folded and the kernel takes it apart from the arrays (the clone is then ``W0``, for the caller to slice); or a tensor that
+    replaces it.  ``bf16``: also ``Ws_bf16``, the weights of layers 2 and up rounded once to bf16 (``[None, ...]``), and ``c_W``
+    points at those.  ``pad_last``: the last layer's weight, scale and shift padded to a multiple of 32 rows (zero weights);
+    ``widths`` keeps the layer's own.  ``bf16_first`` (with ``bf16``): ALL layers as bf16 -- ``_OWN`` rounds the first layer's own
+    weight like the others, a bf16 tensor stands for it (a folded weight its caller rounded straight from fp64); by default the
+    first entry stays ``None``."""
 
     def __init__(self, layers, first=_OWN, bf16=False, pad_last=False, bf16_first=None):
         self.L = L = len(layers)
@@ -152,13 +127,16 @@ class _SegStack:
             self.Ws.append(W.contiguous().clone() if i or first is _OWN else first)
             self.scales.append(sc)
             self.shifts.append(sh)
-        operands = self.Ws
+        if first is None:
+            mlp, l = layers[0]
+            self.W0 = mlp.weights[l].detach().float().contiguous().clone()
+        self.operands = self.Ws
         if bf16:                                                       # the bf16 operands of layers 2 and up, rounded once here
-            operands = self.Ws_bf16 = [None] + [w.to(torch.bfloat16).contiguous() for w in self.Ws[1:]]
+            self.operands = self.Ws_bf16 = [None] + [w.to(torch.bfloat16).contiguous() for w in self.Ws[1:]]
             if bf16_first is not None:
-                operands[0] = self.Ws[0].to(torch.bfloat16).contiguous() if bf16_first is _OWN else bf16_first
+                self.operands[0] = self.Ws[0].to(torch.bfloat16).contiguous() if bf16_first is _OWN else bf16_first
         self.c_widths = (ctypes.c_int32 * L)(*self.widths)
-        self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in operands])
+        self.c_W = (ctypes.c_void_p * L)(*[None if w is None else w.data_ptr() for w in self.operands])
         self.c_scale = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.scales])
         self.c_shift = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.shifts])
 
@@ -169,59 +147,64 @@ class _Fused(_SegStack):
     def __init__(self, mlp, use_xyz, C, precision="fp32"):
         super().__init__([(mlp, l) for l in range(len(mlp.weights))], first=None, bf16=precision == "bf16")
         self.precision = precision
-        W0 = mlp.weights[0].detach().float().contiguous().clone()
         self.use_xyz, self.C, self.slope = use_xyz, C, float(mlp.slope)
-        off = 3 if use_xyz else 0
-        self.W0 = W0
+        W0, off = self.W0, 3 if use_xyz else 0
         self.ldw = W0.shape[1]
         self.Wx = W0[:, :3] if use_xyz else None                       # view: the kernel reads it with the row stride ldw
         self.inline = 0 < C <= 4
         self.Wf = None if C == 0 else (W0[:, off:] if self.inline else W0[:, off:].contiguous())
-        self.entry = "pcl_sa_level_infer_bf16_f32" if precision == "bf16" else "pcl_sa_level_infer_f32"
+        self.entry = _entry("pcl_sa_level_infer_f32", precision)
 
     def run(self, xyz, new_xyz, feature, idx, cnt, out, col0):
         B, N, _ = xyz.shape
         m, ns = idx.shape[1], idx.shape[2]
-        C1 = self.widths[0]
-        st = _stream()
         feat2 = feature.reshape(B * N, self.C).contiguous() if self.C else None
-        Uf = None
-        if self.C and not self.inline:
-            Uf = torch.empty((B * N, C1), dtype=torch.float32, device=xyz.device)
-            _lib.call("pcl_linear_fwd_rows_f32", _p(feat2), _p(self.Wf), None, None, None, 0.0, B * N, self.C, C1, _p(Uf), None, None, None,
-                      st, tag=f"pt{self.C}x{C1}")
+        Uf = _rows_gemm(feat2, self.Wf, tag="pt") if self.C and not self.inline else None
         _lib.call(self.entry, _p(xyz), _p(new_xyz), _p(Uf), _p(self.Wx), _p(feat2) if self.inline else None,
                   _p(self.Wf) if self.inline else None, self.C if self.inline else 0, self.ldw, _p(idx), _p(cnt), B, N, m, ns,
-                  len(self.widths), self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(out), out.shape[-1], col0, st)
+                  len(self.widths), self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(out), out.shape[-1], col0, _stream())
 
 
-class _GroupAllPlan:
-    """Snapshot of the GroupAll level: dense weights and eval constants of every layer."""
+class _RowsStack:
+    """Snapshot of a PointwiseMLP for the stats-free library GEMMs: dense weights and eval constants (conv bias folded into the
+    shift).  ``run(x [P, C0])`` chains ``_rows_gemm`` with the BatchNorm + activation of each layer folded into the next GEMM's
+    operand load -> (pre-BatchNorm output of the last layer, its scale, its shift); ``run_act`` applies them too."""
 
-    def __init__(self, mlp, use_xyz):
-        self.use_xyz, self.slope, self.last_act = use_xyz, float(mlp.slope), mlp.last_act
+    def __init__(self, mlp):
+        self.slope = float(mlp.slope)
+        self.out_slope = self.slope if mlp.last_act else 1.0
         self.Ws = [w.detach().float().contiguous().clone() for w in mlp.weights]
         consts = [_eval_consts(mlp, l) for l in range(len(self.Ws))]
         self.scales, self.shifts = [c[0] for c in consts], [c[1] for c in consts]
 
-    def run(self, xyz, feature):
-        B, N, _ = xyz.shape
-        dev = xyz.device
-        st = _stream()
-        cur = group_all(xyz, feature, self.use_xyz).reshape(B * N, -1)
-        P = B * N
+    def run(self, cur):
         sc = sh = None
         for W, scale, shift in zip(self.Ws, self.scales, self.shifts):
-            cout, cin = W.shape
-            Y = torch.empty((P, cout), dtype=torch.float32, device=dev)
-            _lib.call("pcl_linear_fwd_rows_f32", _p(cur), _p(W), None, _p(sc), _p(sh), self.slope, P, cin, cout, _p(Y), None, None, None, st,
-                      tag=f"fwd{cin}x{cout}")
-            cur, sc, sh = Y, scale, shift
-        C = cur.shape[1]
-        out = torch.empty((B, C), dtype=torch.float32, device=dev)
-        arg = torch.empty((B, C), dtype=torch.int32, device=dev)
-        ymax = torch.empty((B, C), dtype=torch.float32, device=dev)
-        _lib.call("pcl_bn_act_max_f32", _p(cur), _p(sc), _p(sh), self.slope if self.last_act else 1.0, B, N, C, _p(out), _p(arg), _p(ymax), st)
+            cur, sc, sh = _rows_gemm(cur, W, None, sc, sh, self.slope), scale, shift
+        return cur, sc, sh
+
+    def run_act(self, x):
+        Y, sc, sh = self.run(x)
+        out = torch.empty_like(Y)
+        _lib.call("pcl_bn_act_f32", _p(Y), _p(sc), _p(sh), self.out_slope, Y.shape[0], Y.shape[1], _p(out), _stream())
+        return out
+
+
+class _GroupAllPlan:
+    """Snapshot of the GroupAll level: the MLP as a chain of stats-free GEMMs (``_RowsStack``), then the BatchNorm + activation
+    of its last layer and the max over the cloud's points in one launch (``pcl_bn_act_max_f32``)."""
+
+    def __init__(self, mlp, use_xyz):
+        self.use_xyz, self.stack = use_xyz, _RowsStack(mlp)
+
+    def run(self, xyz, feature):
+        B, N, _ = xyz.shape
+        Y, sc, sh = self.stack.run(group_all(xyz, feature, self.use_xyz).reshape(B * N, -1))
+        C = Y.shape[1]
+        out = torch.empty((B, C), dtype=torch.float32, device=xyz.device)
+        arg = torch.empty((B, C), dtype=torch.int32, device=xyz.device)
+        ymax = torch.empty((B, C), dtype=torch.float32, device=xyz.device)
+        _lib.call("pcl_bn_act_max_f32", _p(Y), _p(sc), _p(sh), self.stack.out_slope, B, N, C, _p(out), _p(arg), _p(ymax), _stream())
         return out.view(B, 1, C)
 
 
@@ -232,14 +215,23 @@ def _fusable(mlp, use_xyz, C, ns):
     return mlp.n_layers <= 4 and bool(_lib.size_query("pcl_sa_level_infer_supported", int(ns), mlp.n_layers, *widths[:4]))
 
 
-class _FrozenEncoder:
-    """The set-abstraction levels of a PointNet++ network (``net.pointnet_modules``, input feature 3 wide): a plan per level and
-    scale, and the eval-mode copies of modules without a fused kernel.  Shared by the classification and part-seg evaluators."""
+class _Frozen:
+    """What the evaluators share.  ``NET``: the network class an evaluator takes.  The eval constants are snapshot once on the device
+    by ``refresh()`` (per layer ``scale = gamma / sqrt(running_var + eps)``, ``shift = beta - scale * running_mean``, folded conv
+    bias; dense weights), so a forward launches no small torch ops and computes no BatchNorm statistics; ``net`` itself is never
+    modified (parameters, running statistics, ``training`` flags)."""
+
+    NET = None
 
     def __init__(self, net, precision="fp32"):
+        name = type(self).__name__
+        if not isinstance(net, self.NET):
+            raise TypeError(f"{name} takes {self.NET.__module__.split('.', 1)[1]}.{self.NET.__name__}, got {type(net).__name__}")
+        if precision not in PRECISIONS:
+            raise ValueError(f"{name}: precision must be one of {PRECISIONS}, got {precision!r}")
         self.net = net
         self.precision = precision
-        self._copies = {}          # eval-mode copies of the heads and of levels without a fused kernel, kept across refresh()
+        self._copies = {}          # eval-mode copies of the heads and of modules without a fused kernel, kept across refresh()
         self.refresh()
 
     def _copy(self, key, module):
@@ -249,6 +241,30 @@ class _FrozenEncoder:
         else:
             c.load_state_dict(module.state_dict())        # same objects: the head kernels' plan cache keys on them
         return c
+
+    def _require_f32_gpu(self, x, what="tensor"):
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise TypeError(f"{type(self).__name__}: expected a float32 {what} on the GPU, got {x.dtype} on {x.device}")
+
+    def _fc_head(self, feature):
+        """``self.head`` (the eval-mode head kernels) on the rows of ``feature``, at most ``MAX_ROWS`` of them per call."""
+        logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, feature.shape[0], MAX_ROWS)]
+        return logits[0] if len(logits) == 1 else torch.cat(logits)
+
+
+class _FrozenEncoder(_Frozen):
+    """The set-abstraction levels of a PointNet++ network (``net.pointnet_modules``, input feature 3 wide): a plan per level and
+    scale, and the eval-mode copies of modules without a fused kernel.  Shared by the classification and part-seg evaluators.
+
+    Per ball-query level and scale: the per-point product ``Uf = feat W0[:, 3:]^T`` of the folded first layer (stats-free library
+    GEMM; narrow features such as SA1's normals fold inline instead), then ONE ``pcl_sa_level_infer_f32`` launch that runs the whole
+    MLP + max of every group with its activations in LDS and writes its column slice of the level's output.  The GroupAll level runs
+    the library's forward GEMMs stats-free with the snapshot constants, then its max.  A level whose shape has no fused kernel runs
+    an eval-mode copy of its own module.
+
+    ``precision="bf16"`` runs every fused set-abstraction launch as ``pcl_sa_level_infer_bf16_f32``: layers 2 and up take bf16
+    operands (activations rounded to nearest even, weights snapshot as bf16 once) and accumulate in fp32; the first layer, ``Uf``,
+    the epilogues, the max and every output stay fp32, and so do the GroupAll level, the FP levels and the heads."""
 
     def _refresh_encoder(self):
         net = self.net
@@ -308,7 +324,10 @@ class _FrozenEncoder:
 
 
 class FrozenPointNet2(_FrozenEncoder):
-    """See the module docstring.  ``refresh()`` re-reads weights and running statistics from the network."""
+    """Frozen evaluator of ``PointNet2_cls`` / ``PointNetMSG`` (``frozen(net)``): the encoder plan of ``_FrozenEncoder``, then the
+    eval-mode head kernels on at most 64 rows per call.  ``refresh()`` re-reads weights and running statistics from the network."""
+
+    NET = PointNet2_cls
 
     @torch.no_grad()
     def refresh(self):
@@ -324,9 +343,7 @@ class FrozenPointNet2(_FrozenEncoder):
         """-> ([feature of every set-abstraction level], logits [B, n_classes]).  ``lengths``: see ``frozen``."""
         lengths = self.net.resolve_lengths(xyz, sampling, lengths, self.net.pointnet_modules[0].n_points)
         feats = [f for _, f in self._encode(xyz, feature, sampling, lengths)]
-        feature = feats[-1].squeeze(dim=1)
-        logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, feature.shape[0], MAX_ROWS)]
-        return feats, logits[0] if len(logits) == 1 else torch.cat(logits)
+        return feats, self._fc_head(feats[-1].squeeze(dim=1))
 
 
 class _FusedFP(_SegStack):
@@ -336,29 +353,25 @@ class _FusedFP(_SegStack):
     channels; skips of at most 8 (other) channels fold inline, wider ones through the per-point table ``Us``."""
 
     def __init__(self, mlp, D1, n_onehot=0, head=()):
-        W0 = mlp.weights[0].detach().float().contiguous().clone()
-        self.D1, self.n_onehot, self.slope = D1, n_onehot, float(mlp.slope)
-        self.CS = D1 - n_onehot
-        self.inline = self.CS <= 8
-        self.W0 = W0
-        self.Woh = W0[:, :n_onehot].contiguous() if n_onehot else None
-        self.Wsk = None if self.CS == 0 else (W0[:, n_onehot:D1] if self.inline else W0[:, n_onehot:D1].contiguous())
-        self.Wc = W0[:, D1:].contiguous()
         layers = [(mlp, l, l < mlp.n_layers - 1 or mlp.last_act) for l in range(mlp.n_layers)]
         for h in head:
             layers += [(h, l, l < h.n_layers - 1 or h.last_act) for l in range(h.n_layers)]
         self.act_mask = sum(1 << i for i, (_, _, a) in enumerate(layers) if a)
         self.tap_layer = mlp.n_layers - 1 if head else None          # the level's own output, stored beside the head's
         super().__init__([(m, l) for m, l, _ in layers], first=None, pad_last=True)   # the last layer: padded to 32 columns
+        W0 = self.W0
+        self.D1, self.n_onehot, self.slope = D1, n_onehot, float(mlp.slope)
+        self.CS = D1 - n_onehot
+        self.inline = self.CS <= 8
+        self.Woh = W0[:, :n_onehot].contiguous() if n_onehot else None
+        self.Wsk = None if self.CS == 0 else (W0[:, n_onehot:D1] if self.inline else W0[:, n_onehot:D1].contiguous())
+        self.Wc = W0[:, D1:].contiguous()
 
     @staticmethod
-    def _rows(X, W, P):
-        """X [P, Cin] W^T -> [P, Cout] (stats-free library GEMM)."""
-        Cout, Cin = W.shape
-        Y = torch.empty((P, Cout), dtype=torch.float32, device=X.device)
-        _lib.call("pcl_linear_fwd_rows_f32", _p(X), _p(W), None, None, None, 0.0, P, Cin, Cout, _p(Y), None, None, None, _stream(),
-                  tag=f"pt{Cin}x{Cout}")
-        return Y
+    def _rows(X, W, P=None):
+        """X [P, Cin] W^T -> [P, Cout]: a product of the folded first layer (``_rows_gemm``, tagged ``pt``).  ``P`` is ``X.shape[0]``;
+        tests/test_inference_partseg_gpu.py states it."""
+        return _rows_gemm(X, W, tag="pt")
 
     def run(self, xyz1, xyz2, skip, coarse, onehot=None, lengths=None):
         """xyz1 [B,N,3], xyz2 [B,S,3], skip [B,N,D1 - n_onehot] (or None), coarse [B,S,D2], onehot [B, n_onehot]
@@ -367,7 +380,7 @@ class _FusedFP(_SegStack):
         B, N, _ = xyz1.shape
         S = coarse.shape[1]
         dev = xyz1.device
-        Uc = self._rows(coarse.reshape(B * S, -1).contiguous(), self.Wc, B * S)
+        Uc = self._rows(coarse.reshape(B * S, -1).contiguous(), self.Wc)
         idx3 = w3 = None
         if S == 1:                                                   # a one-row coarse level: a per-cloud bias
             cb, Uc = Uc, None
@@ -375,13 +388,13 @@ class _FusedFP(_SegStack):
             idx3, w3 = three_nn(xyz1, xyz2, lengths1=lengths)
             cb = None
         if self.Woh is not None:
-            c = self._rows(onehot.reshape(B, self.n_onehot).float().contiguous(), self.Woh, B)
+            c = self._rows(onehot.reshape(B, self.n_onehot).float().contiguous(), self.Woh)
             cb = c if cb is None else cb + c
         Us = fs = None
         if self.CS:
             fs = skip.reshape(B * N, self.CS).contiguous()
             if not self.inline:
-                Us, fs = self._rows(fs, self.Wsk, B * N), None
+                Us, fs = self._rows(fs, self.Wsk), None
         out = torch.empty((B, N, self.widths[-1]), dtype=torch.float32, device=dev)
         tap = None if self.tap_layer is None else torch.empty((B, N, self.widths[self.tap_layer]), dtype=torch.float32, device=dev)
         head = (_p(Us), _p(fs), _p(self.Wsk) if fs is not None else None, self.CS if fs is not None else 0, self.W0.shape[1], _p(Uc),
@@ -407,11 +420,18 @@ def _head_fusable(fp_mlp, head1, head2):
 
 
 class FrozenPointNet2Partseg(_FrozenEncoder):
-    """Frozen evaluator of ``PointNet2_partseg`` / its ``PointNetMSG`` (see the module docstring): the encoder plan of the
-    classifiers, one launch per feature-propagation level, the head fused into the last one.  ``refresh()`` re-reads weights
-    and running statistics from the network."""
+    """Frozen evaluator of ``PointNet2_partseg`` / its ``PointNetMSG`` (``frozen(net)``): the encoder plan of the classifiers
+    (``_FrozenEncoder``), one launch per feature-propagation level, the head fused into the last one.  ``refresh()`` re-reads
+    weights and running statistics from the network.
 
-    N_ONEHOT = 16                  # FP1's skip: cat(one-hot class label [16], xyz [3], feature [3])  (pointnet2_partseg.py:170-173)
+    Each feature-propagation level runs the stats-free GEMMs of its folded first layer (``Uc = coarse W0c^T`` at the coarse
+    resolution, ``Us = skip W0s^T`` per point, or the skip inline when it is narrow; the one-hot class label as a per-cloud bias)
+    and then ONE ``pcl_fp_level_infer_f32`` launch.  The last level carries the head (Conv1d + BN, Dropout = identity, Conv1d) in
+    the same launch, which also stores the level's own output (the tap).  FP levels and heads of other widths run eval-mode copies
+    of their own modules."""
+
+    NET = PointNet2_partseg
+    N_ONEHOT = 16                 # FP1's skip: cat(one-hot class label [16], xyz [3], feature [3])  (pointnet2_partseg.py:170-173)
 
     @torch.no_grad()
     def refresh(self):
@@ -486,7 +506,7 @@ class FrozenPointNet2Partseg(_FrozenEncoder):
         return [l1, l2, l3, f3, f2, f1], logits.permute(0, 2, 1)
 
 
-class FrozenPointNet:
+class FrozenPointNet(_Frozen):
     """Frozen evaluator of ``networks.cls.pointnet.PointNet``: ``fnet(x, lengths=None) -> [B, n_classes]`` for ``x`` [B, 3, N] (the
     network's input layout) of any strides -- a transposed view of a loader's [B, N, 3] is read as it is, no copy.  ``lengths``
     (``misc.ops._lengths``): per-cloud point counts of a ragged batch of capacity N; pad points may hold anything and every cloud's
@@ -494,54 +514,38 @@ class FrozenPointNet:
 
     ``plan`` is ``"fused"`` when ``net.convs`` has the kernel's shape (3 -> 64/64/64/128/1024, BatchNorm, activation after every
     layer): dense weights, the eval constants of ``_eval_consts`` and the ctypes arrays are snapshot once, and a forward is
-    ``pcl_pointnet_stack_infer_f32`` + the eval-mode head kernels (at most ``MAX_ROWS`` rows per call).  A stack of other widths
-    gives ``"module"``: an eval-mode copy of ``net.convs`` runs, dense through ``group_max``, ragged through ``mlp_segment_max``.
-    ``refresh()`` re-reads weights and running statistics; ``net`` itself is never modified.
+    ``pcl_pointnet_stack_infer_f32`` (csrc/infer_pointnet.hip: the five convs and the max over the points with the activations in
+    LDS, nothing but per-tile maxima written) + the eval-mode head kernels (at most ``MAX_ROWS`` rows per call).  A stack of other
+    widths gives ``"module"``: an eval-mode copy of ``net.convs`` runs, dense through ``group_max``, ragged through
+    ``mlp_segment_max``.  ``refresh()`` re-reads weights and running statistics; ``net`` itself is never modified.
 
-    ``precision``: "fp32", or "bf16" for bf16 matrix operands in layers 2-5 of the fused stack (module docstring;
-    ``fnet.precision`` tells which).  The head stays fp32, and a ``"module"`` plan ignores the precision and stays fp32.
+    ``precision``: "fp32", or "bf16" (``fnet.precision`` tells which) to run the fused stack as
+    ``pcl_pointnet_stack_infer_bf16_f32``: layers 2-5 take bf16 operands (activations rounded to nearest even, weights snapshot as
+    bf16 in ``refresh()``) and accumulate in fp32; layer 1, the epilogues, the max, the global feature and the head stay fp32
+    (DESIGN.md section 21).  A ``"module"`` plan ignores the precision and stays fp32.
 
     The class is constructed directly; ``frozen(net)`` still takes the PointNet++ networks only (its tests pin that), and taking
     PointNet there is a later change."""
 
-    def __init__(self, net, precision="fp32"):
-        if not isinstance(net, PointNet):
-            raise TypeError(f"FrozenPointNet takes networks.cls.pointnet.PointNet, got {type(net).__name__}")
-        if precision not in PRECISIONS:
-            raise ValueError(f"FrozenPointNet: precision must be one of {PRECISIONS}, got {precision!r}")
-        self.net = net
-        self.precision = precision
-        self._convs = self._head = None
-        self.refresh()
-
-    @staticmethod
-    def _refresh_copy(c, module):
-        if c is None:
-            return copy.deepcopy(module).eval()
-        c.load_state_dict(module.state_dict())            # same objects: the head kernels' plan cache keys on them
-        return c
+    NET = PointNet
 
     @torch.no_grad()
     def refresh(self):
         net, mlp = self.net, self.net.convs
-        self._head = self._refresh_copy(self._head, torch.nn.Sequential(net.linear1, net.bn6, net.relu, net.dp1, net.linear2))
+        self._head = self._copy("head", torch.nn.Sequential(net.linear1, net.bn6, net.relu, net.dp1, net.linear2))
         self.head = list(self._head)
-        widths = [w.shape[0] for w in mlp.weights]
-        L = len(widths)
-        c_widths = (ctypes.c_int32 * L)(*widths)
+        L = len(mlp.weights)
+        c_widths = (ctypes.c_int32 * L)(*[w.shape[0] for w in mlp.weights])
         C0 = mlp.weights[0].shape[1]
         fused = mlp.bn and mlp.last_act and bool(_lib.lib().pcl_pointnet_stack_infer_supported(C0, L, c_widths))
         self.plan = "fused" if fused else "module"
         if not fused:
-            self._convs = self._refresh_copy(self._convs, mlp)
+            self._convs = self._copy("convs", mlp)
             return self
-        self.slope, self.width, self.c_widths = float(mlp.slope), widths[-1], c_widths
+        self.slope = float(mlp.slope)
         bf16 = self.precision == "bf16"                                # layers 2-5 then take the stack's bf16 operands
-        s = _SegStack([(mlp, l) for l in range(L)], bf16=bf16)
-        self.Ws, self.scales, self.shifts, self.c_W, self.c_scale, self.c_shift = s.Ws, s.scales, s.shifts, s.c_W, s.c_scale, s.c_shift
-        if bf16:
-            self.Ws_bf16 = s.Ws_bf16
-        self.entry = "pcl_pointnet_stack_infer_bf16_f32" if bf16 else "pcl_pointnet_stack_infer_f32"
+        vars(self).update(vars(_SegStack([(mlp, l) for l in range(L)], bf16=bf16)))    # Ws, scales, shifts, c_*; bf16: Ws_bf16
+        self.entry = _entry("pcl_pointnet_stack_infer_f32", self.precision)
         return self
 
     def __call__(self, x, lengths=None):
@@ -554,12 +558,12 @@ class FrozenPointNet:
                 return self._convs(x.transpose(1, 2).contiguous()[:, None], group_max=N).reshape(B, -1)
             lengths, row_off, R, row_cloud = packed_layout(lengths, B, N, x.device)
             return mlp_segment_max(self._convs, pack_rows(x.transpose(1, 2), lengths, row_off, R), row_off, row_cloud, B)
-        if not x.is_cuda or x.dtype != torch.float32:
-            raise TypeError(f"FrozenPointNet: expected a float32 tensor on the GPU, got {x.dtype} on {x.device}")
+        self._require_f32_gpu(x)
         lengths = _lengths(lengths, B, N, x.device)
-        ws_bytes = _lib.size_query("pcl_pointnet_stack_infer_workspace_bytes", B, N, self.width)
+        width = self.widths[-1]
+        ws_bytes = _lib.size_query("pcl_pointnet_stack_infer_workspace_bytes", B, N, width)
         ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device)
-        out = torch.empty((B, self.width), dtype=torch.float32, device=x.device)
+        out = torch.empty((B, width), dtype=torch.float32, device=x.device)
         W0 = self.Ws[0]
         _lib.call(self.entry, _p(x), x.stride(0), x.stride(2), x.stride(1), _p(lengths), B, N, C0, _p(W0), W0.shape[1],
                   len(self.Ws), self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(ws), ws_bytes, _p(out), out.shape[1],
@@ -572,8 +576,7 @@ class FrozenPointNet:
         if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.net.convs.spec[0]:
             raise ValueError(f"FrozenPointNet: x must be [B,{self.net.convs.spec[0]},N], got {tuple(getattr(x, 'shape', ()))}")
         feature = self._stack(x, lengths)
-        logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, feature.shape[0], MAX_ROWS)]
-        return feature, logits[0] if len(logits) == 1 else torch.cat(logits)
+        return feature, self._fc_head(feature)
 
 
 # ---------------------------------------------------------------------------------------------- PointNet part segmentation
@@ -622,7 +625,7 @@ def _seg_rows(x, W, scale, shift, slope, out=None):
     return out
 
 
-class FrozenPointNetPartseg:
+class FrozenPointNetPartseg(_Frozen):
     """Frozen evaluator of ``networks.seg.pointnet_partseg.PointNet_partseg``: ``fnet(point_cloud, label, lengths=None) ->
     [B, part_num, N]`` for ``point_cloud`` [B, 3, N] of any strides and ``label`` [B, 16].  ``lengths`` (``misc.ops._lengths``):
     per-cloud point counts of a ragged batch of capacity N; pad points may hold anything, every cloud's result is bit for bit
@@ -631,28 +634,22 @@ class FrozenPointNetPartseg:
     ``plan`` is ``"fused"`` when every stack has its kernel's shape (``pcl_pointnet_seg_infer_supported``; BatchNorm and the
     activation after every layer but ``conv5``'s, one slope): weights, eval constants, the folded head (``fold_partseg_head``)
     and the transposed ``fstn.fc3`` (``transposed_fc3``) are snapshot once, and a forward is the four launches of
-    csrc/infer_pointnet_seg.hip with the B-row tails between them.  Anything else gives ``"module"``: an eval-mode copy of the
-    whole network runs (``forward``; ragged ``forward_packed`` scattered into zeros).  ``refresh()`` re-reads weights and running
-    statistics; ``net`` itself is never modified.  Constructed directly: ``frozen()`` keeps its PointNet++ dispatch.
+    csrc/infer_pointnet_seg.hip with the B-row tails between them.  ``conv5`` has no activation, so the
+    head's 4944-wide first layer folds to 832 columns on a row buffer ``out1 | out2 | out3 | out4`` plus a per-cloud bias
+    (``fold_partseg_head``); neither the concatenation nor ``out5`` is ever stored.  Anything else gives ``"module"``: an eval-mode
+    copy of the whole network runs (``forward``; ragged ``forward_packed`` scattered into zeros).  ``refresh()`` re-reads weights and
+    running statistics; ``net`` itself is never modified.  Constructed directly: ``frozen()`` keeps its PointNet++ dispatch.
 
-    ``precision``: "fp32", or "bf16" for bf16 matrix operands in the global and head launches (module docstring, DESIGN.md
-    section 23; ``fnet.precision`` tells which): every weight of the two launches is snapshot as bf16 in ``refresh()``, the folded
-    ``Wrow`` rounded once straight from fp64.  The two T-Net launches, the trunk, the B-row tails, ``T3``, ``T128``, the row buffer
-    and the per-cloud bias stay fp32, a forward allocates what the fp32 forward does, and a ``"module"`` plan ignores the
-    precision and stays fp32."""
+    ``precision``: "fp32", or "bf16" (``fnet.precision`` tells which) to run the two wide launches as
+    ``pcl_pointnet_seg_global_infer_bf16_f32`` and ``pcl_pointnet_seg_head_infer_bf16_f32``: conv4, conv5 and the head's four layers
+    take bf16 operands (activations rounded to nearest even) and accumulate in fp32; every weight of the two launches is snapshot
+    as bf16 in ``refresh()``, the folded ``Wrow`` rounded once straight from fp64.  The two T-Net launches, the trunk, the product
+    with ``T128``, the B-row tails, ``T3``, ``T128``, the row buffer, the epilogues, the max, the per-cloud bias and the logits stay
+    fp32, a forward allocates what the fp32 forward does, and a ``"module"`` plan ignores the precision and stays fp32."""
 
+    NET = PointNet_partseg
     N_LABEL = 16
     LDF = 832                      # row stride of the row buffer out1 | out2 | out3 | out4
-
-    def __init__(self, net, precision="fp32"):
-        if not isinstance(net, PointNet_partseg):
-            raise TypeError(f"FrozenPointNetPartseg takes networks.seg.pointnet_partseg.PointNet_partseg, got {type(net).__name__}")
-        if precision not in PRECISIONS:
-            raise ValueError(f"FrozenPointNetPartseg: precision must be one of {PRECISIONS}, got {precision!r}")
-        self.net = net
-        self.precision = precision
-        self._module = None
-        self.refresh()
 
     @staticmethod
     def _fusable(net):
@@ -694,7 +691,7 @@ class FrozenPointNetPartseg:
         net = self.net
         self.plan = "fused" if self._fusable(net) else "module"
         if self.plan == "module":
-            self._module = FrozenPointNet._refresh_copy(self._module, net)
+            self._module = self._copy("net", net)
             return self
         self.slope, self.part_num = float(net.conv1.slope), net.convs4.out_features
         self.stn = _SegStack([(net.stn.convs, l) for l in range(3)])
@@ -718,13 +715,11 @@ class FrozenPointNetPartseg:
         self.head = _SegStack([(net.convs, l) for l in range(3)], first=Wrow, bf16=bf16, bf16_first=Wrow16)
         self.Wout = Wout
         self.head_widths = (ctypes.c_int32 * 4)(*self.head.widths, self.part_num)
-        operands = self.head.Ws + [Wout]
         if bf16:
-            self.Wout_bf16 = Wout.to(torch.bfloat16).contiguous()
-            operands = self.head.Ws_bf16 + [self.Wout_bf16]
-        self.head_W = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in operands])
-        self.global_entry = "pcl_pointnet_seg_global_infer_bf16_f32" if bf16 else "pcl_pointnet_seg_global_infer_f32"
-        self.head_entry = "pcl_pointnet_seg_head_infer_bf16_f32" if bf16 else "pcl_pointnet_seg_head_infer_f32"
+            Wout = self.Wout_bf16 = Wout.to(torch.bfloat16).contiguous()
+        self.head_W = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in self.head.operands + [Wout]])
+        self.global_entry = _entry("pcl_pointnet_seg_global_infer_f32", self.precision)
+        self.head_entry = _entry("pcl_pointnet_seg_head_infer_f32", self.precision)
         return self
 
     def __call__(self, point_cloud, label, lengths=None):
@@ -752,8 +747,7 @@ class FrozenPointNetPartseg:
             rows, row_off = self._module.forward_packed(x, label, lengths)
             lengths = _lengths(lengths, B, N, x.device)
             return None, None, None, unpack_rows(rows, lengths, row_off, N).permute(0, 2, 1)
-        if not x.is_cuda or x.dtype != torch.float32:
-            raise TypeError(f"FrozenPointNetPartseg: expected a float32 point cloud on the GPU, got {x.dtype} on {x.device}")
+        self._require_f32_gpu(x, "point cloud")
         if label.device != x.device or label.dtype != torch.float32:
             raise TypeError(f"FrozenPointNetPartseg: label must be float32 on {x.device}, got {label.dtype} on {label.device}")
         dev, st = x.device, _stream()
@@ -821,14 +815,13 @@ class _LevelLinear:
         P, K = X.shape
         C = self.W.shape[0]
         st = _stream()
-        Y = torch.empty((P, C), dtype=torch.float32, device=X.device)
         flush = _linear_flush(K, P)
         if flush:
+            Y = torch.empty((P, C), dtype=torch.float32, device=X.device)
             _lib.call("pcl_frag_linear_fwd_f32", _p(X), K, _p(self.W), K, _p(self.bias), None, None, 0.0, P, K, C, _p(Y), C, None, None,
                       flush, st, tag=f"fwd{K}x{C}")
         else:
-            _lib.call("pcl_linear_fwd_rows_f32", _p(X), _p(self.W), _p(self.bias), None, None, 0.0, P, K, C, _p(Y), None, None, None, st,
-                      tag=f"fwd{K}x{C}")
+            Y = _rows_gemm(X, self.W, self.bias)
         out = torch.empty_like(Y)
         _lib.call("pcl_bn_act_f32", _p(Y), _p(self.scale), _p(self.shift), self.slope, P, C, _p(out), st)
         return out
@@ -851,19 +844,17 @@ def _pointconv_fusable(sa, D):
 class _FusedPointConv(_SegStack):
     """Snapshot of one k-NN PointConv level for pcl_pointconv_level_infer_f32 (or, ``precision="bf16"``,
     pcl_pointconv_level_infer_bf16_f32): the feature MLP (first layer folded), the packed small nets and the level's Linear.
-    ``entry``: another entry point of the same argument list and of that precision (pcl_pointconv_seg_level_infer_f32 /
-    pcl_pointconv_seg_level_infer_bf16_f32: feature MLPs of 2 or 3 layers)."""
+    ``entry``: the fp32 name of another entry point of the same argument list (pcl_pointconv_seg_level_infer_f32: feature MLPs of
+    2 or 3 layers)."""
 
-    def __init__(self, sa, D, precision="fp32", entry=None):
+    def __init__(self, sa, D, precision="fp32", entry="pcl_pointconv_level_infer_f32"):
         mlp = sa.mlp
         super().__init__([(mlp, l) for l in range(mlp.n_layers)], first=None, bf16=precision == "bf16")
         self.precision = precision
-        self.entry = entry or ("pcl_pointconv_level_infer_bf16_f32" if precision == "bf16" else "pcl_pointconv_level_infer_f32")
-        self.operands = self.Ws_bf16 if precision == "bf16" else self.Ws           # what c_W points at
-        W0 = mlp.weights[0].detach().float().contiguous().clone()
+        self.entry = _entry(entry, precision)
         self.D, self.slope = D, float(mlp.slope)
-        self.W0, self.ldw = W0, W0.shape[1]                            # Wx = W0[:, :3]: the kernel reads it with the row stride ldw
-        self.Wf = W0[:, 3:].contiguous() if D else None
+        self.ldw = self.W0.shape[1]                                    # Wx = W0[:, :3]: the kernel reads it with the row stride ldw
+        self.Wf = self.W0[:, 3:].contiguous() if D else None
         self.nets = pack_small_nets(sa.weightnet, sa.densitynet)
         self.linear = _LevelLinear(sa.linear)
 
@@ -872,55 +863,20 @@ class _FusedPointConv(_SegStack):
         B, N, _ = xyz.shape
         S, ns = idx.shape[1], idx.shape[2]
         C1, C3 = self.widths[0], self.widths[-1]
-        st = _stream()
-        Uf = None
-        if self.D:
-            Uf = torch.empty((B * N, C1), dtype=torch.float32, device=xyz.device)
-            _lib.call("pcl_linear_fwd_rows_f32", _p(points.reshape(B * N, self.D)), _p(self.Wf), None, None, None, 0.0, B * N, self.D, C1, _p(Uf),
-                      None, None, None, st, tag=f"pt{self.D}x{C1}")
+        Uf = _rows_gemm(points.reshape(B * N, self.D), self.Wf, tag="pt") if self.D else None
         out = torch.empty((B * S, POINTCONV_M * C3), dtype=torch.float32, device=xyz.device)
         if any(t is not None and t.data_ptr() % 16 for t in (Uf, out, *self.operands[1:])):      # the entry point's precondition (pcl_hip.h)
             raise ValueError(f"{self.entry}: Uf, the weights and out must be 16-byte aligned")
         rows = B * S * ns
         _lib.call(self.entry, _p(xyz), _p(new_xyz), _p(Uf), _p(self.W0), self.ldw, _p(density), _p(idx), B, N, S, ns, self.L,
-                  self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(self.nets), POINTCONV_M, _p(out), out.shape[1], st,
-                  algo_flops=2 * rows * (3 * C1 + sum(a * b for a, b in zip(self.widths, self.widths[1:])) + POINTCONV_M * C3 + 296),
+                  self.c_widths, self.c_W, self.c_scale, self.c_shift, self.slope, _p(self.nets), POINTCONV_M, _p(out), out.shape[1],
+                  _stream(), algo_flops=2 * rows * (3 * C1 + sum(a * b for a, b in zip(self.widths, self.widths[1:])) + POINTCONV_M * C3 + 296),
                   tag=f"pointconv{ns}x{C3}" if self.L == 3 else f"pointconv{ns}x{C3}L{self.L}")
         return out
 
     def run(self, xyz, new_xyz, points, idx, density):
         B, S = idx.shape[0], idx.shape[1]
         return self.linear.run(self.contract(xyz, new_xyz, points, idx, density)).view(B, S, -1)
-
-
-class _RowsStack:
-    """Snapshot of a PointwiseMLP for the stats-free library GEMMs: dense weights and eval constants (conv bias folded into the
-    shift).  ``run(x [P, C0])`` chains ``pcl_linear_fwd_rows_f32`` with the BatchNorm + activation of each layer folded into the
-    next GEMM's operand load -> (pre-BatchNorm output of the last layer, its scale, its shift); ``run_act`` applies them too."""
-
-    def __init__(self, mlp):
-        self.slope = float(mlp.slope)
-        self.out_slope = self.slope if mlp.last_act else 1.0
-        self.Ws = [w.detach().float().contiguous().clone() for w in mlp.weights]
-        consts = [_eval_consts(mlp, l) for l in range(len(self.Ws))]
-        self.scales, self.shifts = [c[0] for c in consts], [c[1] for c in consts]
-
-    def run(self, cur):
-        P, st = cur.shape[0], _stream()
-        sc = sh = None
-        for W, scale, shift in zip(self.Ws, self.scales, self.shifts):
-            cout, cin = W.shape
-            Y = torch.empty((P, cout), dtype=torch.float32, device=cur.device)
-            _lib.call("pcl_linear_fwd_rows_f32", _p(cur), _p(W), None, _p(sc), _p(sh), self.slope, P, cin, cout, _p(Y), None, None, None, st,
-                      tag=f"fwd{cin}x{cout}")
-            cur, sc, sh = Y, scale, shift
-        return cur, sc, sh
-
-    def run_act(self, x):
-        Y, sc, sh = self.run(x)
-        out = torch.empty_like(Y)
-        _lib.call("pcl_bn_act_f32", _p(Y), _p(sc), _p(sh), self.out_slope, Y.shape[0], Y.shape[1], _p(out), _stream())
-        return out
 
 
 class _PointConvGroupAll:
@@ -947,36 +903,30 @@ class _PointConvGroupAll:
         return _pointconv_linear(self.linear, out.view(B, 1, -1))
 
 
-class FrozenPointConv:
+class FrozenPointConv(_Frozen):
     """Frozen evaluator of ``networks.cls.pointconv.PointConvDensityClsSsg``: ``fnet(xyz [B,3,N], start_idx=None, knn_lists=None,
     sampling=None) -> [B, n_classes]``, the signature of ``net.forward``; ``fnet.run(...)`` also returns the three level features
     (channel-last: ``[B, S, C]``).  Index lists and densities come from the network's own ``sa.sample`` (or a handle of
-    ``net.precompute_sampling``).
+    ``net.precompute_sampling``).  Constructed directly.
 
-    ``fnet.levels`` names the plan per level: ``"fused"`` for a k-NN level whose shape has a kernel
-    (``pcl_pointconv_level_infer_supported``; module docstring), ``"all"`` for a ``group_all`` level of the usual small nets,
-    ``"module"`` otherwise -- an eval-mode copy of the level's own module runs.  ``refresh()`` re-reads weights and running
-    statistics; ``net`` itself is never modified (parameters, buffers, ``training`` flags).  ``precision``: "fp32", or "bf16" for
-    bf16 matrix operands in layers 2 and 3 of the fused level launches (module docstring); ``fnet.precision`` tells which.
-    ``levels`` does not depend on it, and everything but the fused launches is the same code on the same types."""
+    ``fnet.levels`` names the plan per level.  ``"fused"`` for a k-NN level whose shape has a kernel
+    (``pcl_pointconv_level_infer_supported``; csrc/infer_pointconv.hip): the per-point product ``Uf = points
+    W0[:, 3:]^T`` (stats-free library GEMM), then ONE ``pcl_pointconv_level_infer_f32`` launch that runs the feature MLP, the
+    WeightNet and the DensityNet of every row and the density-weighted contraction with its activations in LDS -- the ``[B*S, 16
+    C]`` contraction output is the only large tensor a level writes -- then the level's ``Linear(16 C -> C)`` as a stats-free GEMM of
+    the family ``net.eval()`` selects, with the eval constants.  ``"all"`` for a ``group_all`` level of the usual small nets: the
+    stats-free GEMMs and ``pcl_pointconv_contract_bn_f32``.  ``"module"`` otherwise -- an eval-mode copy of the level's own module
+    runs.  The head runs the eval-mode head kernels.  ``refresh()`` re-reads weights and running statistics; ``net`` itself is
+    never modified (parameters, buffers, ``training`` flags).
 
-    def __init__(self, net, precision="fp32"):
-        if precision not in PRECISIONS:
-            raise ValueError(f"FrozenPointConv: precision must be one of {PRECISIONS}, got {precision!r}")
-        if not isinstance(net, PointConvDensityClsSsg):
-            raise TypeError(f"FrozenPointConv takes networks.cls.pointconv.PointConvDensityClsSsg, got {type(net).__name__}")
-        self.net = net
-        self.precision = precision
-        self._copies = {}
-        self.refresh()
+    ``precision``: "fp32", or "bf16" (``fnet.precision`` tells which) to run every fused level launch as
+    ``pcl_pointconv_level_infer_bf16_f32``: layers 2 and 3 of the feature MLP take bf16 operands (activations rounded to nearest
+    even, weights snapshot as bf16 in ``refresh()``) and accumulate in fp32; ``Uf``, layer 1, the WeightNet, the DensityNet, the
+    epilogues, ``z3``, the contraction and its output stay fp32, and so do the level's Linear, the ``group_all`` level, ``"module"``
+    fallbacks and the head.  ``levels`` does not depend on it, and everything but the fused launches is the same code on the same
+    types."""
 
-    def _copy(self, key, module):
-        c = self._copies.get(key)
-        if c is None:
-            c = self._copies[key] = copy.deepcopy(module).eval()
-        else:
-            c.load_state_dict(module.state_dict())        # same objects: the head kernels' plan cache keys on them
-        return c
+    NET = PointConvDensityClsSsg
 
     @torch.no_grad()
     def refresh(self):
@@ -1013,8 +963,7 @@ class FrozenPointConv:
         """-> ([feature of sa1, sa2, sa3: [B, S, C]], logits [B, n_classes])."""
         if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[1] != 3:
             raise ValueError(f"FrozenPointConv: xyz must be [B,3,N], got {tuple(getattr(xyz, 'shape', ()))}")
-        if not xyz.is_cuda or xyz.dtype != torch.float32:
-            raise TypeError(f"FrozenPointConv: expected a float32 tensor on the GPU, got {xyz.dtype} on {xyz.device}")
+        self._require_f32_gpu(xyz)
         net = self.net
         B = xyz.shape[0]
         SamplingPrefetch.adopt_sampling(sampling)
@@ -1038,16 +987,10 @@ class FrozenPointConv:
                     new_xyz = nx.permute(0, 2, 1)
             feats.append(points)
             pts = new_xyz.contiguous() if new_xyz is not None else None
-        feature = feats[-1].reshape(B, -1)
-        logits = [fc_head(self.head, feature[r:r + MAX_ROWS]) for r in range(0, B, MAX_ROWS)]
-        return feats, logits[0] if len(logits) == 1 else torch.cat(logits)
+        return feats, self._fc_head(feats[-1].reshape(B, -1))
 
 
 # ---------------------------------------------------------------------------------------------- PointConv part segmentation
-POINTCONV_SEG_ENTRY = "pcl_pointconv_seg_level_infer_f32"
-POINTCONV_SEG_ENTRIES = {"fp32": POINTCONV_SEG_ENTRY, "bf16": "pcl_pointconv_seg_level_infer_bf16_f32"}
-
-
 def _pointconv_seg_fusable(level, D):
     """A k-NN level (set abstraction or interpolation) of the usual small nets whose shape ``pcl_pointconv_seg_level_infer_f32``
     has a kernel for.  In the query C2 = widths[1] and C3 = widths[L-1] (include/pcl_hip.h)."""
@@ -1059,33 +1002,31 @@ def _pointconv_seg_fusable(level, D):
     return bool(_lib.size_query("pcl_pointconv_seg_level_infer_supported", int(level.nsample), len(w), w[0], w[1], w[-1], POINTCONV_M))
 
 
-class FrozenPointConvPartseg:
+class FrozenPointConvPartseg(_Frozen):
     """Frozen evaluator of ``networks.seg.pointconv_partseg.PointConvDensity_partseg``: ``fnet(xyz [B,N,3], cls_label=None,
     sampling=None, start_idx=None) -> [B, N, part_num]``, the signature and layout of ``net.forward`` (``cls_label`` is accepted
     and unused, as there); ``fnet.run(...)`` also returns the eight level outputs (channel-last ``[B, S, C]``, in call order
     ``sa0..sa3, in0..in3``; an interpolation level's rows are in its FPS visiting order, as upstream).  ``sampling``: a handle of
     ``net.precompute_sampling(xyz)``; without one the evaluator calls it with ``start_idx`` (eight [B] int32 FPS starts, or None
-    for random ones).
+    for random ones).  Constructed directly.
 
-    ``fnet.levels`` names the plan per level: ``"fused"`` for a level whose shape has a kernel
-    (``pcl_pointconv_seg_level_infer_supported``; module docstring), ``"module"`` otherwise -- an eval-mode copy of the level's own
-    module runs on the same sampling entry.  ``refresh()`` re-reads weights and running statistics; ``net`` itself is never
-    modified (parameters, buffers, ``training`` flags).  ``precision``: "fp32", or "bf16" for bf16 matrix operands in the layers
-    behind the first of the fused level launches (module docstring); ``fnet.precision`` tells which.  ``levels`` does not depend
-    on it, and everything but the fused launches -- the interpolation, ``Uf``, each level's Linear, the ``"module"`` levels, the
-    head -- is the same code on the same types."""
+    ``fnet.levels`` names the plan per level.  The eight levels are k-NN levels, and each one whose
+    (neighbours, widths) have a kernel (``pcl_pointconv_seg_level_infer_supported``: feature MLPs of two or three layers, 16 or 32
+    neighbours) is ``"fused"``: ONE ``pcl_pointconv_seg_level_infer_f32`` launch plus its Linear, as in ``FrozenPointConv``.  An
+    interpolation level first runs the 3-NN interpolation and ``Uf = interpolated W0[:, 3:]^T`` over its N points, then that launch
+    over N groups of 16 (the centres are the level's own points in FPS visiting order, as upstream), so no ``[B,N,16,C]`` tensor
+    exists.  ``"module"`` otherwise -- an eval-mode copy of the level's own module runs on the same sampling entry: the two 512-wide
+    levels (``sa3``, ``in0``) have no kernel.  The head runs the stats-free GEMMs on the ``B N`` rows.  ``refresh()`` re-reads
+    weights and running statistics; ``net`` itself is never modified (parameters, buffers, ``training`` flags).
 
-    def __init__(self, net, precision="fp32"):
-        if precision not in PRECISIONS:
-            raise ValueError(f"FrozenPointConvPartseg: precision must be one of {PRECISIONS}, got {precision!r}")
-        if not isinstance(net, PointConvDensity_partseg):
-            raise TypeError(f"FrozenPointConvPartseg takes networks.seg.pointconv_partseg.PointConvDensity_partseg, got {type(net).__name__}")
-        self.net = net
-        self.precision = precision
-        self._copies = {}
-        self.refresh()
+    ``precision``: "fp32", or "bf16" (``fnet.precision`` tells which) to run every fused level launch as
+    ``pcl_pointconv_seg_level_infer_bf16_f32``: the layers behind the first of the feature MLP (one at two layers, two at three)
+    take bf16 operands (activations rounded to nearest even, weights snapshot as bf16 in ``refresh()``) and accumulate in fp32;
+    ``Uf``, layer 1, the WeightNet, the DensityNet, the epilogues, the last activation, the contraction and its output stay fp32.
+    ``levels`` does not depend on it, and everything but the fused launches -- the 3-NN interpolation, ``Uf``, each level's Linear,
+    the two ``"module"`` levels, the head -- is the same code on the same types."""
 
-    _copy = FrozenPointConv._copy
+    NET = PointConvDensity_partseg
 
     @torch.no_grad()
     def refresh(self):
@@ -1098,7 +1039,7 @@ class FrozenPointConvPartseg:
             if isinstance(level, kinds[1]):
                 D = level.mlp.spec[0] - 3                              # the interpolated features of the level below
             if isinstance(level, kinds) and _pointconv_seg_fusable(level, D):
-                self.plans.append(("fused", _FusedPointConv(level, D, self.precision, entry=POINTCONV_SEG_ENTRIES[self.precision])))
+                self.plans.append(("fused", _FusedPointConv(level, D, self.precision, entry="pcl_pointconv_seg_level_infer_f32")))
             else:
                 self.plans.append(("module", self._copy(name, level)))
             D = level.linear.spec[-1]
@@ -1115,19 +1056,14 @@ class FrozenPointConvPartseg:
     def _head(self, rows):
         """fc1 + bn1 + relu (Dropout = identity), fc3: fc1's BatchNorm + activation ride in fc3's operand load."""
         Y, sc, sh = self.fc1.run(rows)
-        P, K = Y.shape
-        out = torch.empty((P, self.W3.shape[0]), dtype=torch.float32, device=rows.device)
-        _lib.call("pcl_linear_fwd_rows_f32", _p(Y), _p(self.W3), _p(self.b3), _p(sc), _p(sh), self.fc1.out_slope, P, K, out.shape[1], _p(out),
-                  None, None, None, _stream(), tag=f"fwd{K}x{out.shape[1]}")
-        return out
+        return _rows_gemm(Y, self.W3, self.b3, sc, sh, self.fc1.out_slope)
 
     @torch.no_grad()
     def run(self, xyz, cls_label=None, sampling=None, start_idx=None):
         """-> ([output of sa0..sa3, in0..in3: [B, S, C]], logits [B, N, part_num])."""
         if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
             raise ValueError(f"FrozenPointConvPartseg: xyz must be [B,N,3], got {tuple(getattr(xyz, 'shape', ()))}")
-        if not xyz.is_cuda or xyz.dtype != torch.float32:
-            raise TypeError(f"FrozenPointConvPartseg: expected a float32 tensor on the GPU, got {xyz.dtype} on {xyz.device}")
+        self._require_f32_gpu(xyz)
         B, N, _ = xyz.shape
         if sampling is None:
             sampling = self.net.precompute_sampling(xyz, start_idx)

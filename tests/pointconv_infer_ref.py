@@ -159,3 +159,48 @@ def pack_nets(wn, dn, size):
     out = torch.zeros(size)
     out[:flat.numel()] = flat
     return out
+
+
+def is_bf16(t):
+    return torch.equal(t.float().to(torch.bfloat16).double(), t.double())
+
+
+def level_call(dev, feat, nets, xyz, new_xyz, points, idx, density, slope=0.0, *, entry):
+    """``entry`` (a PointConv level entry point, through the C ABI) on stacks of (W, scale, shift) (any dtype / device; the weights
+    behind layer 1 rounded to bf16 for a ``..._bf16_f32`` entry) -> [B, m, 16 * C_L] on the device.  ``Uf``, the weights and ``out``
+    must be 16-byte aligned; 8 guard columns behind every output row must stay as they were."""
+    import ctypes
+
+    from pointcloudlib_amd import _lib
+    from pointcloudlib_amd.misc.ops import _p, _stream
+    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
+    xyz, new_xyz, points, density = f32(xyz), f32(new_xyz), f32(points), f32(density)
+    idx = idx.to(device=dev, dtype=torch.int32).contiguous()
+    B, N, _ = xyz.shape
+    m, ns = idx.shape[1], idx.shape[2]
+    layers = [tuple(f32(t) for t in layer) for layer in feat]
+    W0 = layers[0][0]
+    C1, CL = W0.shape[0], layers[-1][0].shape[0]
+    Uf = None
+    if points is not None:
+        D = points.shape[-1]
+        Uf = torch.empty(B * N, C1, device=dev)
+        Wf = W0[:, 3:].contiguous()
+        _lib.call("pcl_linear_fwd_rows_f32", _p(points.reshape(B * N, D)), _p(Wf), None, None, None, 0.0, B * N, D, C1, _p(Uf), None, None, None,
+                  _stream())
+    L = len(layers)
+    Ws = [l[0].to(torch.bfloat16).contiguous() if entry.endswith("_bf16_f32") else l[0] for l in layers[1:]]
+    assert all(w.data_ptr() % 16 == 0 for w in Ws) and (Uf is None or Uf.data_ptr() % 16 == 0)
+    widths = (ctypes.c_int32 * L)(*[l[0].shape[0] for l in layers])
+    c_W = (ctypes.c_void_p * L)(*[None] + [_p(w) for w in Ws])
+    c_sc = (ctypes.c_void_p * L)(*[_p(l[1]) for l in layers])
+    c_sh = (ctypes.c_void_p * L)(*[_p(l[2]) for l in layers])
+    nets = f32(nets)
+    ldo = 16 * CL + 8
+    out = torch.full((B * m, ldo), 7.0, device=dev)
+    assert out.data_ptr() % 16 == 0
+    _lib.call(entry, _p(xyz), _p(new_xyz), _p(Uf), _p(W0), W0.shape[1], _p(density), _p(idx), B, N, m, ns, L, widths, c_W, c_sc, c_sh,
+              float(slope), _p(nets), 16, _p(out), ldo, _stream())
+    torch.cuda.synchronize()
+    assert bool((out[:, 16 * CL:] == 7.0).all()), "wrote beyond its columns"
+    return out[:, :16 * CL].reshape(B, m, 16 * CL)

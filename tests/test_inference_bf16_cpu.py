@@ -76,6 +76,20 @@ def test_frozen_rejects_other_networks_under_either_precision():
         frozen(PointNet(), precision="bf16")
 
 
+def test_direct_construction_checks_the_type_then_the_precision():
+    """The six evaluators share one constructor: a direct ``FrozenPointNet2(net, "bf17")`` raises what ``frozen()`` raises, and a
+    call wrong in both respects names the network."""
+    from pointcloudlib_amd import inference as I
+    from pointcloudlib_amd.networks.cls.pointnet import PointNet
+    from pointcloudlib_amd.networks.cls.pointnet2 import PointNet2_cls
+    for cls in (I.FrozenPointNet2, I.FrozenPointNet2Partseg, I.FrozenPointNet, I.FrozenPointNetPartseg, I.FrozenPointConv, I.FrozenPointConvPartseg):
+        other = PointNet2_cls() if cls.NET is PointNet else PointNet()
+        with pytest.raises(TypeError, match=f"{cls.__name__} takes networks.*{cls.NET.__name__}, got {type(other).__name__}"):
+            cls(other, "bf17")
+    with pytest.raises(ValueError, match="FrozenPointNet2: precision must be one of .*fp32.*bf16.*got 'bf17'"):
+        I.FrozenPointNet2(PointNet2_cls(), "bf17")
+
+
 def test_bf16_snapshot_and_refresh():
     from pointcloudlib_amd.inference import frozen
     from pointcloudlib_amd.networks.cls.pointnet2 import PointNet2_cls

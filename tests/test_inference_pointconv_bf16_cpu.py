@@ -109,10 +109,6 @@ def test_bf16_snapshot_and_refresh():
 
 
 # ----------------------------------------------------------------------------------------------- the exact data stay exact in bf16
-def _is_bf16(t):
-    return torch.equal(t.float().to(torch.bfloat16).double(), t.double())
-
-
 @pytest.mark.parametrize("shape", [SHAPES[32], SHAPES[64], MANY[32], MANY[64]], ids=["ns32", "ns64", "many32", "many64"])
 def test_exact_cases_are_exact_in_bf16(shape):
     """On the data of the bit-for-bit GPU tests every z1 and z2 of the fp64 restatement and every weight of layers 2 and 3 is a bf16
@@ -120,7 +116,7 @@ def test_exact_cases_are_exact_in_bf16(shape):
     ns, widths, D, B, N, m = shape
     c = R.exact_case(ns, widths, D, B, N, m, EXACT_SEED)
     for W, _, _ in c["feat"][1:]:
-        assert _is_bf16(W)
+        assert R.is_bf16(W)
     worst, inexact, total, audit = 0.0, 0, 0, []
     for b in range(B):                                        # a cloud at a time: the rows of the large cases are many
         bs = slice(b, b + 1)

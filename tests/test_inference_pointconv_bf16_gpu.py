@@ -6,14 +6,13 @@ random data, group by group -- then the network, and the contract of the evaluat
 
 Shapes, seeds and modules are those of tests/test_inference_pointconv_gpu.py (imported, so the cached cases are shared)."""
 import copy
-import ctypes
+import functools
 
 import pytest
 import torch
 
 import pointconv_bf16_bound as PB
 import pointconv_infer_ref as R
-from test_inference_gpu import _P, _stream
 from test_inference_pointconv_gpu import (EXACT_SEED, MANY, SHAPES, _clouds, _frozen_stacks, _module_case, _net, _sampling_from, _start_idx)
 
 pytestmark = pytest.mark.gpu
@@ -22,40 +21,7 @@ BF16 = "pcl_pointconv_level_infer_bf16_f32"
 FP32 = "pcl_pointconv_level_infer_f32"
 
 
-def _level_call(dev, feat, nets, xyz, new_xyz, points, idx, density, slope=0.0, entry=BF16):
-    """``entry`` on stacks of (W, scale, shift) (any dtype / device; W[1], W[2] rounded to bf16 for the bf16 entry)
-    -> [B, m, 16 * C3] on the device."""
-    from pointcloudlib_amd import _lib
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
-    xyz, new_xyz, points, density = f32(xyz), f32(new_xyz), f32(points), f32(density)
-    idx = idx.to(device=dev, dtype=torch.int32).contiguous()
-    B, N, _ = xyz.shape
-    m, ns = idx.shape[1], idx.shape[2]
-    layers = [tuple(f32(t) for t in layer) for layer in feat]
-    W0 = layers[0][0]
-    C1, C3 = W0.shape[0], layers[-1][0].shape[0]
-    Uf = None
-    if points is not None:
-        D = points.shape[-1]
-        Uf = torch.empty(B * N, C1, device=dev)
-        Wf = W0[:, 3:].contiguous()
-        _lib.call("pcl_linear_fwd_rows_f32", _P(points.reshape(B * N, D)), _P(Wf), None, None, None, 0.0, B * N, D, C1, _P(Uf), None, None, None,
-                  _stream())
-    L = len(layers)
-    Ws = [l[0].to(torch.bfloat16).contiguous() if entry == BF16 else l[0] for l in layers[1:]]
-    assert all(w.data_ptr() % 16 == 0 for w in Ws)
-    widths = (ctypes.c_int32 * L)(*[l[0].shape[0] for l in layers])
-    c_W = (ctypes.c_void_p * L)(*[None] + [_P(w) for w in Ws])
-    c_sc = (ctypes.c_void_p * L)(*[_P(l[1]) for l in layers])
-    c_sh = (ctypes.c_void_p * L)(*[_P(l[2]) for l in layers])
-    nets = f32(nets)
-    ldo = 16 * C3 + 8
-    out = torch.full((B * m, ldo), 7.0, device=dev)
-    _lib.call(entry, _P(xyz), _P(new_xyz), _P(Uf), _P(W0), W0.shape[1], _P(density), _P(idx), B, N, m, ns, L, widths, c_W, c_sc, c_sh,
-              float(slope), _P(nets), 16, _P(out), ldo, _stream())
-    torch.cuda.synchronize()
-    assert bool((out[:, 16 * C3:] == 7.0).all()), "wrote beyond its columns"
-    return out[:, :16 * C3].reshape(B, m, 16 * C3)
+_level_call = functools.partial(R.level_call, entry=BF16)
 
 
 # ------------------------------------------------------------------------------------------------- 1. exactly representable data

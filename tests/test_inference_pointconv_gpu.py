@@ -10,14 +10,13 @@ eval-mode ``PointwiseMLP`` copies + ``pointconv_contract``; of a network, ``net.
 ``_perturb`` makes a fifth of the BatchNorm gammas negative; a DensityNet's single output channel behind a negative gamma is zero
 for every point and erases its level, so ``_alive`` gives that one channel a positive gamma and beta after the perturbation."""
 import copy
-import ctypes
 import functools
 
 import pytest
 import torch
 
 import pointconv_infer_ref as R
-from test_inference_gpu import _P, _err, _perturb, _stream
+from test_inference_gpu import _err, _perturb
 
 pytestmark = pytest.mark.gpu
 
@@ -37,37 +36,7 @@ def _alive(root):
     return root
 
 
-def _level_call(dev, feat, nets, xyz, new_xyz, points, idx, density, slope=0.0):
-    """pcl_pointconv_level_infer_f32 on stacks of (W, scale, shift) (any dtype / device) -> [B, m, 16 * C3] on the device."""
-    from pointcloudlib_amd import _lib
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
-    xyz, new_xyz, points, density = f32(xyz), f32(new_xyz), f32(points), f32(density)
-    idx = idx.to(device=dev, dtype=torch.int32).contiguous()
-    B, N, _ = xyz.shape
-    m, ns = idx.shape[1], idx.shape[2]
-    layers = [tuple(f32(t) for t in layer) for layer in feat]
-    W0 = layers[0][0]
-    C1, C3 = W0.shape[0], layers[-1][0].shape[0]
-    Uf = None
-    if points is not None:
-        D = points.shape[-1]
-        Uf = torch.empty(B * N, C1, device=dev)
-        Wf = W0[:, 3:].contiguous()
-        _lib.call("pcl_linear_fwd_rows_f32", _P(points.reshape(B * N, D)), _P(Wf), None, None, None, 0.0, B * N, D, C1, _P(Uf), None, None, None,
-                  _stream())
-    L = len(layers)
-    widths = (ctypes.c_int32 * L)(*[l[0].shape[0] for l in layers])
-    c_W = (ctypes.c_void_p * L)(*[None] + [_P(l[0]) for l in layers[1:]])
-    c_sc = (ctypes.c_void_p * L)(*[_P(l[1]) for l in layers])
-    c_sh = (ctypes.c_void_p * L)(*[_P(l[2]) for l in layers])
-    nets = f32(nets)
-    ldo = 16 * C3 + 8
-    out = torch.full((B * m, ldo), 7.0, device=dev)
-    _lib.call("pcl_pointconv_level_infer_f32", _P(xyz), _P(new_xyz), _P(Uf), _P(W0), W0.shape[1], _P(density), _P(idx), B, N, m, ns, L, widths,
-              c_W, c_sc, c_sh, float(slope), _P(nets), 16, _P(out), ldo, _stream())
-    torch.cuda.synchronize()
-    assert bool((out[:, 16 * C3:] == 7.0).all()), "wrote beyond its columns"
-    return out[:, :16 * C3].reshape(B, m, 16 * C3)
+_level_call = functools.partial(R.level_call, entry="pcl_pointconv_level_infer_f32")
 
 
 # ------------------------------------------------------------------------------------------------- 1. against fp64

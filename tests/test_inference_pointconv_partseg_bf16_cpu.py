@@ -119,10 +119,6 @@ def test_bf16_snapshot_and_refresh():
 
 
 # ----------------------------------------------------------------------------------------------- the exact data stay exact in bf16
-def _is_bf16(t):
-    return torch.equal(t.float().to(torch.bfloat16).double(), t.double())
-
-
 @pytest.mark.parametrize("name,ns,widths,D,B,N,m", EXACT, ids=[e[0] for e in EXACT])
 def test_exact_cases_are_exact_in_bf16(name, ns, widths, D, B, N, m):
     """On the data of the bit-for-bit GPU tests every activation that the contract rounds (z1; at three layers z2 too) and every
@@ -130,7 +126,7 @@ def test_exact_cases_are_exact_in_bf16(name, ns, widths, D, B, N, m):
     bit for bit."""
     c = R.exact_case(ns, widths, D, B, N, m, EXACT_SEED)
     for W, _, _ in c["feat"][1:]:
-        assert _is_bf16(W)
+        assert R.is_bf16(W)
     worst, inexact, total, audit = 0.0, 0, 0, []
     for b in range(B):                                        # a cloud at a time: the rows of the large cases are many
         bs = slice(b, b + 1)

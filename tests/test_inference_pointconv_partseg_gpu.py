@@ -7,7 +7,6 @@ Yardstick (tests/test_inference_gpu.py): the fused path may be no further from t
 same inputs (max |difference|), x 1.25, plus 1e-6.  The existing path of the level kernel is the composite ``index_points`` +
 eval-mode ``PointwiseMLP`` copies + ``pointconv_contract``; of the network, ``net.eval()`` under ``no_grad``."""
 import copy
-import ctypes
 import functools
 
 import pytest
@@ -16,7 +15,7 @@ import torch
 import pointconv_infer_ref as R
 import pointconv_partseg_infer_ref as RS
 from pointconv_partseg_infer_ref import EXACT_SEED, MANY, SHAPES
-from test_inference_gpu import _P, _err, _perturb, _stream
+from test_inference_gpu import _err, _perturb
 from test_inference_pointconv_gpu import _alive, _composite, _frozen_stacks
 from test_inference_pointconv_gpu import _level_call as _cls_level_call
 
@@ -26,38 +25,7 @@ NEW = sorted(SHAPES)
 STOCK = ["fused", "fused", "fused", "module", "module", "fused", "fused", "fused"]
 
 
-def _level_call(dev, feat, nets, xyz, new_xyz, points, idx, density, slope=0.0, entry="pcl_pointconv_seg_level_infer_f32"):
-    """The entry point on stacks of (W, scale, shift) (any dtype / device) -> [B, m, 16 * C_L] on the device; 8 guard columns behind
-    every output row must stay as they were."""
-    from pointcloudlib_amd import _lib
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
-    xyz, new_xyz, points, density = f32(xyz), f32(new_xyz), f32(points), f32(density)
-    idx = idx.to(device=dev, dtype=torch.int32).contiguous()
-    B, N, _ = xyz.shape
-    m, ns = idx.shape[1], idx.shape[2]
-    layers = [tuple(f32(t) for t in layer) for layer in feat]
-    W0 = layers[0][0]
-    C1, CL = W0.shape[0], layers[-1][0].shape[0]
-    Uf = None
-    if points is not None:
-        D = points.shape[-1]
-        Uf = torch.empty(B * N, C1, device=dev)
-        Wf = W0[:, 3:].contiguous()
-        _lib.call("pcl_linear_fwd_rows_f32", _P(points.reshape(B * N, D)), _P(Wf), None, None, None, 0.0, B * N, D, C1, _P(Uf), None, None, None,
-                  _stream())
-    L = len(layers)
-    widths = (ctypes.c_int32 * L)(*[l[0].shape[0] for l in layers])
-    c_W = (ctypes.c_void_p * L)(*[None] + [_P(l[0]) for l in layers[1:]])
-    c_sc = (ctypes.c_void_p * L)(*[_P(l[1]) for l in layers])
-    c_sh = (ctypes.c_void_p * L)(*[_P(l[2]) for l in layers])
-    nets = f32(nets)
-    ldo = 16 * CL + 8
-    out = torch.full((B * m, ldo), 7.0, device=dev)
-    _lib.call(entry, _P(xyz), _P(new_xyz), _P(Uf), _P(W0), W0.shape[1], _P(density), _P(idx), B, N, m, ns, L, widths, c_W, c_sc, c_sh,
-              float(slope), _P(nets), 16, _P(out), ldo, _stream())
-    torch.cuda.synchronize()
-    assert bool((out[:, 16 * CL:] == 7.0).all()), "wrote beyond its columns"
-    return out[:, :16 * CL].reshape(B, m, 16 * CL)
+_level_call = functools.partial(R.level_call, entry="pcl_pointconv_seg_level_infer_f32")
 
 
 def _case_args(c):

@@ -9,33 +9,14 @@ import numpy as np
 import pytest
 import torch
 
+from test_inference_gpu import _perturb
+
 pytestmark = pytest.mark.gpu
 
 TIE = 4
 FILLS = ("copies", "nan", "huge")
 CLS_N, CLS_LENGTHS = 1024, [1024, 1000, 777, 640, 513, 512]          # N, n_samples + 1, n_samples, not multiples of 64
 SEG_N, SEG_LENGTHS = 2048, [2048, 512, 513, 2011, 1281, 1500]        # (cloud 1: 24 of its 32 FP1 tiles hold pad rows only)
-
-
-def _perturb(net, seed):
-    """Running statistics, gamma and beta of every BatchNorm away from their initial values (some gamma < 0)."""
-    from pointcloudlib_amd.misc.layers import PointwiseMLP
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for mod in net.modules():
-            pairs = []
-            if isinstance(mod, PointwiseMLP) and mod.bn:
-                pairs = [(mod.gammas[l], mod.betas[l], getattr(mod, f"running_mean_{l}"), getattr(mod, f"running_var_{l}")) for l in range(mod.n_layers)]
-            elif isinstance(mod, torch.nn.BatchNorm1d):
-                pairs = [(mod.weight, mod.bias, mod.running_mean, mod.running_var)]
-            for gam, bet, rm, rv in pairs:
-                c = gam.numel()
-                sign = torch.where(torch.rand(c, generator=g) < 0.2, -1.0, 1.0)
-                gam.copy_(sign * (0.5 + torch.rand(c, generator=g)))
-                bet.copy_(0.1 * torch.randn(c, generator=g))
-                rm.copy_(0.1 * torch.randn(c, generator=g))
-                rv.copy_(0.5 + 1.5 * torch.rand(c, generator=g))
-    return net
 
 
 def _net(task, kind, dev, seed=0):
