@@ -890,7 +890,7 @@ int pcl_pointconv_level_infer_f32(const float* xyz, const float* new_xyz, const 
  * In the queries C1 = widths[0], C2 = widths[1] and C3 = widths[L-1] (so C2 = C3 at L = 2).  Kernels exist, with M = 16, for
  *     ns = 32, L = 3: 32/32/64, 64/64/128, 128/128/256        ns = 64, L = 3: 128/128/256
  *     ns = 16, L = 2: 256/256, 128/128                        ns = 16, L = 3: 128/128/128
- * and for nothing else (256/256/512 at ns = 32 and 512/512 at ns = 16 do not fit the tile's LDS); any other shape returns
+ * and for nothing else (256/256/512 at ns = 32 and 512/512 at ns = 16 do not fit the tile's LDS: pcl_pointconv_wide_level_infer_f32, below); any other shape returns
  * PCL_EINVAL ("no kernel") before any launch.  (32, 64/64/128) and (64, 128/128/256) launch the very kernels of
  * pcl_pointconv_level_infer_f32.  pcl_pointconv_seg_level_infer_group_tile: as pcl_pointconv_level_infer_group_tile, for ns in
  * {16, 32, 64} (a multiple of 64 / ns, at most 8 tiles).  Both queries answer for both precisions: every shape has its fp32 and its
@@ -933,6 +933,26 @@ int pcl_pointconv_seg_level_infer_bf16_f32(const float* xyz, const float* new_xy
                                            const int32_t* widths, const void* const* W, const float* const* scale,
                                            const float* const* shift, float slope, const float* nets, int M, float* out, int ldo,
                                            void* stream);
+/* No reference counterpart: the same launch for the two 512-wide levels of networks/seg/pointconv_partseg.py, which the tile of
+ * pcl_pointconv_seg_level_infer_f32 cannot hold (FrozenPointConvPartseg(net, wide_levels=True)); fp32 only.  Arguments, host checks
+ * (all before any HIP call), preconditions (Uf, W_l with l >= 1 and out 16-byte aligned; idx in [0, N), clamped) and the numeric
+ * contract of pcl_pointconv_seg_level_infer_f32, expression by expression: the last layer and the contraction run over the output
+ * columns in chunks (128 or 64 of them), each column the same k chain and each output the same s chain as there, so no result
+ * depends on the chunking; a group's result depends only on its own rows (not on B, on the group's place in the launch or on how
+ * many groups a workgroup owns); no atomics, two calls give identical bits; all 16 * widths[L-1] outputs of every group are
+ * written and none beyond them.  One workgroup per compute unit on up to 160 KiB of LDS.  Kernels exist, with M = 16, for
+ *     ns = 32, L = 3: 256/256/512                             ns = 16, L = 2: 512/512
+ * (queries as above: C2 = widths[1], C3 = widths[L-1]) and for nothing else, the shapes of pcl_pointconv_seg_level_infer_f32
+ * included; any other shape returns PCL_EINVAL ("no kernel", naming pcl_pointconv_wide_level_infer_supported) before any launch.
+ * pcl_pointconv_wide_level_infer_group_tile: as pcl_pointconv_seg_level_infer_group_tile, for ns in {16, 32} (a multiple of
+ * 64 / ns, at most 8 tiles; sized for one workgroup per compute unit); 0 for another ns or G < 1. */
+int pcl_pointconv_wide_level_infer_supported(int ns, int L, int C1, int C2, int C3, int M);
+int pcl_pointconv_wide_level_infer_group_tile(int ns, int G);
+int pcl_pointconv_wide_level_infer_f32(const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
+                                       const float* density, const int32_t* idx, int B, int N, int m, int ns, int L,
+                                       const int32_t* widths, const float* const* W, const float* const* scale,
+                                       const float* const* shift, float slope, const float* nets, int M, float* out, int ldo,
+                                       void* stream);
 
 /* ---- Frozen inference: one PointNet++ feature-propagation level in evaluation mode as ONE launch ------------------------
  * misc/ops.py:54-107 (PointNetFeaturePropagation.execute: 3-NN inverse-distance interpolation, concat with the skip features,

@@ -286,6 +286,31 @@ __global__ __launch_bounds__(NT, 2) void pointconv_level_infer_kernel(const Poin
     }
 }
 
+// What every entry point of this argument list checks behind its own shape table, all before any HIP call, and the argument struct
+// (GT is the launch's to set).  W3 / sc3 / sh3 are the last layer's whatever L is; W2 / sc2 / sh2 the middle layer's of L = 3.
+// Uf, W[1], W[2] and out are moved in 16-byte pieces: their alignment is the caller's precondition (include/pcl_hip.h), held by
+// pointcloudlib_amd/inference.py before the call; there is no other path to choose here.
+inline int pointconv_args(const char* fn, const float* xyz, const float* new_xyz, const float* Uf, const float* Wx, int ldw,
+                          const float* density, const int32_t* idx, int B, int N, int m, int L, const int32_t* widths,
+                          const void* const* W, const float* const* scale, const float* const* shift, float slope, const float* nets,
+                          int M, float* out, int ldo, PointConvArgs& a) {
+    const int C3 = widths[L - 1];
+    PCL_REQUIRE(xyz && new_xyz && Wx && density && idx && nets && out, "%s: null pointer", fn);
+    PCL_REQUIRE(ldw >= 3, "%s: ldw=%d", fn, ldw);
+    PCL_REQUIRE(B >= 1 && N >= 1 && m >= 1, "%s: bad sizes B=%d N=%d m=%d", fn, B, N, m);
+    PCL_REQUIRE((size_t)B * m < (1u << 31) && (size_t)B * N < (1u << 31), "%s: too many groups / points", fn);
+    for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", fn, l);
+    PCL_REQUIRE(ldo >= C3 * M && ldo % 4 == 0, "%s: ldo=%d for %d columns (a multiple of 4)", fn, ldo, C3 * M);
+    a = {};
+    a.xyz = xyz; a.new_xyz = new_xyz; a.Uf = Uf; a.Wx = Wx; a.ldw = ldw; a.density = density; a.idx = idx;
+    a.G = B * m; a.N = N; a.m = m;
+    if (L == 3) { a.W2 = static_cast<const float*>(W[1]); a.sc2 = scale[1]; a.sh2 = shift[1]; }
+    a.W3 = static_cast<const float*>(W[L - 1]);
+    a.sc1 = scale[0]; a.sh1 = shift[0]; a.sc3 = scale[L - 1]; a.sh3 = shift[L - 1];
+    a.slope = slope; a.nets = nets; a.out = out; a.ldo = ldo;
+    return PCL_OK;
+}
+
 // groups per workgroup of a launch over G groups (infer_pointconv.hip): the same for every instantiation and both precisions
 int pointconv_group_tile(int ns, int G);
 // the five bf16 kernels of the part-seg shapes, by the shape id of infer_pointconv.hip (2 .. 6): infer_pointconv_seg_bf16.hip

@@ -1,7 +1,8 @@
 // infer_pointconv.hip -- the entry points of the fused k-NN PointConv level (infer_pointconv.h has the kernel and its description):
 // the shape tables, the host checks and the launches.  This file instantiates the seven fp32 kernels and the two bf16 kernels of
 // pcl_pointconv_level_infer_bf16_f32; the five bf16 kernels of the part-seg shapes are instantiated in infer_pointconv_seg_bf16.hip
-// (its header says why they are not instantiated here).
+// (its header says why they are not instantiated here).  The two 512-wide levels of the part-seg network have another kernel and
+// entry points of their own: infer_pointconv_wide.hip.
 #include "infer_pointconv.h"
 
 namespace pcl {
@@ -32,8 +33,9 @@ int pointconv_shape_id(int ns, int L, int C1, int C2, int C3, int M) {
 
 // every instantiation (pcl_pointconv_seg_level_infer_f32 and, with bf16 tiles, pcl_pointconv_seg_level_infer_bf16_f32): the two
 // above keep their ids, then the levels of networks/seg/pointconv_partseg.py that fit the tile -- sa0, sa2 at ns = 32; in1, in2
-// (two layers: C2 = C3 = widths[1]) and in3 at ns = 16.  sa3 (256/256/512) and in0 (512/512) need about 133 KB of LDS (Z is fp32
-// under either element type) and have no kernel.
+// (two layers: C2 = C3 = widths[1]) and in3 at ns = 16.  sa3 (256/256/512) and in0 (512/512) need about 133 KB of LDS in this form
+// (Z is fp32 under either element type) and are not in this table: their kernel is infer_pointconv_wide.hip's, which holds Z a
+// column chunk at a time (pcl_pointconv_wide_level_infer_f32, a table of its own).
 int pointconv_seg_shape_id(int ns, int L, int C1, int C2, int C3, int M) {
     const int sid = pointconv_shape_id(ns, L, C1, C2, C3, M);
     if (sid >= 0 || M != PC_M) return sid;
@@ -59,23 +61,9 @@ int pointconv_level_infer(const char* fn, const float* xyz, const float* new_xyz
     else if (L == 3) sid = pointconv_shape_id(ns, L, widths[0], widths[1], widths[2], M);
     PCL_REQUIRE(sid >= 0, "%s: no kernel for ns=%d L=%d widths %d/%d/%d M=%d (%s)", fn, ns, L, widths[0], L > 1 ? widths[1] : 0,
                 L > 2 ? widths[2] : 0, M, SEG ? "pcl_pointconv_seg_level_infer_supported" : "pcl_pointconv_level_infer_supported");
-    const int C3 = widths[L - 1];
-    PCL_REQUIRE(xyz && new_xyz && Wx && density && idx && nets && out, "%s: null pointer", fn);
-    PCL_REQUIRE(ldw >= 3, "%s: ldw=%d", fn, ldw);
-    PCL_REQUIRE(B >= 1 && N >= 1 && m >= 1, "%s: bad sizes B=%d N=%d m=%d", fn, B, N, m);
-    PCL_REQUIRE((size_t)B * m < (1u << 31) && (size_t)B * N < (1u << 31), "%s: too many groups / points", fn);
-    for (int l = 0; l < L; ++l) PCL_REQUIRE(scale[l] && shift[l] && (l == 0 || W[l]), "%s: layer %d: null pointer", fn, l);
-    PCL_REQUIRE(ldo >= C3 * M && ldo % 4 == 0, "%s: ldo=%d for %d columns (a multiple of 4)", fn, ldo, C3 * M);
-    // Uf, W[1], W[2] and out are moved in 16-byte pieces: their alignment is the caller's precondition (include/pcl_hip.h), held by
-    // pointcloudlib_amd/inference.py before the call; there is no other path to choose here
-    PointConvArgs a = {};
-    a.xyz = xyz; a.new_xyz = new_xyz; a.Uf = Uf; a.Wx = Wx; a.ldw = ldw; a.density = density; a.idx = idx;
-    a.G = B * m; a.N = N; a.m = m;
-    // W3 / sc3 / sh3 are the last layer's whatever L is; W2 / sc2 / sh2 the middle layer's of L = 3
-    if (L == 3) { a.W2 = static_cast<const float*>(W[1]); a.sc2 = scale[1]; a.sh2 = shift[1]; }
-    a.W3 = static_cast<const float*>(W[L - 1]);
-    a.sc1 = scale[0]; a.sh1 = shift[0]; a.sc3 = scale[L - 1]; a.sh3 = shift[L - 1];
-    a.slope = slope; a.nets = nets; a.out = out; a.ldo = ldo;
+    PointConvArgs a;
+    if (int rc = pointconv_args(fn, xyz, new_xyz, Uf, Wx, ldw, density, idx, B, N, m, L, widths, W, scale, shift, slope, nets, M, out, ldo, a))
+        return rc;
     hipStream_t st = as_stream(stream);
     if (sid == 0) return launch_pointconv<32, 3, 64, 64, 128, BF16>(fn, a, st);
     if (sid == 1) return launch_pointconv<64, 3, 128, 128, 256, BF16>(fn, a, st);

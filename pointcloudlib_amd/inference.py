@@ -11,7 +11,7 @@
 - ``FrozenPointConv``: ``networks.cls.pointconv.PointConvDensityClsSsg``; csrc/infer_pointconv.hip; DESIGN.md sections 24 and 25
   (bf16).
 - ``FrozenPointConvPartseg``: ``networks.seg.pointconv_partseg.PointConvDensity_partseg``; csrc/infer_pointconv.hip and
-  csrc/infer_pointconv_seg_bf16.hip; DESIGN.md sections 26 and 27 (bf16).
+  csrc/infer_pointconv_seg_bf16.hip, csrc/infer_pointconv_wide.hip; DESIGN.md sections 26, 27 (bf16) and 28 (``wide_levels``).
 
 All but the two PointNet++ evaluators are constructed directly: ``frozen()`` keeps its PointNet++ dispatch."""
 import copy
@@ -991,15 +991,16 @@ class FrozenPointConv(_Frozen):
 
 
 # ---------------------------------------------------------------------------------------------- PointConv part segmentation
-def _pointconv_seg_fusable(level, D):
+def _pointconv_seg_fusable(level, D, query="pcl_pointconv_seg_level_infer_supported"):
     """A k-NN level (set abstraction or interpolation) of the usual small nets whose shape ``pcl_pointconv_seg_level_infer_f32``
-    has a kernel for.  In the query C2 = widths[1] and C3 = widths[L-1] (include/pcl_hip.h)."""
+    has a kernel for (or, by its ``query``, ``pcl_pointconv_wide_level_infer_f32``).  In the query C2 = widths[1] and C3 =
+    widths[L-1] (include/pcl_hip.h)."""
     mlp = level.mlp
     if getattr(level, "group_all", False) or not (mlp.n_layers in (2, 3) and mlp.bn and mlp.last_act and mlp.spec[0] == 3 + D
                                                    and _small_nets_ok(level)):
         return False
     w = [int(c) for c in mlp.spec[1:]]
-    return bool(_lib.size_query("pcl_pointconv_seg_level_infer_supported", int(level.nsample), len(w), w[0], w[1], w[-1], POINTCONV_M))
+    return bool(_lib.size_query(query, int(level.nsample), len(w), w[0], w[1], w[-1], POINTCONV_M))
 
 
 class FrozenPointConvPartseg(_Frozen):
@@ -1016,7 +1017,7 @@ class FrozenPointConvPartseg(_Frozen):
     interpolation level first runs the 3-NN interpolation and ``Uf = interpolated W0[:, 3:]^T`` over its N points, then that launch
     over N groups of 16 (the centres are the level's own points in FPS visiting order, as upstream), so no ``[B,N,16,C]`` tensor
     exists.  ``"module"`` otherwise -- an eval-mode copy of the level's own module runs on the same sampling entry: the two 512-wide
-    levels (``sa3``, ``in0``) have no kernel.  The head runs the stats-free GEMMs on the ``B N`` rows.  ``refresh()`` re-reads
+    levels (``sa3``, ``in0``) have no kernel in that table (``wide_levels``, below).  The head runs the stats-free GEMMs on the ``B N`` rows.  ``refresh()`` re-reads
     weights and running statistics; ``net`` itself is never modified (parameters, buffers, ``training`` flags).
 
     ``precision``: "fp32", or "bf16" (``fnet.precision`` tells which) to run every fused level launch as
@@ -1024,9 +1025,27 @@ class FrozenPointConvPartseg(_Frozen):
     take bf16 operands (activations rounded to nearest even, weights snapshot as bf16 in ``refresh()``) and accumulate in fp32;
     ``Uf``, layer 1, the WeightNet, the DensityNet, the epilogues, the last activation, the contraction and its output stay fp32.
     ``levels`` does not depend on it, and everything but the fused launches -- the 3-NN interpolation, ``Uf``, each level's Linear,
-    the two ``"module"`` levels, the head -- is the same code on the same types."""
+    the two ``"module"`` levels, the head -- is the same code on the same types.
+
+    ``wide_levels``: False, or True (``fnet.wide_levels`` tells which) to run a level that the table above
+    rejects and ``pcl_pointconv_wide_level_infer_supported`` accepts -- ``sa3`` (32 neighbours, 256/256/512) and ``in0`` (16
+    neighbours, 512/512) of the stock network -- as ``"fused"`` too: ``Uf``, ONE ``pcl_pointconv_wide_level_infer_f32`` launch (the
+    same values, the last layer and the contraction a chunk of columns at a time, one workgroup per compute unit), then its Linear,
+    exactly as the six others; ``in0`` runs the 3-NN interpolation first.  The stock network is then ``["fused"] * 8`` and a forward
+    forms no BatchNorm constants and no ``[B,S,ns,C]`` tensor.  The wide kernel is fp32 only: under ``precision="bf16"`` those
+    levels run the fp32 wide kernel, so ``levels`` does not depend on the precision here either.  With False (the default) plans,
+    launches and bits are what they were.  What it saves is the two module copies' small launches and grouped tensors; each
+    level's 8192 -> 512 Linear is untouched and is the larger part of what those two levels still cost (DESIGN.md section 28 has
+    the measured times)."""
 
     NET = PointConvDensity_partseg
+    WIDE_ENTRY = "pcl_pointconv_wide_level_infer_f32"
+
+    def __init__(self, net, precision="fp32", wide_levels=False):
+        if not isinstance(wide_levels, bool):
+            raise ValueError(f"FrozenPointConvPartseg: wide_levels must be a bool, got {wide_levels!r}")
+        self.wide_levels = wide_levels
+        super().__init__(net, precision)
 
     @torch.no_grad()
     def refresh(self):
@@ -1040,6 +1059,8 @@ class FrozenPointConvPartseg(_Frozen):
                 D = level.mlp.spec[0] - 3                              # the interpolated features of the level below
             if isinstance(level, kinds) and _pointconv_seg_fusable(level, D):
                 self.plans.append(("fused", _FusedPointConv(level, D, self.precision, entry="pcl_pointconv_seg_level_infer_f32")))
+            elif self.wide_levels and isinstance(level, kinds) and _pointconv_seg_fusable(level, D, "pcl_pointconv_wide_level_infer_supported"):
+                self.plans.append(("fused", _FusedPointConv(level, D, "fp32", entry=self.WIDE_ENTRY)))   # fp32 under either precision
             else:
                 self.plans.append(("module", self._copy(name, level)))
             D = level.linear.spec[-1]

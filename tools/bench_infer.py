@@ -51,6 +51,15 @@ per-point top-1 agreement of the two precisions, recorded and not asserted), ``l
 ``pcl_pointconv_seg_level_infer_bf16_f32`` launches) and ``frozen_level_ms_bf16`` with the shares of the two ``"module"`` levels and
 of in3's Linear in the bf16 forward; the line goes to profiles/infer_pointconv_partseg_bf16_bench_line.json instead.
 ``--frozen_only --precision bf16`` runs the bf16 form alone (for a kernel trace) and writes no file.
+``--nets pointconv_partseg --wide`` adds ``FrozenPointConvPartseg(net, wide_levels=True)`` as one more interleaved form on the same
+tensor and the same sampling handle (``frozen_wide_ms`` with its window minimum and maximum and its peak memory,
+``wide_below_frozen_min``: the wide form's median against the default frozen form's window minimum, the max-abs logit distance of
+the two), ``level_kernel_ms_wide`` (the per-call times and TF/s of the two ``pcl_pointconv_wide_level_infer_f32`` launches) and
+``frozen_level_ms_wide`` (device events around each level and the head, and inside sa3, in0 and in3 around the launch with its ``Uf``
+GEMM and around the level's Linear -- ``sa3_linear`` and ``in0_linear`` are the 8192 -> 512 Linears on B 36 and B 64 rows), with the
+share of sa3 + in0 and of their two Linears; with ``--precision fp32 bf16`` the same for the bf16 forms (``frozen_bf16_wide_ms``,
+``wide_below_frozen_min_bf16``, ``frozen_level_ms_bf16_wide``).  The line goes to
+profiles/infer_pointconv_partseg_wide_bench_line.json.
 
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
@@ -135,9 +144,10 @@ def _pointconv_level_times(fwd, entry="pcl_pointconv_level_infer_f32", repeats=5
     return out
 
 
-def _partseg_level_times(fpcs, fwd, repeats=5):
-    """Device events around every level, the head, and in3's two halves (the launch that writes the contraction output, the
-    Linear that reads it) of FrozenPointConvPartseg forwards: average ms over ``repeats`` (the events' dispatch gaps are inside)."""
+def _partseg_level_times(fpcs, fwd, repeats=5, split=(7,)):
+    """Device events around every level, the head, and the two halves of the fused levels ``split`` (by default in3's: the launch
+    that writes the contraction output, the Linear that reads it; keys ``<level>_contract``, ``<level>_linear``) of
+    FrozenPointConvPartseg forwards: average ms over ``repeats`` (the events' dispatch gaps are inside)."""
     marks = []
 
     def timed(fn, key):
@@ -151,12 +161,14 @@ def _partseg_level_times(fpcs, fwd, repeats=5):
         return wrapper
 
     names = list(fpcs.net.LEVELS)
-    in3 = fpcs.plans[7][1] if fpcs.levels[7] == "fused" else None
     saved = [(fpcs, "_level", fpcs._level), (fpcs, "_head", fpcs._head)]
     fpcs._level, fpcs._head = timed(fpcs._level, lambda i, *r: names[i]), timed(fpcs._head, lambda *r: "head")
-    if in3 is not None:
-        saved += [(in3, "contract", in3.contract), (in3.linear, "run", in3.linear.run)]
-        in3.contract, in3.linear.run = timed(in3.contract, lambda *r: "in3_contract"), timed(in3.linear.run, lambda *r: "in3_linear")
+    for i in split:
+        if fpcs.levels[i] == "fused":
+            plan = fpcs.plans[i][1]
+            saved += [(plan, "contract", plan.contract), (plan.linear, "run", plan.linear.run)]
+            plan.contract = timed(plan.contract, lambda *r, n=names[i]: f"{n}_contract")
+            plan.linear.run = timed(plan.linear.run, lambda *r, n=names[i]: f"{n}_linear")
     try:
         for _ in range(repeats):
             fwd()
@@ -224,6 +236,7 @@ def main():
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
     ap.add_argument("--precision", nargs="+", default=["fp32"], choices=["fp32", "bf16"],
                     help="fp32 bf16: frozen(net, precision='bf16') as one more form of every row")
+    ap.add_argument("--wide", action="store_true", help="pointconv_partseg: FrozenPointConvPartseg(net, wide_levels=True) as one more form")
     ap.add_argument("--ragged", action="store_true", help="ragged batches: dense / ragged at full length / ragged / per-cloud loop")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -237,6 +250,8 @@ def main():
     pn_partseg_only = all(k == "pointnet_partseg" for k in a.nets)
     pointconv_only = all(k == "pointconv" for k in a.nets)
     pc_partseg_only = all(k == "pointconv_partseg" for k in a.nets)
+    if a.wide and (not pc_partseg_only or a.ragged or a.frozen_only):
+        raise SystemExit("bench_infer.py: --wide goes with --nets pointconv_partseg alone, without --ragged or --frozen_only")
     if a.ragged and ("pointconv" in a.nets or "pointconv_partseg" in a.nets):
         raise SystemExit("bench_infer.py: PointConv's sampling has no ragged form")
     res = {"N": (a.points or 1024) if cls_only else (a.points or 2048), "windows": a.windows, "iters": a.iters, "cases": []}
@@ -288,6 +303,8 @@ def main():
         elif pc_seg:
             fpcs = FrozenPointConvPartseg(net)
             fnet_bf16 = fpcs16 = FrozenPointConvPartseg(net, precision="bf16") if "bf16" in a.precision else None
+            fpcs_w = FrozenPointConvPartseg(net, wide_levels=True) if a.wide else None
+            fpcs16_w = FrozenPointConvPartseg(net, precision="bf16", wide_levels=True) if a.wide and "bf16" in a.precision else None
         elif pn_seg:
             fps = FrozenPointNetPartseg(net)
 
@@ -385,6 +402,13 @@ def main():
                 forms = [("eval", eval_fwd), ("frozen", frozen_fwd)]
             if fnet_bf16 is not None:
                 forms.append(("frozen_bf16", frozen_bf16_fwd))
+            wide_forms = []                                   # (suffix of the result keys, default form, wide form)
+            if a.wide and "fp32" in a.precision:
+                wide_forms.append(("", "frozen", fpcs_w))
+            if a.wide and fpcs16_w is not None:
+                wide_forms.append(("_bf16", "frozen_bf16", fpcs16_w))
+            for _, base, form in wide_forms:
+                forms.append((f"{base}_wide", lambda form=form: form(xyz, sampling=samp)))
             for _ in range(a.warmup):
                 for _, fn in forms:
                     fn()
@@ -443,9 +467,24 @@ def main():
                 case["module_levels_share_bf16"] = round(sum(lt[n] for n, k in zip(net.LEVELS, fpcs16.levels) if k == "module") / total, 4)
                 if "in3_linear" in lt:
                     case["in3_linear_share_bf16"] = round(lt["in3_linear"] / total, 4)
+            for sfx, base, form in wide_forms:
+                fwd = dict(forms)[f"{base}_wide"]
+                case[f"wide_below_frozen_min{sfx}"] = case[f"{base}_wide_ms"] < case[f"{base}_ms_min"]
+                case[f"wide_vs_frozen{sfx}"] = round(case[f"{base}_wide_ms"] / case[f"{base}_ms"], 4)
+                case[f"max_abs_logit_diff_wide{sfx}"] = float((dict(forms)[base]() - fwd()).abs().max())
+                case[f"levels{sfx}_wide"] = form.levels
+                case[f"level_kernel_ms{sfx}_wide"] = _pointconv_level_times(fwd, "pcl_pointconv_wide_level_infer_f32")
+                lt = case[f"frozen_level_ms{sfx}_wide"] = _partseg_level_times(form, fwd, split=(3, 4, 7))
+                total = sum(v for k, v in lt.items() if "_" not in k)
+                case[f"wide_levels_share{sfx}"] = round((lt["sa3"] + lt["in0"]) / total, 4)
+                case[f"wide_linears_share{sfx}"] = round((lt["sa3_linear"] + lt["in0_linear"]) / total, 4)
             res["cases"].append(case)
     print(json.dumps(res))
-    if "bf16" in a.precision and not a.ragged and not ((pointnet_only or pn_partseg_only or pointconv_only or pc_partseg_only) and a.frozen_only):
+    if a.wide:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "infer_pointconv_partseg_wide_bench_line.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
+    elif "bf16" in a.precision and not a.ragged and not ((pointnet_only or pn_partseg_only or pointconv_only or pc_partseg_only) and a.frozen_only):
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         name = ("infer_pointnet_bf16_bench_line.json" if pointnet_only else
                 "infer_pointnet_partseg_bf16_bench_line.json" if pn_partseg_only else
