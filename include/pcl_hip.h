@@ -954,6 +954,41 @@ int pcl_pointconv_wide_level_infer_f32(const float* xyz, const float* new_xyz, c
                                        const float* const* shift, float slope, const float* nets, int M, float* out, int ldo,
                                        void* stream);
 
+/* ---- Frozen inference: one X-conv stage of PointCNN in evaluation mode as ONE launch (csrc/infer_xconv.hip) --------------
+ * misc/layers.py:340-517 (PointCNN.execute :393-402 and XConv.execute :472-509 up to and including the depthwise conv of SepConv
+ * :151) as evaluated by net.eval().  Per region r = b*P + p (representative rep[r], neighbours idx[k] = knn[b, k*D, p], k < K):
+ *     d[k]  = pts[b*N + idx[k]] - rep[r]                                          (the subtraction of pcl_group_f32)
+ *     h1[k] = relu(sa * (Wa d[k]) + ta),   h2[k] = relu(sb * (Wb h1[k]) + tb)     the lift 3 -> C_mid -> C_mid
+ *     x0 = relu(W0 [d[0] .. d[K-1]]),  x1 = relu(sc1 * (W1 x0) + sh1),  X = W2 x1 + b2   (X [K, K], row-major in the K*K outputs)
+ *     FX = X [h2 | relu(fs * feat[b*N + idx[.]] + ft)],   out[r * ldo + c*dm + j] = bias[c*dm + j] + sum_k wd[c, j, k] FX[k, c],   c < C_mid + C2
+ * x_trans_0 activates and THEN normalises (misc/layers.py:196-204); its BatchNorm affine (s0, t0) is the caller's to fold:
+ * W1 = W1' diag(s0) and sh1 = shift1' + scale1' * (W1' t0), with (W1', scale1', shift1') the eval constants of x_trans_1.
+ * pts [B*N, 3], rep [B*P, 3], feat [B*N, C2] (the per-point dense BEFORE its BatchNorm; fs, ft [C2] its eval scale and shift), knn [B, K*D, P] int32 AS pcl_knn_f32 WRITES IT (rows 0, D, 2D, ... are read; D = 1
+ * reads pre-sliced lists) with every entry in [0, N) (a precondition: an entry outside it is clamped to the nearest end so that no
+ * load leaves the cloud, and nothing is reported).  Wa [C_mid, 3]; sa, ta, sb, tb [C_mid]; Wb [C_mid', C_mid'] with C_mid' = C_mid
+ * rounded up to 16, pad rows and columns zero; W0 [K*K, D0'] with D0' = 3K rounded up to 16, column 3k + i the weight of d[k][i], pad
+ * columns zero; W1, W2 [K*K, K*K]; sc1, sh1, b2 [K*K]; wd [C, dm, K] and bias [C * dm] as for pcl_xconv_core_fwd_f32.  out
+ * [B*P, ldo], ldo >= C * dm and a multiple of 4.  Wb, W0, W1, W2 and out MUST be 16-byte aligned: the kernel moves them in
+ * 16-byte pieces and has no other form, so this is the caller's precondition (pointcloudlib_amd/inference.py raises before the
+ * call).  Every dot product of the lift's second layer and of the X-transform runs on v_mfma_f32_16x16x4_f32 (fp32 fma chains; k
+ * permuted inside blocks of 16); FX and the taps are the fmaf chains of pcl_xconv_core_fwd_f32 in its order.  Neither X, the lift
+ * nor a gathered tensor is stored.  A region's result depends only on its own rows (not on B, on the region's place in the launch
+ * or on how many regions a workgroup owns); no atomics, two calls give identical bits; all C * dm outputs of every region are
+ * written and none beyond them.  Kernels exist
+ * for (K, C_mid, C2, dm) = (8, 12, 24, 16), (12, 24, 48, 2), (16, 48, 96, 2), (16, 96, 192, 2) -- the stages of
+ * networks/cls/pointcnn.py -- and for nothing else: pcl_xconv_level_infer_supported answers for any query; any other shape returns
+ * PCL_EINVAL ("no kernel") before any launch. */
+int pcl_xconv_level_infer_supported(int K, int C_mid, int C2, int dm);
+/* How many consecutive regions one workgroup of a launch over R regions owns (whole 16-region tiles, at most 8; 0 for a K without
+ * a kernel or R < 1).  It depends on the device's compute-unit count; no result depends on it. */
+int pcl_xconv_level_infer_region_tile(int K, int R);
+/* reference: misc/layers.py:393-402 + :472-509 + :151 in eval mode */
+int pcl_xconv_level_infer_f32(const float* pts, const float* rep, const float* feat, const float* fs, const float* ft,
+                              const int32_t* knn, int B, int N, int P, int K, int D, int C_mid, int C2, int dm, const float* Wa,
+                              const float* sa, const float* ta, const float* Wb, const float* sb, const float* tb, const float* W0,
+                              const float* W1, const float* sc1, const float* sh1, const float* W2, const float* b2, const float* wd,
+                              const float* bias, float* out, int ldo, void* stream);
+
 /* ---- Frozen inference: one PointNet++ feature-propagation level in evaluation mode as ONE launch ------------------------
  * misc/ops.py:54-107 (PointNetFeaturePropagation.execute: 3-NN inverse-distance interpolation, concat with the skip features,
  * conv/bn/relu x L) as evaluated by net.eval(), optionally followed by the part-seg head of networks/seg/pointnet2_partseg.py:151-176

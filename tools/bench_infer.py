@@ -61,6 +61,12 @@ share of sa3 + in0 and of their two Linears; with ``--precision fp32 bf16`` the 
 ``wide_below_frozen_min_bf16``, ``frozen_level_ms_bf16_wide``).  The line goes to
 profiles/infer_pointconv_partseg_wide_bench_line.json.
 
+``--nets pointcnn`` compares ``net.eval()`` under ``no_grad`` with ``FrozenPointCNN(net)`` (B in {32, 256}, N = 1024; both forms read
+the same [B,N,3] tensor and run their own FPS and k-NN), with the peak memory of both, ``frozen_below_eval_min`` (the frozen median
+against ``net.eval()``'s window minimum) and, per stage, the time of the ``pcl_xconv_level_infer_f32`` call between two device events
+(``level_kernel_ms``, with its flops; ``level_kernel_share``: their sum over the frozen median); the line goes to
+profiles/infer_pointcnn_bench_line.json.  fp32 only.
+
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
 (a) ``dense`` frozen at N, (b) ``ragged_full`` with every length = N, (c) ``ragged`` with the drawn lengths, (d) ``loop``: B calls
@@ -231,7 +237,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, nargs="+", default=None, help="default: 32 256 (cls), 16 64 (part-seg, pointnet_partseg), 8 32 256 (pointnet)")
     ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg", "pointnet", "pointnet_partseg", "pointconv",
-                                                                                "pointconv_partseg"])
+                                                                                "pointconv_partseg", "pointcnn"])
     ap.add_argument("--points", type=int, default=None, help="default: 1024 (cls), 2048 (part-seg)")
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
     ap.add_argument("--precision", nargs="+", default=["fp32"], choices=["fp32", "bf16"],
@@ -245,7 +251,10 @@ def main():
     from pointcloudlib_amd.inference import frozen
     from pointcloudlib_amd.networks.cls.pointnet2 import PointNet2_cls, PointNetMSG
     dev = torch.device("cuda")
-    cls_only = all(k in ("ssg", "msg", "pointnet", "pointconv") for k in a.nets)
+    cls_only = all(k in ("ssg", "msg", "pointnet", "pointconv", "pointcnn") for k in a.nets)
+    pointcnn_only = all(k == "pointcnn" for k in a.nets)
+    if "pointcnn" in a.nets and (a.ragged or "bf16" in a.precision):
+        raise SystemExit("bench_infer.py: FrozenPointCNN is fp32 only and has no ragged form")
     pointnet_only = all(k == "pointnet" for k in a.nets)
     pn_partseg_only = all(k == "pointnet_partseg" for k in a.nets)
     pointconv_only = all(k == "pointconv" for k in a.nets)
@@ -276,6 +285,10 @@ def main():
             from pointcloudlib_amd.inference import FrozenPointConv
             from pointcloudlib_amd.networks.cls.pointconv import PointConvDensityClsSsg
             net = PointConvDensityClsSsg().to(dev).eval()
+        elif kind == "pointcnn":
+            from pointcloudlib_amd.inference import FrozenPointCNN
+            from pointcloudlib_amd.networks.cls.pointcnn import PointCNNcls
+            net = PointCNNcls().to(dev).eval()
         elif pn_seg:
             from pointcloudlib_amd.inference import FrozenPointNetPartseg
             from pointcloudlib_amd.networks.seg.pointnet_partseg import PointNet_partseg
@@ -300,6 +313,9 @@ def main():
         elif kind == "pointconv":
             fpc = FrozenPointConv(net)
             fnet_bf16 = fpc16 = FrozenPointConv(net, precision="bf16") if "bf16" in a.precision else None
+        elif kind == "pointcnn":
+            fcnn = FrozenPointCNN(net)
+            fnet_bf16 = None
         elif pc_seg:
             fpcs = FrozenPointConvPartseg(net)
             fnet_bf16 = fpcs16 = FrozenPointConvPartseg(net, precision="bf16") if "bf16" in a.precision else None
@@ -365,6 +381,14 @@ def main():
                 def frozen_bf16_fwd():
                     return fpc16(x_cf, sampling=samp)
 
+            if kind == "pointcnn":
+                def eval_fwd(net=net):
+                    with torch.no_grad():
+                        return net(xyz)
+
+                def frozen_fwd():
+                    return fcnn(xyz)
+
             if pc_seg:
                 samp = net.precompute_sampling(xyz)           # one sampling handle feeds both forms
 
@@ -427,9 +451,9 @@ def main():
                 case["speedup"] = round(case["eval_ms"] / case["frozen_ms"], 3)
                 if seg:
                     case["speedup_vs_acc0"] = round(case["eval_acc0_ms"] / case["frozen_ms"], 3)
-                if pc_seg:
+                if pc_seg or kind == "pointcnn":
                     case["frozen_below_eval_min"] = case["frozen_ms"] < case["eval_ms_min"]
-                if seg or pn_seg or pc_seg or kind == "pointconv":
+                if seg or pn_seg or pc_seg or kind in ("pointconv", "pointcnn"):
                     case["mem_ratio"] = round(case["eval_peak_mib"] / max(case["frozen_peak_mib"], 0.1), 1)
                 with torch.no_grad():
                     case["max_abs_logit_diff"] = float((eval_fwd() - frozen_fwd()).abs().max())
@@ -451,6 +475,10 @@ def main():
                 case["level_kernel_ms"] = _pointconv_level_times(frozen_fwd)
             if kind == "pointconv" and fnet_bf16 is not None:
                 case["level_kernel_ms_bf16"] = _pointconv_level_times(frozen_bf16_fwd, "pcl_pointconv_level_infer_bf16_f32")
+            if kind == "pointcnn" and "frozen" in times:
+                case["levels"] = fcnn.levels
+                lk = case["level_kernel_ms"] = _pointconv_level_times(frozen_fwd, "pcl_xconv_level_infer_f32")
+                case["level_kernel_share"] = round(sum(v["ms"] for v in lk.values()) / case["frozen_ms"], 4)
             if pc_seg and "frozen" in times:
                 case["levels"] = fpcs.levels
                 case["level_kernel_ms"] = _pointconv_level_times(frozen_fwd, "pcl_pointconv_seg_level_infer_f32")
@@ -503,6 +531,10 @@ def main():
     elif pc_partseg_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "infer_pointconv_partseg_bench_line.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
+    elif pointcnn_only and not a.frozen_only:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "infer_pointcnn_bench_line.json"), "w") as f:
             f.write(json.dumps(res) + "\n")
     elif pn_partseg_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
