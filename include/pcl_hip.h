@@ -976,7 +976,7 @@ int pcl_pointconv_wide_level_infer_f32(const float* xyz, const float* new_xyz, c
  * or on how many regions a workgroup owns); no atomics, two calls give identical bits; all C * dm outputs of every region are
  * written and none beyond them.  Kernels exist
  * for (K, C_mid, C2, dm) = (8, 12, 24, 16), (12, 24, 48, 2), (16, 48, 96, 2), (16, 96, 192, 2) -- the stages of
- * networks/cls/pointcnn.py -- and for nothing else: pcl_xconv_level_infer_supported answers for any query; any other shape returns
+ * networks/cls/pointcnn.py --, for the two part-seg shapes named below and for nothing else: pcl_xconv_level_infer_supported answers for any query; any other shape returns
  * PCL_EINVAL ("no kernel") before any launch. */
 int pcl_xconv_level_infer_supported(int K, int C_mid, int C2, int dm);
 /* How many consecutive regions one workgroup of a launch over R regions owns (whole 16-region tiles, at most 8; 0 for a K without
@@ -988,6 +988,25 @@ int pcl_xconv_level_infer_f32(const float* pts, const float* rep, const float* f
                               const float* sa, const float* ta, const float* Wb, const float* sb, const float* tb, const float* W0,
                               const float* W1, const float* sc1, const float* sh1, const float* W2, const float* b2, const float* wd,
                               const float* bias, float* out, int ldo, void* stream);
+/* The stages of networks/seg/pointcnn_partseg.py (csrc/infer_xconv_seg.hip).  The tap form above also has
+ * kernels for (K, C_mid, C2, dm) = (12, 64, 128, 1) -- encoder_1 and decoder_2 -- and (8, 12, 25, 1) -- decoder_3: 37 columns, so
+ * ldo >= 40; feat rows have the odd stride 25, the gather is scalar.  At dm = 1 an output is stored as one float and out needs
+ * no more than its natural alignment.
+ * The FX form: everything above up to FX, and NO taps --
+ *     out[r * ldo + k * C + c] = FX[k, c],   k < K, c < C = C_mid + C2        (ldo >= K * C and a multiple of 4)
+ * -- the same fmaf chains in the same order as the tap form's FX, the same operands with the same preconditions (wd and bias
+ * aside), the same numeric contract; all K * C outputs of every region are written and none beyond them.  It is for a stage
+ * whose depth multiplier exceeds K: in evaluation mode the taps and the pointwise conv are two linear maps with nothing between
+ * them, and a frozen evaluator contracts FX with their product [C_out, K*C] (pointcloudlib_amd/inference.py: fold_taps) instead
+ * of writing C * dm columns per region.  One kernel, (K, C_mid, C2) = (8, 64, 128): encoder_0 (dm = 86);
+ * pcl_xconv_level_infer_fx_supported answers for any query, any other shape returns PCL_EINVAL ("no kernel") before any launch. */
+int pcl_xconv_level_infer_fx_supported(int K, int C_mid, int C2);
+/* reference: misc/layers.py:393-402 + :472-505 in eval mode */
+int pcl_xconv_level_infer_fx_f32(const float* pts, const float* rep, const float* feat, const float* fs, const float* ft,
+                                 const int32_t* knn, int B, int N, int P, int K, int D, int C_mid, int C2, const float* Wa,
+                                 const float* sa, const float* ta, const float* Wb, const float* sb, const float* tb,
+                                 const float* W0, const float* W1, const float* sc1, const float* sh1, const float* W2,
+                                 const float* b2, float* out, int ldo, void* stream);
 
 /* ---- Frozen inference: one PointNet++ feature-propagation level in evaluation mode as ONE launch ------------------------
  * misc/ops.py:54-107 (PointNetFeaturePropagation.execute: 3-NN inverse-distance interpolation, concat with the skip features,

@@ -13,6 +13,8 @@
 - ``FrozenPointConvPartseg``: ``networks.seg.pointconv_partseg.PointConvDensity_partseg``; csrc/infer_pointconv.hip and
   csrc/infer_pointconv_seg_bf16.hip, csrc/infer_pointconv_wide.hip; DESIGN.md sections 26, 27 (bf16) and 28 (``wide_levels``).
 - ``FrozenPointCNN``: ``networks.cls.pointcnn.PointCNNcls``; csrc/infer_xconv.hip; DESIGN.md section 29 (fp32 only).
+- ``FrozenPointCNNPartseg``: ``networks.seg.pointcnn_partseg.PointCNN_partseg``; csrc/infer_xconv.hip and csrc/infer_xconv_seg.hip;
+  DESIGN.md section 30 (fp32 only).
 
 All but the two PointNet++ evaluators are constructed directly: ``frozen()`` keeps its PointNet++ dispatch."""
 import copy
@@ -25,18 +27,19 @@ from .misc.head import MAX_ROWS, fc_head
 from .misc.layers import PointwiseMLP
 from .misc.ops import (_lengths, _p, _stream, group_all, group_points, knn_indices, mlp_segment_max, pack_rows, packed_layout,
                        three_interpolate, three_nn, unpack_rows)
-from .misc.pointcnn import Dense_Conv1d, RandPointCNN
+from .misc.pointcnn import Dense_Conv1d, RandPointCNN, RandPointCNN_Decoder
 from .misc.pointconv_utils import (DensityNet, PointConvDensitySetAbstraction, PointConvDensitySetInterpolation, WeightNet, _linear_flush,
                                    _pointconv_linear, compute_density, sample_level)
 from .networks.cls.pointcnn import PointCNNcls
 from .networks.cls.pointconv import PointConvDensityClsSsg
 from .networks.cls.pointnet import PointNet
 from .networks.cls.pointnet2 import PointNet2_cls, SamplingPrefetch
+from .networks.seg.pointcnn_partseg import PointCNN_partseg
 from .networks.seg.pointconv_partseg import PointConvDensity_partseg
 from .networks.seg.pointnet2_partseg import PointNet2_partseg
 from .networks.seg.pointnet_partseg import PointNet_partseg
 
-__all__ = ["frozen", "FrozenPointCNN", "FrozenPointConv", "FrozenPointConvPartseg", "FrozenPointNet", "FrozenPointNet2", "FrozenPointNet2Partseg", "FrozenPointNetPartseg"]
+__all__ = ["frozen", "FrozenPointCNN", "FrozenPointCNNPartseg", "FrozenPointConv", "FrozenPointConvPartseg", "FrozenPointNet", "FrozenPointNet2", "FrozenPointNet2Partseg", "FrozenPointNetPartseg"]
 
 
 PRECISIONS = ("fp32", "bf16")
@@ -1174,15 +1177,21 @@ def _relu_mlp(mlp, layers, bn=True, act=True):
 def _xconv_fusable(stage):
     """A ``RandPointCNN`` of the usual parts (per-point dense, ReLU everywhere, BatchNorm where the stock modules have one) whose
     shape ``pcl_xconv_level_infer_f32`` has a kernel for."""
-    if not isinstance(stage, RandPointCNN) or stage.pointcnn.dense is None:
+    if not isinstance(stage, RandPointCNN) or not _xconv_stock_parts(stage.pointcnn):
         return False
     pc, xc = stage.pointcnn, stage.pointcnn.x_conv
-    ec = xc.end_conv
-    if not (xc.dims == 3 and _relu_mlp(pc.dense.mlp, 1) and _relu_mlp(xc.dense, 2) and _relu_mlp(xc.x_trans_0.linear, 1, bn=False)
-            and xc.x_trans_0.bn is not None and _relu_mlp(xc.x_trans_1.mlp, 1) and _relu_mlp(xc.x_trans_2.mlp, 1, bn=False, act=False)
-            and ec.backend == "auto" and ec.bn is not None and _relu_mlp(ec.pointwise, 1, bn=False) and pc.dense.mlp.biases is not None):
+    return bool(_lib.size_query("pcl_xconv_level_infer_supported", int(pc.K), int(xc.C_mid), int(xc.C_in), int(xc.end_conv.dm)))
+
+
+def _xconv_stock_parts(pc):
+    """A ``PointCNN`` of the usual parts: per-point dense, ReLU everywhere, BatchNorm where the stock modules have one."""
+    if pc.dense is None:
         return False
-    return bool(_lib.size_query("pcl_xconv_level_infer_supported", int(pc.K), int(xc.C_mid), int(xc.C_in), int(ec.dm)))
+    xc = pc.x_conv
+    ec = xc.end_conv
+    return (xc.dims == 3 and _relu_mlp(pc.dense.mlp, 1) and _relu_mlp(xc.dense, 2) and _relu_mlp(xc.x_trans_0.linear, 1, bn=False)
+            and xc.x_trans_0.bn is not None and _relu_mlp(xc.x_trans_1.mlp, 1) and _relu_mlp(xc.x_trans_2.mlp, 1, bn=False, act=False)
+            and ec.backend == "auto" and ec.bn is not None and _relu_mlp(ec.pointwise, 1, bn=False) and pc.dense.mlp.biases is not None)
 
 
 class _FusedXConv:
@@ -1238,7 +1247,10 @@ class _FusedXConv:
             rows = _rows_gemm(x, self.Wd, self.bd, self.ones, self.zeros, 0.0, tag="pt")
         else:
             rows = _rows_gemm(x, self.Wd, self.bd, tag="pt")
-        return _rows_gemm(self.contract(pts, rep, rows, knn), self.Wp)
+        return self.pointwise(self.contract(pts, rep, rows, knn))
+
+    def pointwise(self, D):
+        return _rows_gemm(D, self.Wp)
 
 
 class FrozenPointCNN(_Frozen):
@@ -1344,3 +1356,218 @@ class FrozenPointCNN(_Frozen):
         y = _rows_gemm(y, self.hW[1], self.hb[1], *self.hc[0], 0.0)
         y = _rows_gemm(y, self.hW[2], self.hb[2], *self.hc[1], 0.0)
         return feats, y.view(B, P, -1).mean(dim=1)
+
+
+# ---------------------------------------------------------------------------------------------- PointCNN part segmentation
+def fold_taps(wd, bias_d, Wp):
+    """The depthwise taps of a ``SepConv`` folded into its pointwise conv, in fp64: in evaluation mode the two are linear maps with
+    nothing between them, so ``raw[o] = sum_{c,j} Wp[o, c*dm+j] (bias_d[c*dm+j] + sum_k wd[c,j,k] FX[k,c]) = bf[o] + sum_{k,c}
+    Wf[o, k*C+c] FX[k,c]`` with ``Wf[o, k*C+c] = sum_j Wp[o, c*dm+j] wd[c,j,k]`` and ``bf = Wp bias_d``.  wd [C, dm, K], bias_d
+    [C*dm], Wp [C_out, C*dm] -> (Wf [C_out, K*C], bf [C_out]).  The contraction shrinks from C*dm to K*C columns per region: worth
+    it where dm > K (``encoder_0`` of PointCNN_partseg: dm = 86, K = 8)."""
+    wd, bias_d, Wp = wd.detach().double(), bias_d.detach().double(), Wp.detach().double()
+    C, dm, K = wd.shape
+    Wf = torch.einsum("ocj,cjk->okc", Wp.reshape(Wp.shape[0], C, dm), wd).reshape(Wp.shape[0], K * C)
+    return Wf.contiguous(), Wp @ bias_d
+
+
+def fold_conv_fuse(fuse, affines):
+    """``conv_fuse`` of a ``RandPointCNN_Decoder`` reads ``cat(stage output, skip)``; where both are ``s * relu(raw) + t`` their
+    affines (``affines``: [(s, t), (s, t)] in fp64, the stage's first) fold into the two column blocks of its weight
+    (``fold_affine_into_linear`` on the concatenated scale and shift) -> (W', b') in fp64, to be applied to ``relu(cat(raw,
+    raw_skip))``."""
+    mlp = fuse.mlp
+    return fold_affine_into_linear(mlp.weights[0], mlp.biases[0], torch.cat([a[0] for a in affines]), torch.cat([a[1] for a in affines]))
+
+
+def _xconv_seg_form(stage):
+    """The plan of a stage of PointCNN_partseg (``RandPointCNN`` or ``RandPointCNN_Decoder``): ``"fx"`` -- the FX form of the level
+    kernel and the taps folded into the pointwise weight -- where dm > K and that shape has a kernel; else ``"taps"`` where the tap
+    form has one; else ``None`` (the stage's own module runs), as for a stage whose parts are not the stock ones."""
+    if not isinstance(stage, (RandPointCNN, RandPointCNN_Decoder)) or not _xconv_stock_parts(stage.pointcnn):
+        return None
+    if isinstance(stage, RandPointCNN_Decoder) and not (isinstance(stage.conv_fuse, Dense_Conv1d) and _relu_mlp(stage.conv_fuse.mlp, 1)
+                                                        and stage.conv_fuse.mlp.biases is not None):
+        return None
+    pc, xc = stage.pointcnn, stage.pointcnn.x_conv
+    K, Cm, C2, dm = int(pc.K), int(xc.C_mid), int(xc.C_in), int(xc.end_conv.dm)
+    if dm > K and _lib.size_query("pcl_xconv_level_infer_fx_supported", K, Cm, C2):
+        return "fx"
+    return "taps" if _lib.size_query("pcl_xconv_level_infer_supported", K, Cm, C2, dm) else None
+
+
+class _FusedXConvSeg(_FusedXConv):
+    """``_FusedXConv`` for the stages of PointCNN_partseg.  ``form == "fx"``: ``pcl_xconv_level_infer_fx_f32`` writes FX [B*P, K*C]
+    and one GEMM with ``fold_taps``' (Wf, bf) gives ``raw`` (the taps and the pointwise weight themselves are not kept).
+    ``"taps"``: the tap form with the row stride of D padded to a multiple of 4 (decoder_3: 37 columns in 40; the pointwise
+    weight gets zero columns, D's pad columns are zeros)."""
+
+    def __init__(self, stage, in_affine, form):
+        super().__init__(stage, in_affine)
+        self.form = form
+        C = self.C_mid + self.C2
+        if form == "fx":
+            ec = stage.pointcnn.x_conv.end_conv
+            Wf, bf = fold_taps(ec.depthwise, ec.depthwise_bias, ec.pointwise.weights[0])
+            self.Wf, self.bf = Wf.float().contiguous(), bf.float().contiguous()
+            self.wd = self.bias = self.Wp = None
+            self.ldo = self.K * C
+        else:
+            self.ldo = -(-C * self.dm // 4) * 4
+            if self.ldo != C * self.dm:
+                Wp = torch.zeros((self.Wp.shape[0], self.ldo), dtype=torch.float32, device=self.Wp.device)
+                Wp[:, :C * self.dm] = self.Wp
+                self.Wp = Wp
+
+    def contract(self, pts, rep, rows, knn):
+        """The fused launch -> FX [B*P, K*C] (``"fx"``) or D [B*P, ldo] (``"taps"``)."""
+        B, N, _ = pts.shape
+        P = rep.shape[1]
+        K, Cm, C, dm = self.K, self.C_mid, self.C_mid + self.C2, self.dm
+        fx = self.form == "fx"
+        cols = K * C if fx else C * dm
+        out = (torch.empty if self.ldo == cols else torch.zeros)((B * P, self.ldo), dtype=torch.float32, device=pts.device)
+        if any(t.data_ptr() % 16 for t in (self.Wb, self.W0, self.W1, self.W2, out)):
+            raise ValueError("FrozenPointCNNPartseg: the X-conv kernel moves Wb, W0, W1, W2 and its output in 16-byte pieces: unaligned operand")
+        flops = 2 * B * P * (K * (3 * Cm + Cm * Cm) + 3 * K * K * K + 2 * K ** 4 + K * K * C + (0 if fx else K * C * dm))
+        head = (_p(pts), _p(rep), _p(rows), _p(self.fs), _p(self.ft), _p(knn), B, N, P, K, self.D, Cm, self.C2)
+        consts = (_p(self.Wa), _p(self.sa), _p(self.ta), _p(self.Wb), _p(self.sb), _p(self.tb), _p(self.W0), _p(self.W1), _p(self.sc1),
+                  _p(self.sh1), _p(self.W2), _p(self.b2))
+        prof = dict(algo_bytes=4 * B * P * (cols + K * (4 + self.C2)), algo_flops=flops)
+        if fx:
+            _lib.call("pcl_xconv_level_infer_fx_f32", *head, *consts, _p(out), self.ldo, _stream(), tag=f"xconvfx{K}x{C}", **prof)
+        else:
+            _lib.call("pcl_xconv_level_infer_f32", *head, dm, *consts, _p(self.wd), _p(self.bias), _p(out), self.ldo, _stream(),
+                      tag=f"xconv{K}x{C}x{dm}", **prof)
+        return out
+
+    def pointwise(self, D):
+        """What ``run`` (pts [B,N,3], rep [B,P,3] -- a decoder's: the finer level's points, P > N allowed --, x [B*N, C_in]) puts
+        behind the launch -> raw [B*P, C_out]."""
+        return _rows_gemm(D, self.Wf, self.bf) if self.form == "fx" else _rows_gemm(D, self.Wp)
+
+
+class _FuseConv:
+    """Snapshot of a decoder's ``conv_fuse`` (Linear + bias, BatchNorm, ReLU on ``cat(stage output, skip)``).  ``affines``: the
+    (s, t) of the two inputs in fp64, or None for an input that arrives as plain features.  With both, ``fold_conv_fuse`` folds
+    them into the weight and ``run`` takes the two ``raw`` tensors (ReLU in the GEMM's operand load); otherwise the weight is the
+    module's own and ``run`` takes features."""
+
+    def __init__(self, fuse, affines):
+        mlp = fuse.mlp
+        self.folded = all(a is not None for a in affines)
+        W, b = fold_conv_fuse(fuse, affines) if self.folded else (mlp.weights[0], mlp.biases[0])
+        self.W, self.b = (t.detach().float().contiguous().clone() for t in (W, b))
+        if self.folded:
+            self.ones, self.zeros = torch.ones(self.W.shape[1], device=self.W.device), torch.zeros(self.W.shape[1], device=self.W.device)
+        self.sc, self.sh = _eval_consts(mlp, 0, fold_bias=False)
+
+    def run(self, a, skip):
+        """a [R, C_out], skip [R, C_last] -> relu(bn(.)) [R, C_out], a stored feature."""
+        X = torch.cat((a, skip), dim=1)
+        Y = _rows_gemm(X, self.W, self.b, self.ones, self.zeros, 0.0) if self.folded else _rows_gemm(X, self.W, self.b)
+        out = torch.empty_like(Y)
+        _lib.call("pcl_bn_act_f32", _p(Y), _p(self.sc), _p(self.sh), 0.0, Y.shape[0], Y.shape[1], _p(out), _stream())
+        return out
+
+
+def _plain(d, affine):
+    """Features from what a stage hands on: ``d`` itself, or ``s * relu(raw) + t`` for a fused stage's ``raw``."""
+    return d if affine is None else torch.relu(d) * affine[0] + affine[1]
+
+
+class FrozenPointCNNPartseg(_Frozen):
+    """Frozen evaluator of ``networks.seg.pointcnn_partseg.PointCNN_partseg``: ``fnet(x [B,N,3], normal=None) -> [B, part_num, N]``,
+    the signature of ``net.forward`` (``normal`` is ignored there too); ``fnet.run(x)`` also returns the features of the eight
+    stages, channel-last (four encoders, then the four decoders' fused outputs).  Constructed directly; fp32 only.  DESIGN.md
+    section 30.
+
+    ``fnet.levels``: ``"fused"`` or ``"module"`` per stage, encoder_0 .. encoder_3, decoder_0 .. decoder_3 (``_xconv_seg_form``).
+    A fused stage is FPS where the module samples, ``pcl_knn_f32``, the per-point ``dense`` as one stats-free GEMM, ONE launch of
+    the level kernel and one GEMM.  encoder_0 (dm = 86 > K = 8) takes the FX form: the kernel writes ``FX [B*N, K*C = 1536]`` and
+    the GEMM contracts it with ``fold_taps``' weight -- the ``[B, N, 16512]`` tensor of the module and its 16512 -> 256 pointwise
+    conv do not exist.  The other fused stages (encoder_1, decoder_2, decoder_3) take the tap form.  A decoder's representatives
+    are the finer level's points, its points the coarser level's; no sampling.  Its ``conv_fuse`` is one stats-free GEMM on
+    ``cat(raw, raw_skip)`` with both trailing affines folded into the weight where both producers are fused (``_FuseConv``), then
+    BatchNorm + ReLU: a stored feature.  ``"module"``: an eval-mode copy of the stage's own module (the four K = 16 stages, whose
+    tiles do not fit the kernel's LDS plan, and any stage with a part that is not the stock one).
+
+    All folds are made in fp64 at ``refresh()`` and rounded once.  ``net`` itself is never modified (parameters, buffers,
+    ``training`` flags); a stale evaluator keeps its constants until ``refresh()``."""
+
+    NET = PointCNN_partseg
+
+    def __init__(self, net, precision="fp32"):
+        if precision != "fp32":
+            raise ValueError(f"FrozenPointCNNPartseg: fp32 only, got precision={precision!r}")
+        super().__init__(net, precision)
+
+    @torch.no_grad()
+    def refresh(self):
+        net = self.net
+        self.stages = [net.encoder_0, net.encoder_1, net.encoder_2, net.encoder_3, net.decoder_0, net.decoder_1, net.decoder_2, net.decoder_3]
+        self.plans, self.fuses, enc = [], [], []
+        affine = None                                                  # of what the next stage's dense reads
+        for i, stage in enumerate(self.stages):
+            form = _xconv_seg_form(stage)
+            skip = enc[7 - i] if i >= 4 else None                      # decoder_0 .. 3 fuse with encoder_3 .. 0; decoder_0 reads encoder_3
+            if form is None:
+                self.plans.append(("module", self._copy(i, stage)))
+                out = None
+            else:
+                plan = _FusedXConvSeg(stage, affine, form)
+                self.plans.append(("fused", plan))
+                out = plan.out_affine
+            if i < 4:
+                enc.append(out)
+                affine = out
+            else:
+                self.fuses.append(None if form is None else _FuseConv(stage.conv_fuse, [out, skip]))
+                affine = None                                          # a decoder hands on relu(bn(.)): plain rows
+        self.levels = [k for k, _ in self.plans]
+        return self
+
+    def __call__(self, x, normal=None):
+        return self._forward(x, False)[1]
+
+    def run(self, x, normal=None):
+        """-> ([features of the eight stages: [B, P, C]], logits [B, part_num, N])."""
+        return self._forward(x, True)
+
+    @torch.no_grad()
+    def _forward(self, x, want_feats):
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[2] != 3:
+            raise ValueError(f"FrozenPointCNNPartseg: x must be [B,N,3], got {tuple(getattr(x, 'shape', ()))}")
+        self._require_f32_gpu(x)
+        B = x.shape[0]
+        pts = x.contiguous()
+        cur, feats, enc = (pts, pts, None), [], []                     # (points [B,P,3], data [B,P,C], its affine or None)
+        for stage, (kind, plan) in zip(self.stages[:4], self.plans[:4]):
+            p, d, aff = cur
+            n = p.shape[1]
+            if kind == "fused":
+                rep = (stage.sampler(p) if 0 < plan.P < n else p).contiguous()
+                cur = (rep, plan.run(p, rep, d.reshape(B * n, -1)).view(B, rep.shape[1], -1), (plan.s, plan.t))
+            else:
+                rep, f = plan((p, _plain(d, aff)))
+                cur = (rep.contiguous(), f, None)
+            enc.append(cur)
+            if want_feats:
+                feats.append(_plain(cur[1], cur[2]))
+        low = enc[3]
+        for j, (kind, plan) in enumerate(self.plans[4:]):
+            (pl, dl, al), (ph, dh, ah) = low, enc[3 - j]
+            nh = ph.shape[1]
+            if kind == "fused":
+                fuse = self.fuses[j]
+                raw = plan.run(pl, ph, dl.reshape(B * pl.shape[1], -1))
+                if fuse.folded:
+                    f = fuse.run(raw, dh.reshape(B * nh, -1))
+                else:
+                    f = fuse.run(_plain(raw, (plan.s, plan.t)), _plain(dh, ah).reshape(B * nh, -1))
+                f = f.view(B, nh, -1)
+            else:
+                _, f = plan((pl, _plain(dl, al)), (ph, _plain(dh, ah)))
+            low = (ph, f, None)
+            feats.append(f)
+        return (feats if want_feats else []), low[1].permute(0, 2, 1)

@@ -67,6 +67,12 @@ against ``net.eval()``'s window minimum) and, per stage, the time of the ``pcl_x
 (``level_kernel_ms``, with its flops; ``level_kernel_share``: their sum over the frozen median); the line goes to
 profiles/infer_pointcnn_bench_line.json.  fp32 only.
 
+``--nets pointcnn_partseg`` compares ``net.eval()`` under ``no_grad`` with ``FrozenPointCNNPartseg(net)`` (B in {16, 64}, N = 2048; both
+forms read the same [B,N,3] tensor and run their own FPS and k-NN), with the peak memory of both, ``frozen_below_eval_min``, the
+plans (``levels``), the time of every ``pcl_xconv_level_infer_fx_f32`` / ``pcl_xconv_level_infer_f32`` call between two device events
+(``level_kernel_ms``) and device events around every stage and every fused ``conv_fuse`` (``frozen_stage_ms``; ``module_stages_share``:
+the stages that run as their own module over the sum); the line goes to profiles/infer_pointcnn_partseg_bench_line.json.  fp32 only.
+
 ``--ragged`` measures batches of clouds with different point counts instead (``frozen(net)(..., lengths=...)``): per net and batch,
 lengths drawn once with a fixed seed uniformly from [N/2, N] (the largest forced to N), and four forms in interleaved windows --
 (a) ``dense`` frozen at N, (b) ``ragged_full`` with every length = N, (c) ``ragged`` with the drawn lengths, (d) ``loop``: B calls
@@ -148,6 +154,47 @@ def _pointconv_level_times(fwd, entry="pcl_pointconv_level_infer_f32", repeats=5
         out[tag] = {"ms": round(r["avg_ms"], 4), "gflop": round(r["algo_flops"] / 1e9, 2),
                     "tflops": round(r["algo_flops"] / (r["avg_ms"] * 1e-3) / 1e12, 1)}
     return out
+
+
+def _pointcnn_partseg_stage_times(fnet, fwd, repeats=5):
+    """Device events around every stage of FrozenPointCNNPartseg forwards (a fused stage: k-NN, dense GEMM, the launch and the GEMM
+    behind it; a module stage: the whole module, a decoder's ``conv_fuse`` included) and around every fused ``conv_fuse``
+    (``<stage>_fuse``): average ms over ``repeats`` (the events' dispatch gaps are inside)."""
+    marks = []
+    names = ["encoder_0", "encoder_1", "encoder_2", "encoder_3", "decoder_0", "decoder_1", "decoder_2", "decoder_3"]
+
+    def timed(fn, key):
+        def wrapper(*args, **kw):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            out = fn(*args, **kw)
+            b.record()
+            marks.append((key, a, b))
+            return out
+        return wrapper
+
+    plans, saved = list(fnet.plans), []
+    for i, (kind, plan) in enumerate(plans):
+        if kind == "fused":
+            saved.append((plan, "run"))
+            plan.run = timed(plan.run, names[i])
+            if i >= 4:
+                saved.append((fnet.fuses[i - 4], "run"))
+                fnet.fuses[i - 4].run = timed(fnet.fuses[i - 4].run, names[i] + "_fuse")
+        else:
+            fnet.plans[i] = (kind, timed(plan, names[i]))
+    try:
+        for _ in range(repeats):
+            fwd()
+        torch.cuda.synchronize()
+    finally:
+        fnet.plans[:] = plans
+        for obj, attr in saved:
+            delattr(obj, attr)
+    out = {}
+    for key, a, b in marks:
+        out[key] = out.get(key, 0.0) + a.elapsed_time(b) / repeats
+    return {k: round(v, 4) for k, v in out.items()}
 
 
 def _partseg_level_times(fpcs, fwd, repeats=5, split=(7,)):
@@ -237,7 +284,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, nargs="+", default=None, help="default: 32 256 (cls), 16 64 (part-seg, pointnet_partseg), 8 32 256 (pointnet)")
     ap.add_argument("--nets", nargs="+", default=["ssg", "msg"], choices=["ssg", "msg", "partseg_ssg", "partseg_msg", "pointnet", "pointnet_partseg", "pointconv",
-                                                                                "pointconv_partseg", "pointcnn"])
+                                                                                "pointconv_partseg", "pointcnn", "pointcnn_partseg"])
     ap.add_argument("--points", type=int, default=None, help="default: 1024 (cls), 2048 (part-seg)")
     ap.add_argument("--frozen_only", action="store_true", help="run only the frozen form (for a kernel trace)")
     ap.add_argument("--precision", nargs="+", default=["fp32"], choices=["fp32", "bf16"],
@@ -253,8 +300,9 @@ def main():
     dev = torch.device("cuda")
     cls_only = all(k in ("ssg", "msg", "pointnet", "pointconv", "pointcnn") for k in a.nets)
     pointcnn_only = all(k == "pointcnn" for k in a.nets)
-    if "pointcnn" in a.nets and (a.ragged or "bf16" in a.precision):
-        raise SystemExit("bench_infer.py: FrozenPointCNN is fp32 only and has no ragged form")
+    pcnn_partseg_only = all(k == "pointcnn_partseg" for k in a.nets)
+    if ("pointcnn" in a.nets or "pointcnn_partseg" in a.nets) and (a.ragged or "bf16" in a.precision):
+        raise SystemExit("bench_infer.py: FrozenPointCNN and FrozenPointCNNPartseg are fp32 only and have no ragged form")
     pointnet_only = all(k == "pointnet" for k in a.nets)
     pn_partseg_only = all(k == "pointnet_partseg" for k in a.nets)
     pointconv_only = all(k == "pointconv" for k in a.nets)
@@ -270,7 +318,8 @@ def main():
         seg = kind.startswith("partseg")
         pn_seg = kind == "pointnet_partseg"
         pc_seg = kind == "pointconv_partseg"
-        N = a.points or (2048 if seg or pn_seg or pc_seg else 1024)
+        pcnn_seg = kind == "pointcnn_partseg"
+        N = a.points or (2048 if seg or pn_seg or pc_seg or pcnn_seg else 1024)
         torch.manual_seed(0)
         if seg:
             from pointcloudlib_amd.misc.layers import set_accumulation
@@ -289,6 +338,10 @@ def main():
             from pointcloudlib_amd.inference import FrozenPointCNN
             from pointcloudlib_amd.networks.cls.pointcnn import PointCNNcls
             net = PointCNNcls().to(dev).eval()
+        elif pcnn_seg:
+            from pointcloudlib_amd.inference import FrozenPointCNNPartseg
+            from pointcloudlib_amd.networks.seg.pointcnn_partseg import PointCNN_partseg
+            net = PointCNN_partseg().to(dev).eval()
         elif pn_seg:
             from pointcloudlib_amd.inference import FrozenPointNetPartseg
             from pointcloudlib_amd.networks.seg.pointnet_partseg import PointNet_partseg
@@ -316,6 +369,9 @@ def main():
         elif kind == "pointcnn":
             fcnn = FrozenPointCNN(net)
             fnet_bf16 = None
+        elif pcnn_seg:
+            fcnn = FrozenPointCNNPartseg(net)
+            fnet_bf16 = None
         elif pc_seg:
             fpcs = FrozenPointConvPartseg(net)
             fnet_bf16 = fpcs16 = FrozenPointConvPartseg(net, precision="bf16") if "bf16" in a.precision else None
@@ -335,7 +391,7 @@ def main():
         else:
             fnet = frozen(net)
             fnet_bf16 = frozen(net, precision="bf16") if "bf16" in a.precision else None
-        for B in a.batch or ([16, 64] if seg or pn_seg or pc_seg else [8, 32, 256] if kind == "pointnet" else [32, 256]):
+        for B in a.batch or ([16, 64] if seg or pn_seg or pc_seg or pcnn_seg else [8, 32, 256] if kind == "pointnet" else [32, 256]):
             xyz = torch.from_numpy(synth.gauss_ball(B, N, 1)).to(dev)
             nrm = torch.from_numpy(synth.unit_normals(B, N, 2)).to(dev)
             extra = ()
@@ -381,7 +437,7 @@ def main():
                 def frozen_bf16_fwd():
                     return fpc16(x_cf, sampling=samp)
 
-            if kind == "pointcnn":
+            if kind == "pointcnn" or pcnn_seg:
                 def eval_fwd(net=net):
                     with torch.no_grad():
                         return net(xyz)
@@ -440,7 +496,7 @@ def main():
             for w in range(a.windows):
                 for name, fn in (forms if w % 2 == 0 else forms[::-1]):
                     times[name].append(_window(fn, a.iters))
-            case = {"net": kind, "B": B, "N": N} if seg or pn_seg or pc_seg else {"net": kind, "B": B}
+            case = {"net": kind, "B": B, "N": N} if seg or pn_seg or pc_seg or pcnn_seg else {"net": kind, "B": B}
             for name, fn in forms:
                 case[f"{name}_ms"] = round(statistics.median(times[name]), 4)
                 case[f"{name}_ms_min"] = round(min(times[name]), 4)
@@ -451,9 +507,9 @@ def main():
                 case["speedup"] = round(case["eval_ms"] / case["frozen_ms"], 3)
                 if seg:
                     case["speedup_vs_acc0"] = round(case["eval_acc0_ms"] / case["frozen_ms"], 3)
-                if pc_seg or kind == "pointcnn":
+                if pc_seg or pcnn_seg or kind == "pointcnn":
                     case["frozen_below_eval_min"] = case["frozen_ms"] < case["eval_ms_min"]
-                if seg or pn_seg or pc_seg or kind in ("pointconv", "pointcnn"):
+                if seg or pn_seg or pc_seg or pcnn_seg or kind in ("pointconv", "pointcnn"):
                     case["mem_ratio"] = round(case["eval_peak_mib"] / max(case["frozen_peak_mib"], 0.1), 1)
                 with torch.no_grad():
                     case["max_abs_logit_diff"] = float((eval_fwd() - frozen_fwd()).abs().max())
@@ -479,6 +535,13 @@ def main():
                 case["levels"] = fcnn.levels
                 lk = case["level_kernel_ms"] = _pointconv_level_times(frozen_fwd, "pcl_xconv_level_infer_f32")
                 case["level_kernel_share"] = round(sum(v["ms"] for v in lk.values()) / case["frozen_ms"], 4)
+            if pcnn_seg and "frozen" in times:
+                case["levels"] = fcnn.levels
+                case["level_kernel_ms"] = {**_pointconv_level_times(frozen_fwd, "pcl_xconv_level_infer_fx_f32"),
+                                           **_pointconv_level_times(frozen_fwd, "pcl_xconv_level_infer_f32")}
+                st = case["frozen_stage_ms"] = _pointcnn_partseg_stage_times(fcnn, frozen_fwd)
+                names = [n for n in st if not n.endswith("_fuse")]
+                case["module_stages_share"] = round(sum(st[n] for n, k in zip(names, fcnn.levels) if k == "module") / sum(st.values()), 4)
             if pc_seg and "frozen" in times:
                 case["levels"] = fpcs.levels
                 case["level_kernel_ms"] = _pointconv_level_times(frozen_fwd, "pcl_pointconv_seg_level_infer_f32")
@@ -535,6 +598,10 @@ def main():
     elif pointcnn_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "infer_pointcnn_bench_line.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
+    elif pcnn_partseg_only and not a.frozen_only:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "infer_pointcnn_partseg_bench_line.json"), "w") as f:
             f.write(json.dumps(res) + "\n")
     elif pn_partseg_only and not a.frozen_only:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
